@@ -29,15 +29,28 @@ changes from its parent's squares (pv_sib_kernel): within 2e-5 of the full
 forward's logits / value (1e-4 of the reference's fp32 forward).
 --pv-precision fp32 runs the exact-f32 MFMA kernel.
 
-Also reported: the roofline of the PV forward (executed MFMA FLOP / kernel time,
-and the full-forward-equivalent rate), config 4 (planner plies) and the exact-fp32
-run as labelled secondaries, the prior-elided MCTS-only rate (moves identical
-without the priors), and the CPU baseline: the C oracle + torch-fp32 forwards
-("port") on the host cores -- P processes x 1 thread, 1 process x P threads, and
-config 1.
-Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1 either under torchrun
-(one rank per GPU from its env) or self-launched: without WORLD_SIZE in the
-environment, bench.py starts `python -m torch.distributed.run --nproc-per-node N`
+A plain run sets up, burns in, warms up, times the K steps and prints the line:
+the headline figure and what the timed steps themselves recorded (the roofline
+of the PV forward: executed MFMA FLOP / kernel time and the full-forward-
+equivalent rate; the share of searched plies).
+
+--full adds the measurements that take runs of their own: config 4 (planner
+plies), the exact-fp32 run and config 5 (training iterations/h) as labelled
+secondaries, the prior-elided MCTS-only rate (moves identical without the
+priors), and the CPU baseline: the C oracle + torch-fp32 forwards ("port") on
+the host cores -- P processes x 1 thread, 1 process x P threads, and config 1
+(BASELINE.md section 4).  Their own switches (--config4-steps, --fp32-steps,
+--config5-games, --no-elided, --no-cpu-baseline, ...) choose among them and do
+nothing without --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step left
+for its caller as DIR/<name>.npy (rank 0's shard; see dump_outputs).  The inputs
+are fixed by the arguments (seeded games, seeded weights), so two builds run with
+the same arguments can be compared array for array.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].
+N > 1 either under torchrun (one rank per GPU from its env) or self-launched:
+without WORLD_SIZE in the environment, bench.py starts `python -m torch.distributed.run --nproc-per-node N`
 as a child process and relays rank 0's line.  The line's `distributed` block names
 the backend, the world size and every rank's device (PCI address).
 """
@@ -256,11 +269,12 @@ def cpu_baseline(pool, procs, positions, sims, seed, budget_s):
     }
 
 
-def measure(eng, steps, warmup, burn_in, ws, ex=None):
+def measure(eng, steps, warmup, burn_in, ws, ex=None, want_boards=False):
     """Burn-in plies (no PV forward), `warmup` untimed steps, then EXACTLY `steps`
     timed steps bracketed by barrier + synchronize, MAX over ranks.  A step = every
     slot plays plies_per_step plies, then the PV forward of every node created,
-    then (N > 1) the record exchange."""
+    then (N > 1) the record exchange.  want_boards: also return the slots' positions
+    at the start of the timed window (the CPU baseline's start positions)."""
     def barrier():
         if ws > 1:
             dist.barrier()
@@ -290,7 +304,7 @@ def measure(eng, steps, warmup, burn_in, ws, ex=None):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    boards0, gids0 = eng.boards()  # timed-window start positions (for the CPU baseline)
+    boards0, gids0 = eng.boards() if want_boards else (None, None)  # timed-window start positions
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -309,7 +323,7 @@ def measure(eng, steps, warmup, burn_in, ws, ex=None):
     T = float(elapsed.item())
     leaves = [min(int(c["leaves"]), eng.leaf_cap) for c in ctrs]
     exec_per_board = None
-    if eng.tree:
+    if eng.tree and not any(t[6] + t[7] for t in tree):  # the kernels counted nothing: the model
         fl, nl = eng.tree_exec_flops()
         exec_per_board = fl / max(1, nl)
     pv_ms = [a.elapsed_time(b) for (a, b), _, _ in recs]
@@ -319,6 +333,86 @@ def measure(eng, steps, warmup, burn_in, ws, ex=None):
         "dropped": sum(int(c["leaves_dropped"]) + max(0, int(c["leaves"]) - eng.leaf_cap) for c in ctrs),
         "boards0": boards0, "gids0": gids0,
     }
+
+
+DUMP_SAMPLE = 8192  # leaves whose forward outputs --dump-outputs writes
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def _leaf_keys(rows, seed):
+    """One seeded 64-bit key per leaf board ([n,16] uint32 rows): the sample of
+    dump_outputs is chosen by board content, not by the board's place in the buffer."""
+    h = np.full(rows.shape[0], 0x9E3779B97F4A7C15 ^ (int(seed) & 0xFFFFFFFF), dtype=np.uint64)
+    for i in range(rows.shape[1]):
+        h ^= rows[:, i].astype(np.uint64)
+        h *= np.uint64(0x100000001B3)
+        h ^= h >> np.uint64(29)
+    return h
+
+
+def collect_outputs(eng, seed, sample=DUMP_SAMPLE):
+    """What the engine's last step left for its caller, as {name: float32 / float64 array}
+    in an order that does not depend on the run:
+
+    counters     [7]     the step's counters (COUNTER_DTYPE's fields, in order)
+    slot_state   [S,5]   per slot: game id, plies played, player to move, over, winner
+    slot_boards  [S,16]  per slot: the position after the step (8 black + 8 white words)
+    records      [R,21]  the (s, pi, z) records of the games the step finished, sorted by
+                         (game id, ply): game id, ply, move, player, z, 8 + 8 board words
+    and of the policy-value forward of every node the step's searches created, a sample:
+    the searches append their leaves in the order the wavefronts reach the buffer, which
+    differs from run to run, so the sample is the `sample` boards with the smallest seeded
+    key (_leaf_keys) among the boards that occur once, in key order --
+    leaves       [K,16]  the sampled boards (8 black + 8 white words)
+    leaf_kind    [K]     tree forward only: 0 root, 1 root child, 2 grandchild, 3 untagged
+    logits [K,225], value [K], probs [K,225]  float32;  prior [K,225]  float64."""
+    torch.cuda.synchronize()
+    c = eng.counters()
+    out = {"counters": np.array([float(c[k]) for k in COUNTER_DTYPE.names], dtype=np.float64)}
+    st, gids = eng.boards()
+    out["slot_state"] = np.stack([gids, st["n_moves"], st["player"], st["over"], st["winner"]],
+                                 axis=1).astype(np.float64)
+    out["slot_boards"] = np.concatenate([st["black"], st["white"]], axis=1).astype(np.float64)
+    recs = eng.records()
+    recs = recs[np.lexsort((recs["ply"], recs["game_id"]))]
+    head = np.stack([recs[k].astype(np.float64) for k in ("game_id", "ply", "move", "player", "z")], axis=1)
+    out["records"] = np.concatenate([head.reshape(len(recs), 5), recs["black"].astype(np.float64),
+                                     recs["white"].astype(np.float64)], axis=1)
+    if not eng.gather:
+        return out
+    n = min(int(c["leaves"]), eng.leaf_cap)
+    rows = eng.d_leaves[: n * 16].cpu().numpy().view(np.uint32).reshape(n, 16)
+    keys = _leaf_keys(rows, seed)
+    order = np.argsort(keys, kind="stable")
+    ks = keys[order]
+    once = np.ones(n, dtype=bool)
+    once[1:] &= ks[1:] != ks[:-1]
+    once[:-1] &= ks[:-1] != ks[1:]
+    sel = order[once][:sample]
+    idx = torch.from_numpy(sel).cuda()
+    out["leaves"] = rows[sel].astype(np.float64)
+    if eng.tree:
+        meta = eng.d_meta[:n].cpu().numpy()
+        m = meta[sel]
+        parent = meta[np.clip(m, 0, max(0, n - 1))]
+        out["leaf_kind"] = np.where(m == -1, 0, np.where(m < 0, 3, np.where(parent == -1, 1, 2))).astype(np.float32)
+    out["logits"] = eng.d_logits[: n * 225].view(n, 225)[idx].cpu().numpy()
+    out["value"] = eng.d_value[:n][idx].cpu().numpy()
+    out["probs"] = eng.d_probs[: n * 225].view(n, 225)[idx].cpu().numpy()
+    out["prior"] = eng.d_prior[: n * 225].view(n, 225)[idx].cpu().numpy()
+    return out
+
+
+def dump_outputs(eng, seed, directory):
+    """--dump-outputs: collect_outputs of the last timed step as DIRECTORY/<name>.npy."""
+    arrays = collect_outputs(eng, seed)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"dump-outputs: {len(arrays)} arrays, {total / 1e6:.1f} MB in {directory}")
 
 
 def config5(games, sims, seed, iterations=2):
@@ -545,6 +639,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondaries (config 4, exact fp32, config 5), the "
+                         "prior-elided run and the CPU baseline; without it their switches below do nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: the counters, the slots' positions, the finished "
+                         "games' records and a seeded sample of the policy-value outputs)")
     ap.add_argument("--slots", type=int, default=4096, help="concurrent games per GPU")
     ap.add_argument("--sims", type=int, default=200)
     ap.add_argument("--beta", type=float, default=0.0)
@@ -579,6 +680,9 @@ def main():
                     help="multi-rank plumbing only (rendezvous, device report, timing, JSON line) without a GPU")
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)  # CPU test: a failing rank
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -587,7 +691,7 @@ def main():
     rank, ws = gdist.init_from_env()
     pool = None
     procs = 0
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and ws == 1 and not args.no_cpu_baseline:
         # host worker processes come from a forkserver started before this process
         # touches the GPU (no process that initialised HIP forks or execs)
         import multiprocessing as mp
@@ -604,7 +708,7 @@ def main():
     base, stride = gdist.shard_ids(rank, ws, args.slots)
     P = args.plies_per_step
     gnw = None
-    if args.planner_steps or (ws == 1 and args.config4_steps):
+    if args.planner_steps or (full and ws == 1 and args.config4_steps):
         from gzero import planner_nets
         gnw = planner_nets.pack_planner_weights(planner_nets.init_graphnet_state(0), planner_nets.init_dqn_state(1))
 
@@ -623,7 +727,7 @@ def main():
     ex = gdist.RecordExchange(eng.record_cap, 2 * args.slots * P, "cuda", max_push=4 * args.slots * P) \
         if ws > 1 else None
     burn_in = args.burn_in
-    m = measure(eng, args.steps, args.warmup, burn_in, ws, ex)
+    m = measure(eng, args.steps, args.warmup, burn_in, ws, ex, want_boards=pool is not None)
     T = m["T"]
     value = m["moves"] / T
     half = args.steps // 2
@@ -685,11 +789,13 @@ def main():
                 "pending_after": [p for p, _ in every], "overflow": [o for _, o in every],
                 "note": "per rank (index = rank): records still queued after the window and records lost to "
                         "a full outbox; fixed-size RCCL all_gather_into_tensor per step, counts on the device"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.seed, args.dump_outputs)
     boards0, gids0 = m["boards0"], m["gids0"]
     del eng
 
     # ---- N = 1 secondaries: config 4 and the exact-fp32 forward (same burn-in)
-    if ws == 1 and args.config4_steps and not args.planner_steps:
+    if full and ws == 1 and args.config4_steps and not args.planner_steps:
         e4 = engine(0.2, 5, w, args.pv_mode if args.pv_precision == "f16x3" else "full")
         m4 = measure(e4, args.config4_steps, 2, burn_in, 1)
         gs = e4.gn_stats()
@@ -708,7 +814,7 @@ def main():
                          "searched without planner plies (the planner pipeline needs the GN forward per ply)"),
         }
         del e4
-    if ws == 1 and args.fp32_steps and args.pv_precision == "f16x3" and not args.planner_steps:
+    if full and ws == 1 and args.fp32_steps and args.pv_precision == "f16x3" and not args.planner_steps:
         w32 = PVWeights(weights.pack_pv_weights(sd), precision="fp32")
         e32 = engine(args.beta, 0, w32)
         m32 = measure(e32, args.fp32_steps, 1, burn_in, 1)
@@ -719,11 +825,11 @@ def main():
         del e32, w32
 
     # ---- N = 1 secondary: config 5 (training iterations per hour)
-    if ws == 1 and args.config5_games and not args.planner_steps:
+    if full and ws == 1 and args.config5_games and not args.planner_steps:
         out["config5"] = config5(args.config5_games, args.sims, args.seed)
 
     # ---- prior-elided run (same kernel, no PV gather / forward)
-    if not args.no_elided and not args.planner_steps:
+    if full and not args.no_elided and not args.planner_steps:
         el = SelfPlayEngine(n_slots=args.slots, num_simulations=args.sims, c_puct=1.6, exploration=0.05,
                             beta=args.beta, seed=args.seed, pv_weights=None, plies_per_step=10,
                             game_id_base=base, game_id_stride=stride)

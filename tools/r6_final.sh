@@ -15,7 +15,7 @@ tail -2 $out/pytest_gpu.log
 grep -h "tree vs full forward\|tree vs torch\|capacity fallbacks" $out/pytest_gpu.log || true
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { echo "smoke rc $?"; tail -20 $out/smoke.log; exit 1; }
 tail -1 $out/smoke.log
-timeout -k 10 900 python -u bench.py > $out/bench.json 2> $out/bench.err || { echo "bench rc $?"; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { echo "bench rc $?"; tail -20 $out/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$out/bench.json').read().strip().splitlines()[-1])
 print('headline', d['value'], d['ms_per_step'], 'frac', d['roofline']['frac'], 'config4', d['config4']['value'], 'config5', d['config5']['value'], d['config5']['selfplay_s'], d['config5']['sgd_s'])"
