@@ -15,6 +15,12 @@ fixed (seed, game_id) reproduces a game exactly, on any number of GPUs.
 With ``planner_steps > 0`` (the reference's default, 5) every rollout starts
 with that many BG-planner plies (ai_agent.py:265-274): the search runs as the
 batched pipeline of ``gz_plan_search`` with the AI's ``bg_planner`` nets.
+``search="puct"`` (opt-in; the default ``"reference"`` is everything above) runs
+the network-guided PUCT search of ``gz_puct_search`` on every ply instead: the
+model's priors steer selection and its value head replaces the rollout.  It has no
+opening book and no exploration move, ignores ``beta`` and ``planner_steps``, samples
+the move from the visit counts below ``temp_plies`` plies (default 0: always the most
+visited cell) and sets ``last_search_visits`` / ``last_root_value``.
 ``time_limit`` is accepted for compatibility; the GPU completes every
 simulation, so the reference's wall-clock cut-off (ai_agent.py:183-189) never
 applies.
@@ -36,7 +42,14 @@ class AlphaZeroGomokuAI:
     def __init__(self, player: int, difficulty: str = "medium", model_path: Optional[str] = None,
                  device: Optional[str] = None, beta: float = 0.2, planner_steps: int = 5,
                  time_limit: float = 5.0, time_reward_factor: float = 0.1, seed: Optional[int] = None,
-                 game_id: int = 0, compute_priors: bool = True):
+                 game_id: int = 0, compute_priors: bool = True, search: str = "reference",
+                 temp_plies: int = 0):
+        if search not in ("reference", "puct"):
+            raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
+        self.search = search
+        self.temp_plies = int(temp_plies)
+        self.last_search_visits = None  # puct: int32 [n, 225] root visit counts of the last call
+        self.last_root_value = None     # puct: the roots' mean value for the side to move
         self.player = player
         self.difficulty = difficulty
         self.name = f"AlphaZero_{difficulty}"
@@ -102,6 +115,8 @@ class AlphaZeroGomokuAI:
         """get_move for many boards in one batched search: board i draws from the
         streams of (self.seed, game_ids[i]), so the result equals get_move on each
         board with ``game_id = game_ids[i]``."""
+        if self.search == "puct":
+            return self._puct_moves(boards, game_ids)
         t0 = time.time()
         out = [None] * len(boards)
         # per board: the search's (predicts, main_draws, sim_draws); None if no search ran
@@ -134,6 +149,26 @@ class AlphaZeroGomokuAI:
                 self.last_batch_stats[i] = (int(stats[k]["predicts"]), int(stats[k]["main_draws"]),
                                             int(stats[k]["sim_draws"]))
             self.last_search_stats = stats[-1]
+        self._last_decision_time = time.time() - t0
+        self.games_played += len(boards)
+        return out
+
+    def _puct_moves(self, boards, game_ids):
+        """search="puct": the network-guided search (gz_puct_search) with the model's
+        packed weights on every ply -- no opening book, no exploration move; beta and
+        planner_steps are not used.  Sets last_search_visits and last_root_value."""
+        t0 = time.time()
+        out = [None] * len(boards)
+        self.last_batch_stats = [None] * len(boards)
+        if boards:
+            w = self.model.device_weights()
+            p = device.puct_params(self.params.get("num_simulations", 200), self.params["c_puct"], self.temp_plies,
+                                   self.seed, w.precision)
+            states = np.concatenate([b.to_state() for b in boards])
+            mv, visits, q, _ = device.puct_search(states, [int(g) for g in game_ids], p, w)
+            self.last_search_visits, self.last_root_value = visits, q
+            for i, m in enumerate(mv):
+                out[i] = None if int(m) < 0 else (int(m) // 15, int(m) % 15)
         self._last_decision_time = time.time() - t0
         self.games_played += len(boards)
         return out

@@ -1,0 +1,685 @@
+// gz_puct.hip -- network-guided PUCT search (the opt-in "puct" search mode).
+//
+// The default mode reproduces the reference's search, in which MCTSNode.prior_prob
+// is written and never read and the value head is never consulted.  Here the
+// priors steer selection (PUCT) and the value head replaces the rollout; self-play
+// emits the root's visit counts as the policy target.
+//
+// One 64-lane wavefront (one workgroup) owns one game.  Lane l owns the cells l,
+// l+64, l+128 and l+192 (the last chunk has 33 valid lanes), so chunk k of a wave
+// is the contiguous cell range [64k, 64k+64).  A search is S+1 lock-step rounds
+// over all games, each round three stream-ordered steps:
+//
+//   1. puct_select_kernel  descends by PUCT from the root to a new child, creates
+//                          it and puts its board into the game's leaf row (row g of
+//                          [n][16]); a descent that ends in a terminal node backs
+//                          its value up at once and leaves an empty board;
+//   2. gz_pv_forward       over the n leaf rows (rows are fixed per game, never
+//                          compacted: static launch shapes, order-independent results);
+//   3. puct_backup_kernel  stores the prior row and the value in the new node and
+//                          backs the value up.
+//
+// Round 0 evaluates the root (gz_puct_begin writes its board instead of step 1).
+// Nothing synchronises the host and nothing is copied to it.
+//
+// Semantics (tests/puct_ref.py restates them in Python, bit for bit): v is the
+// value for the side to move at node i; a node's W is from the view of the player
+// who moved into it.
+//
+//   backup(i, v):  s = -v; while i >= 0: visits[i] += 1; W[i] += s; s = -s; i = parent[i]
+//   score(c)    =  q + u,  q = n ? W[child]/n : 0.0,
+//                  u = ((c_puct * prior[i][c]) * sqrt((double)visits[i])) / (1.0 + n)
+//   the move    =  the first maximum of score over the empty cells, ascending
+//   terminal    :  backup(j, draw ? 0.0 : -1.0)  (proper negamax, draw = 0 -- not the
+//                  default mode's un-negated, draw = 0.1 backup)
+//
+// All score arithmetic is fp64 in exactly that order (-ffp-contract=off); the
+// network's value enters as (double)float32.
+//
+// Workspace (gz_puct_workspace_bytes(n, S), M = S+1 nodes per game):
+//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S), written by gz_puct_begin
+//   n x game_stride     per game, game_stride = al256(128 + 2334 M):
+//        PuctHdr  128 B   root position, game id, node count, pending node, ...
+//        W        f64 [M]
+//        prior    f64 [M][225]   the evaluator's row, copied by the backup step
+//        visits   i32 [M]
+//        value    f32 [M]        the value the network returned for the node
+//        board    u32 [M][16]    black[8], white[8] of the node's position
+//        child    i16 [M][225]   -1 = none
+//        parent   i16 [M]
+//        move     u8  [M]        row-major cell (255 for the root)
+//        term     u8  [M]        0 live, 1/2 winner colour, 3 draw (as Tree.term)
+//   gz_puct_search's round buffers: leaves u32 [n][16], active i32 [n], logits f32
+//   [n][225], probs f32 [n][225], value f32 [n], prior f64 [n][225], then
+//   gz_pv_workspace_bytes(n) for the forward.
+// About 2.3 KB per node: 1.9 GB at 4096 games x 200 simulations.
+//
+// Export (gz_puct_trees, gz_puct_tree_bytes(S) = al256(16 + 1884 M) per game):
+//   i32 n_nodes, n_evals, main_draws, move; then W, prior, visits, value, board,
+//   parent, move, term as above (no child table), nodes in creation order.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <string>
+
+#include "gz_search.h"
+
+using namespace gz;
+
+extern "C" void gz_internal_set_error(const char* msg);
+// selfplay_commit_kernel (gz_selfplay.hip) with the optional visit buffers
+extern "C" int gz_internal_selfplay_commit(void* d_slots, int32_t n_slots, const int32_t* d_moves,
+                                           const gz_search_stats* d_stats, gz_record* d_records, int32_t record_cap,
+                                           gz_selfplay_counters* d_counters, const uint16_t* d_pend_visits,
+                                           uint16_t* d_out_visits, void* stream);
+
+namespace {
+
+int fail(int code, const std::string& msg) {
+    gz_internal_set_error(msg.c_str());
+    return code;
+}
+
+int check_launch(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GZ_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return GZ_OK;
+}
+
+__host__ __device__ constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct PuctCfg {
+    double c_puct;
+    uint64_t seed;
+    int32_t temp_plies;
+    int32_t S;
+};
+
+struct PuctHdr {  // 128 bytes
+    uint32_t black[8];
+    uint32_t white[8];
+    int64_t game_id;
+    int32_t n_moves;
+    int32_t player;
+    int32_t over;        // the root is finished (or full): no search, move -1
+    int32_t n_nodes;
+    int32_t n_evals;     // nodes the evaluator was asked for
+    int32_t main_draws;  // draws on the (game, ply, 0) stream (0 or 1)
+    int32_t pending;     // node waiting for its prior and value, -1 = none
+    int32_t move;
+    int32_t pad[6];
+};
+static_assert(sizeof(PuctHdr) == 128, "puct header");
+
+__host__ __device__ inline size_t game_stride_for(int S) {
+    const size_t M = (size_t)S + 1;
+    return al256(sizeof(PuctHdr) + 2334 * M);
+}
+
+__host__ __device__ inline size_t export_bytes_for(int S) {
+    const size_t M = (size_t)S + 1;
+    return al256(16 + 1884 * M);
+}
+
+struct PuctTree {
+    PuctHdr* h;
+    double* W;
+    double* prior;
+    int32_t* visits;
+    float* value;
+    uint32_t* board;
+    int16_t* child;
+    int16_t* parent;
+    uint8_t* move;
+    uint8_t* term;
+};
+
+__device__ inline PuctTree tree_of(char* ws, int g, int S) {
+    const size_t M = (size_t)S + 1;
+    char* b = ws + 256 + (size_t)g * game_stride_for(S);
+    PuctTree t;
+    t.h = (PuctHdr*)b;
+    b += sizeof(PuctHdr);
+    t.W = (double*)b;
+    b += 8 * M;
+    t.prior = (double*)b;
+    b += 1800 * M;
+    t.visits = (int32_t*)b;
+    b += 4 * M;
+    t.value = (float*)b;
+    b += 4 * M;
+    t.board = (uint32_t*)b;
+    b += 64 * M;
+    t.child = (int16_t*)b;
+    b += 450 * M;
+    t.parent = (int16_t*)b;
+    b += 2 * M;
+    t.move = (uint8_t*)b;
+    b += M;
+    t.term = (uint8_t*)b;
+    return t;
+}
+
+__device__ inline void backup(const PuctTree& t, int i, double v) {
+    double s = -v;
+    while (i >= 0) {
+        t.visits[i] += 1;
+        t.W[i] += s;
+        s = -s;
+        i = t.parent[i];
+    }
+}
+
+// row g of the leaf buffer: the board, or the empty board when the game has no leaf
+__device__ inline void write_leaf(uint32_t* leaves, int32_t* active, int g, const BB& black, const BB& white,
+                                  bool live) {
+    const int lane = lane_id();
+    if (lane < 16) {
+        uint32_t w = lane < 8 ? bb_word(black, lane) : bb_word(white, lane - 8);
+        leaves[(size_t)g * 16 + lane] = live ? w : 0u;
+    }
+    if (lane == 0) active[g] = live ? 1 : 0;
+}
+
+__device__ inline void new_node(const PuctTree& t, int j, int parent, int move, int term, const BB& black,
+                                const BB& white) {
+    const int lane = lane_id();
+    for (int c = lane; c < GZ_CELLS; c += WAVE) t.child[(size_t)j * GZ_CELLS + c] = -1;
+    if (lane < 16) t.board[(size_t)j * 16 + lane] = lane < 8 ? bb_word(black, lane) : bb_word(white, lane - 8);
+    if (lane == 0) {
+        t.parent[j] = (int16_t)parent;
+        t.move[j] = (uint8_t)move;
+        t.term[j] = (uint8_t)term;
+        t.visits[j] = 0;
+        t.W[j] = 0.0;
+        t.value[j] = 0.0f;
+    }
+}
+
+// ---------------------------------------------------------------- begin
+__global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* boards, const int64_t* game_ids, int n,
+                                                          gz_puct_params p, char* ws, uint32_t* leaves,
+                                                          int32_t* active) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    const int S = p.num_simulations;
+    if (g == 0 && lane == 0) {
+        PuctCfg* cfg = (PuctCfg*)ws;
+        cfg->c_puct = p.c_puct;
+        cfg->seed = p.seed;
+        cfg->temp_plies = p.temp_plies;
+        cfg->S = S;
+    }
+    PuctTree t = tree_of(ws, g, S);
+    const gz_board_state& bs = boards[g];
+    BB black, white;
+    load_bb(black, bs.black);
+    load_bb(white, bs.white);
+    const bool over = bs.over != 0 || !bb_any(empties(black, white));
+    new_node(t, 0, -1, 255, 0, black, white);
+    if (lane == 0) {
+        PuctHdr* h = t.h;
+        store_bb(h->black, black);
+        store_bb(h->white, white);
+        h->game_id = game_ids[g];
+        h->n_moves = bs.n_moves;
+        h->player = bs.player;
+        h->over = over ? 1 : 0;
+        h->n_nodes = 1;
+        h->n_evals = 0;
+        h->main_draws = 0;
+        h->pending = over ? -1 : 0;
+        h->move = -1;
+    }
+    write_leaf(leaves, active, g, black, white, !over);
+}
+
+// ---------------------------------------------------------------- select
+__global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int S, uint32_t* leaves, int32_t* active) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    const PuctCfg cfg = *(const PuctCfg*)ws;
+    PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    if (h->over || h->pending >= 0) {  // (pending: the caller skipped a backup; keep the tree as it is)
+        write_leaf(leaves, active, g, black, white, false);
+        return;
+    }
+    int mover = h->player, cnt = h->n_moves;
+    int i = 0;
+    while (true) {
+        const int tm = t.term[i];
+        if (tm) {
+            if (lane == 0) backup(t, i, tm == 3 ? 0.0 : -1.0);
+            write_leaf(leaves, active, g, black, white, false);
+            return;
+        }
+        const BB E = empties(black, white);
+        const double sq = __builtin_sqrt((double)t.visits[i]);
+        const double* pr = t.prior + (size_t)i * GZ_CELLS;
+        const int16_t* ch = t.child + (size_t)i * GZ_CELLS;
+        double bv = -__builtin_inf();
+        int bi = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = lane + WAVE * k;
+            if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) {
+                const int cj = ch[c];
+                int nn = 0;
+                double q = 0.0;
+                if (cj >= 0) {
+                    nn = t.visits[cj];
+                    q = nn ? t.W[cj] / (double)nn : 0.0;
+                }
+                const double u = ((cfg.c_puct * pr[c]) * sq) / (1.0 + (double)nn);
+                const double sc = q + u;
+                if (sc > bv) {
+                    bv = sc;
+                    bi = c;
+                }
+            }
+        }
+        wave_argmax(bv, bi);
+        if (bi == INT_MAX) bi = bit_to_cell(lowest_bit(E));  // only if the evaluator gave non-finite priors
+        if (bi < 0 || bi >= GZ_CELLS) {  // (a live node always has an empty cell)
+            write_leaf(leaves, active, g, black, white, false);
+            return;
+        }
+        const int bit = cell_to_bit(bi);
+        const int cj = ch[bi];
+        if (cj >= 0) {
+            if (mover == 1) bb_set(black, bit);
+            else bb_set(white, bit);
+            mover = 3 - mover;
+            cnt++;
+            i = cj;
+            continue;
+        }
+        const int j = h->n_nodes;
+        if (j > S) {  // more select steps than the workspace was sized for: no node left
+            write_leaf(leaves, active, g, black, white, false);
+            return;
+        }
+        // make_move (gomoku_board.py:84-113): five or more wins, then the full board /
+        // the 200-ply cap draws
+        const bool win = bb_test(threats(mover == 1 ? black : white).win, bit);
+        const int ne = bb_count(E);
+        if (mover == 1) bb_set(black, bit);
+        else bb_set(white, bit);
+        cnt++;
+        const int term = win ? mover : ((ne == 1 || cnt >= GZ_MAX_GAME_PLIES) ? 3 : 0);
+        new_node(t, j, i, bi, term, black, white);
+        if (lane == 0) {
+            t.child[(size_t)i * GZ_CELLS + bi] = (int16_t)j;
+            h->n_nodes = j + 1;
+            if (term) backup(t, j, term == 3 ? 0.0 : -1.0);
+            else h->pending = j;
+        }
+        write_leaf(leaves, active, g, black, white, term == 0);
+        return;
+    }
+}
+
+// ---------------------------------------------------------------- backup
+__global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int S, const double* prior,
+                                                           const float* value) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    PuctTree t = tree_of(ws, g, S);
+    const int j = t.h->pending;
+    if (j < 0) return;
+    for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[(size_t)g * GZ_CELLS + c];
+    if (lane == 0) {
+        const float v = value[g];
+        t.value[j] = v;
+        backup(t, j, (double)v);
+        t.h->pending = -1;
+        t.h->n_evals += 1;
+    }
+}
+
+// ---------------------------------------------------------------- finish
+__global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int S, int32_t* moves, int32_t* visits,
+                                                           double* root_q, gz_search_stats* stats) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    const PuctCfg cfg = *(const PuctCfg*)ws;
+    PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    const BB E = empties(black, white);
+    const bool over = h->over != 0;
+    int v[4];
+    long long tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int c = lane + WAVE * k;
+        v[k] = 0;
+        if (c < GZ_CELLS) {
+            const int cj = over ? -1 : t.child[c];
+            if (cj >= 0) v[k] = t.visits[cj];
+            if (visits) visits[(size_t)g * GZ_CELLS + c] = v[k];
+        }
+        tot += v[k];
+    }
+    const long long total = wave_sum_ll(tot);
+    int mv = -1, draws = 0;
+    if (!over) {
+        if (h->n_moves >= cfg.temp_plies || total == 0) {
+            // most visits, first maximum (occupied cells never win: -1)
+            int bv = -2, bi = INT_MAX;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int c = lane + WAVE * k;
+                if (c < GZ_CELLS) {
+                    const int x = bb_test(E, cell_to_bit(c)) ? v[k] : -1;
+                    if (x > bv) {
+                        bv = x;
+                        bi = c;
+                    }
+                }
+            }
+            wave_argmax_int(bv, bi);
+            mv = bi;
+        } else {
+            // one draw of the game's main stream; the first cell whose running visit
+            // sum exceeds pick = (draw * total) >> 64
+            const uint64_t key = stream_key(cfg.seed, h->game_id, h->n_moves, 0);
+            const uint64_t pick = __umul64hi(draw(key, 0), (uint64_t)total);
+            draws = 1;
+            long long base = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                long long inc = v[k];
+#pragma unroll
+                for (int off = 1; off < WAVE; off <<= 1) {
+                    const long long o = __shfl_up(inc, off);
+                    if (lane >= off) inc += o;
+                }
+                const uint64_t hit = ballot((uint64_t)(base + inc) > pick);
+                if (mv < 0 && hit) mv = WAVE * k + (int)__builtin_ctzll(hit);
+                base += __shfl(inc, WAVE - 1);
+            }
+        }
+    }
+    if (lane == 0) {
+        moves[g] = mv;
+        // the root's mean value for the side to move (W[0] is the opponent's view)
+        if (root_q) root_q[g] = (over || t.visits[0] == 0) ? 0.0 : -t.W[0] / (double)t.visits[0];
+        h->move = mv;
+        h->main_draws = draws;
+        if (stats) {
+            gz_search_stats st;
+            st.n_nodes = over ? 0 : h->n_nodes;
+            st.predicts = h->n_evals;
+            st.main_draws = draws;
+            st.pad = 0;
+            st.sim_draws = 0;
+            stats[g] = st;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- export
+__global__ __launch_bounds__(256) void puct_export_kernel(const char* ws, int n, int S, char* out) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const size_t M = (size_t)S + 1;
+    const char* src = ws + 256 + (size_t)g * game_stride_for(S);
+    char* dst = out + (size_t)g * export_bytes_for(S);
+    const PuctHdr* h = (const PuctHdr*)src;
+    if (threadIdx.x == 0) {
+        int32_t* o = (int32_t*)dst;
+        o[0] = h->n_nodes;
+        o[1] = h->n_evals;
+        o[2] = h->main_draws;
+        o[3] = h->move;
+    }
+    // W .. board: 1880 M bytes, 4-byte words on both sides
+    const uint32_t* a = (const uint32_t*)(src + sizeof(PuctHdr));
+    uint32_t* b = (uint32_t*)(dst + 16);
+    for (size_t w = threadIdx.x; w < 470 * M; w += 256) b[w] = a[w];
+    // parent, move, term: 4 M bytes after the child table
+    const char* c = src + sizeof(PuctHdr) + 2330 * M;
+    char* d = dst + 16 + 1880 * M;
+    for (size_t w = threadIdx.x; w < 4 * M; w += 256) d[w] = c[w];
+}
+
+// int32 visit row of the search -> the slot's pending uint16 row of this ply
+__global__ __launch_bounds__(WAVE) void puct_stash_kernel(const gz_board_state* boards, const int32_t* moves,
+                                                          const int32_t* visits, int n, uint16_t* pend) {
+    const int s = blockIdx.x;
+    if (s >= n) return;
+    const int ply = boards[s].n_moves;
+    if (moves[s] < 0 || ply < 0 || ply >= GZ_MAX_GAME_PLIES) return;
+    uint16_t* row = pend + ((size_t)s * GZ_MAX_GAME_PLIES + ply) * GZ_CELLS;
+    for (int c = lane_id(); c < GZ_CELLS; c += WAVE) row[c] = (uint16_t)visits[(size_t)s * GZ_CELLS + c];
+}
+
+inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+struct RoundBufs {
+    uint32_t* leaves;
+    int32_t* active;
+    float *logits, *probs, *value;
+    double* prior;
+    void* pvws;
+};
+
+size_t rounds_offset(int32_t n, int32_t S) { return 256 + (size_t)n * game_stride_for(S); }
+
+RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) {
+    char* p = (char*)ws + rounds_offset(n, S);
+    RoundBufs r;
+    r.leaves = (uint32_t*)p;
+    p += al256((size_t)n * 64);
+    r.active = (int32_t*)p;
+    p += al256((size_t)n * 4);
+    r.logits = (float*)p;
+    p += al256((size_t)n * 900);
+    r.probs = (float*)p;
+    p += al256((size_t)n * 900);
+    r.value = (float*)p;
+    p += al256((size_t)n * 4);
+    r.prior = (double*)p;
+    p += al256((size_t)n * 1800);
+    r.pvws = p;
+    return r;
+}
+
+int check_S(const char* who, int32_t n, int32_t S) {
+    if (S < 1 || S > GZ_MAX_SIMULATIONS)
+        return fail(GZ_ERR_ARG, std::string(who) + ": num_simulations out of range [1, 4095]");
+    if (n < 0) return fail(GZ_ERR_ARG, std::string(who) + ": n < 0");
+    return GZ_OK;
+}
+
+int finish_impl(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
+                gz_search_stats* d_stats, void* stream) {
+    puct_finish_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q, d_stats);
+    return check_launch("puct_finish_kernel");
+}
+
+int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
+                const float* d_pv_weights, void* ws, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
+                gz_search_stats* d_stats, void* stream) {
+    const int S = p->num_simulations;
+    const RoundBufs r = carve_rounds(ws, n, S);
+    int rc = gz_puct_begin(d_boards, d_game_ids, n, p, ws, r.leaves, r.active, stream);
+    if (rc) return rc;
+    for (int round = 0; round <= S; round++) {
+        if (round > 0) {
+            rc = gz_puct_select(ws, n, S, r.leaves, r.active, stream);
+            if (rc) return rc;
+        }
+        rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
+                           p->precision, stream);
+        if (rc) return rc;
+        rc = gz_puct_backup(ws, n, S, r.prior, r.value, stream);
+        if (rc) return rc;
+    }
+    return finish_impl(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
+}
+
+int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
+    if (!p) return fail(GZ_ERR_ARG, std::string(who) + ": params is NULL");
+    int rc = check_S(who, n, p->num_simulations);
+    if (rc) return rc;
+    if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3)
+        return fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
+    return GZ_OK;
+}
+
+struct SelfplayWs {
+    gz_board_state* boards;
+    int64_t* gids;
+    int32_t* moves;
+    gz_search_stats* stats;
+    int32_t* visits;
+    double* root_q;
+    uint16_t* pend;
+    void* puct;
+};
+
+size_t pend_bytes(int32_t n_slots) { return al256((size_t)n_slots * GZ_MAX_GAME_PLIES * GZ_CELLS * 2); }
+
+SelfplayWs carve_selfplay(void* ws, int32_t n) {
+    char* p = (char*)ws;
+    SelfplayWs w;
+    w.boards = (gz_board_state*)p;
+    p += al256((size_t)n * sizeof(gz_board_state));
+    w.gids = (int64_t*)p;
+    p += al256((size_t)n * 8);
+    w.moves = (int32_t*)p;
+    p += al256((size_t)n * 4);
+    w.stats = (gz_search_stats*)p;
+    p += al256((size_t)n * sizeof(gz_search_stats));
+    w.visits = (int32_t*)p;
+    p += al256((size_t)n * 900);
+    w.root_q = (double*)p;
+    p += al256((size_t)n * 8);
+    w.pend = (uint16_t*)p;
+    p += pend_bytes(n);
+    w.puct = p;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gz_puct_tree_bytes(int32_t S) { return S < 0 ? 0 : export_bytes_for(S); }
+
+size_t gz_puct_workspace_bytes(int32_t n, int32_t S) {
+    if (n < 1) n = 1;
+    if (S < 0) S = 0;
+    const size_t m = (size_t)n;
+    return rounds_offset(n, S) + al256(m * 64) + al256(m * 4) + 2 * al256(m * 900) + al256(m * 4) + al256(m * 1800) +
+           gz_pv_workspace_bytes(n);
+}
+
+int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
+                  void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream) {
+    if (!p) return fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
+    int rc = check_S("gz_puct_begin", n, p->num_simulations);
+    if (rc) return rc;
+    if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
+        return fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, (char*)d_workspace, d_leaves,
+                                                         d_active);
+    return check_launch("puct_begin_kernel");
+}
+
+int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, int32_t* d_active, void* stream) {
+    int rc = check_S("gz_puct_select", n, S);
+    if (rc) return rc;
+    if (n > 0 && (!d_workspace || !d_leaves || !d_active)) return fail(GZ_ERR_ARG, "gz_puct_select: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_select_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
+    return check_launch("puct_select_kernel");
+}
+
+int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prior, const float* d_value,
+                   void* stream) {
+    int rc = check_S("gz_puct_backup", n, S);
+    if (rc) return rc;
+    if (n > 0 && (!d_workspace || !d_prior || !d_value)) return fail(GZ_ERR_ARG, "gz_puct_backup: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_prior, d_value);
+    return check_launch("puct_backup_kernel");
+}
+
+int gz_puct_finish(void* d_workspace, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
+                   void* stream) {
+    int rc = check_S("gz_puct_finish", n, S);
+    if (rc) return rc;
+    if (n > 0 && (!d_workspace || !d_moves)) return fail(GZ_ERR_ARG, "gz_puct_finish: bad arguments");
+    if (n == 0) return GZ_OK;
+    return finish_impl(d_workspace, n, S, d_moves, d_visits, d_root_q, nullptr, stream);
+}
+
+int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
+                   const float* d_pv_weights, void* d_workspace, int32_t* d_moves, int32_t* d_visits,
+                   double* d_root_q, void* stream) {
+    int rc = check_search_args("gz_puct_search", p, n);
+    if (rc) return rc;
+    if (n > 0 && (!d_boards || !d_game_ids || !d_pv_weights || !d_workspace || !d_moves))
+        return fail(GZ_ERR_ARG, "gz_puct_search: bad arguments");
+    if (n == 0) return GZ_OK;
+    return search_impl(d_boards, d_game_ids, n, p, d_pv_weights, d_workspace, d_moves, d_visits, d_root_q, nullptr,
+                       stream);
+}
+
+int gz_puct_trees(const void* d_workspace, int32_t n, int32_t S, void* d_out, void* stream) {
+    int rc = check_S("gz_puct_trees", n, S);
+    if (rc) return rc;
+    if (n > 0 && (!d_workspace || !d_out)) return fail(GZ_ERR_ARG, "gz_puct_trees: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_export_kernel<<<n, 256, 0, as_stream(stream)>>>((const char*)d_workspace, n, S, (char*)d_out);
+    return check_launch("puct_export_kernel");
+}
+
+size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t S) {
+    if (n_slots < 1) n_slots = 1;
+    const size_t m = (size_t)n_slots;
+    return al256(m * sizeof(gz_board_state)) + al256(m * 8) + al256(m * 4) + al256(m * sizeof(gz_search_stats)) +
+           al256(m * 900) + al256(m * 8) + pend_bytes(n_slots) + gz_puct_workspace_bytes(n_slots, S);
+}
+
+int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
+                         void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
+                         uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
+    int rc = check_search_args("gz_selfplay_puct_run", p, n_slots);
+    if (rc) return rc;
+    if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
+        !d_pv_weights || !d_visits)
+        return fail(GZ_ERR_ARG, "gz_selfplay_puct_run: bad arguments");
+    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
+    hipStream_t st = as_stream(stream);
+    for (int it = 0; it < n_plies; it++) {
+        rc = gz_selfplay_boards(d_slots, n_slots, p->num_simulations, w.boards, w.gids, stream);
+        if (rc) return rc;
+        rc = search_impl(w.boards, w.gids, n_slots, p, d_pv_weights, w.puct, w.moves, w.visits, w.root_q, w.stats,
+                         stream);
+        if (rc) return rc;
+        puct_stash_kernel<<<n_slots, WAVE, 0, st>>>(w.boards, w.moves, w.visits, n_slots, w.pend);
+        rc = check_launch("puct_stash_kernel");
+        if (rc) return rc;
+        rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
+                                         d_visits, stream);
+        if (rc) return rc;
+    }
+    return GZ_OK;
+}
+
+}  // extern "C"

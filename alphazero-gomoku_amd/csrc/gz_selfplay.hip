@@ -635,10 +635,14 @@ __global__ __launch_bounds__(WAVE, GZ_SP_WPE) void selfplay_kernel(char* slots, 
 }
 
 // The move-application half of selfplay_kernel for searches run elsewhere
-// (gz_plan_search): record, make_move, finish / restart (training.py:141-218).
+// (gz_plan_search, gz_puct_search): record, make_move, finish / restart
+// (training.py:141-218).  pend_visits / out_visits (optional, the PUCT mode): the
+// slot's pending visit rows [n_slots][200][225] and the rows of the finished games'
+// records [rec_cap][225]; a finished game's rows go where its records go.
 __global__ __launch_bounds__(WAVE) void selfplay_commit_kernel(char* slots, int n_slots, const int32_t* moves,
                                                               const gz_search_stats* stats, gz_record* records,
-                                                              int rec_cap, gz_selfplay_counters* ctr) {
+                                                              int rec_cap, gz_selfplay_counters* ctr,
+                                                              const uint16_t* pend_visits, uint16_t* out_visits) {
     const int s = blockIdx.x;
     if (s >= n_slots) return;
     const int lane = lane_id();
@@ -683,6 +687,12 @@ __global__ __launch_bounds__(WAVE) void selfplay_commit_kernel(char* slots, int 
                 r.z = (int8_t)(winner == 0 ? 0 : (r.player == winner ? 1 : -1));
                 records[base + i] = r;
             }
+        }
+        if (pend_visits && out_visits) {
+            const uint16_t* src = pend_visits + (size_t)s * GZ_MAX_GAME_PLIES * GZ_CELLS;
+            for (int i = 0; i < n && base + i < rec_cap; i++)
+                for (int c = lane; c < GZ_CELLS; c += WAVE)
+                    out_visits[(size_t)(base + i) * GZ_CELLS + c] = src[(size_t)i * GZ_CELLS + c];
         }
         if (lane == 0 && base + n > rec_cap) {
             int lost = base + n - (base > rec_cap ? base : rec_cap);
@@ -1000,11 +1010,21 @@ int gz_selfplay_plan_run(void* d_slots, int32_t n_slots, const gz_search_params*
                                      gather ? d_leaf_meta : nullptr, stream);
         if (rc) return rc;
         selfplay_commit_kernel<<<n_slots, WAVE, 0, st>>>((char*)d_slots, n_slots, d_moves, d_stats, d_records,
-                                                         record_cap, d_counters);
+                                                         record_cap, d_counters, nullptr, nullptr);
         rc = check_launch("selfplay_commit_kernel");
         if (rc) return rc;
     }
     return GZ_OK;
+}
+
+// selfplay_commit_kernel for gz_selfplay_puct_run (gz_puct.hip; not part of gzero.h)
+int gz_internal_selfplay_commit(void* d_slots, int32_t n_slots, const int32_t* d_moves, const gz_search_stats* d_stats,
+                                gz_record* d_records, int32_t record_cap, gz_selfplay_counters* d_counters,
+                                const uint16_t* d_pend_visits, uint16_t* d_out_visits, void* stream) {
+    selfplay_commit_kernel<<<n_slots, WAVE, 0, as_stream(stream)>>>((char*)d_slots, n_slots, d_moves, d_stats,
+                                                                    d_records, record_cap, d_counters, d_pend_visits,
+                                                                    d_out_visits);
+    return check_launch("selfplay_commit_kernel");
 }
 
 int gz_plan_gn_stats(void* d_workspace, int32_t n, int32_t num_simulations, int64_t* out, int32_t reset, void* stream);

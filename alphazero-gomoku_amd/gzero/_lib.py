@@ -56,6 +56,12 @@ def planner_params(difficulty):
     return PlannerParams(k, 0, a, e)
 
 
+class PuctParams(ctypes.Structure):  # gz_puct_params
+    _fields_ = [("num_simulations", ctypes.c_int32), ("temp_plies", ctypes.c_int32),
+                ("c_puct", ctypes.c_double), ("seed", ctypes.c_uint64),
+                ("precision", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
 class Record(ctypes.Structure):  # gz_record, 80 bytes
     _fields_ = [("black", ctypes.c_uint32 * 8), ("white", ctypes.c_uint32 * 8),
                 ("game_id", ctypes.c_int64), ("ply", ctypes.c_int16), ("move", ctypes.c_int16),
@@ -155,6 +161,17 @@ SIGNATURES = {
     "gz_gn_chain_workspace_bytes": (_SZ, [_I32]),
     "gz_gn_forward_chain": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "gz_selfplay_plan_gn_stats": (ctypes.c_int, [_P, _I32, _I32, _P, _I32, _P]),
+    "gz_puct_workspace_bytes": (_SZ, [_I32, _I32]),
+    "gz_puct_begin": (ctypes.c_int, [_P, _P, _I32, ctypes.POINTER(PuctParams), _P, _P, _P, _P]),
+    "gz_puct_select": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "gz_puct_backup": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "gz_puct_finish": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P]),
+    "gz_puct_search": (ctypes.c_int, [_P, _P, _I32, ctypes.POINTER(PuctParams), _P, _P, _P, _P, _P, _P]),
+    "gz_puct_tree_bytes": (_SZ, [_I32]),
+    "gz_puct_trees": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
+    "gz_selfplay_puct_workspace_bytes": (_SZ, [_I32, _I32]),
+    "gz_selfplay_puct_run": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32, _P, _P,
+                                            _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
     "gz_dataset_gather": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P]),

@@ -317,6 +317,129 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
     return d_moves.cpu().numpy(), st, trees, leaves
 
 
+# ---------------------------------------------------------------- PUCT search
+def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3"):
+    """gz_puct_params; precision ("fp32" / "f16x3") is the forward gz_puct_search runs."""
+    if precision not in ("fp32", "f16x3"):
+        raise ValueError(f"unknown precision {precision!r}")
+    mode = _lib.GZ_PV_FP32 if precision == "fp32" else _lib.GZ_PV_F16X3
+    return _lib.PuctParams(int(num_simulations), int(temp_plies), float(c_puct), int(seed) & ((1 << 64) - 1),
+                           mode, 0)
+
+
+def parse_puct_tree(raw, num_simulations):
+    """One exported PUCT tree (gz_puct_trees, layout in csrc/gz_puct.hip) -> dict:
+    n_nodes, n_evals, main_draws, move and, per node in creation order, W, prior
+    [k,225], visits, value, board [k,16], parent, move_of (255 = root), term."""
+    M = num_simulations + 1
+    b = np.asarray(raw, np.uint8)
+    hdr = b[:16].view(np.int32)
+    k = int(hdr[0])
+    o = 16
+    out = {"n_nodes": k, "n_evals": int(hdr[1]), "main_draws": int(hdr[2]), "move": int(hdr[3])}
+    for name, dt, width in (("W", np.float64, 1), ("prior", np.float64, 225), ("visits", np.int32, 1),
+                            ("value", np.float32, 1), ("board", np.uint32, 16), ("parent", np.int16, 1),
+                            ("move_of", np.uint8, 1), ("term", np.uint8, 1)):
+        nb = np.dtype(dt).itemsize * width * M
+        a = b[o:o + nb].view(dt)
+        out[name] = (a.reshape(M, width)[:k] if width > 1 else a[:k]).copy()
+        o += nb
+    return out
+
+
+def _puct_trees(lib, ws, n, S):
+    tb = lib.gz_puct_tree_bytes(S)
+    d_out = torch.zeros(n * tb, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.gz_puct_trees(ptr(ws), n, S, ptr(d_out), stream()), "gz_puct_trees")
+    raw = d_out.cpu().numpy().reshape(n, tb)
+    return [parse_puct_tree(raw[i], S) for i in range(n)]
+
+
+def puct_search(states, game_ids, params, pv_weights, want_trees=False):
+    """One network-guided PUCT search per state (gz_puct_search) with the forward of
+    params.precision.  Returns (moves int32 [n] (-1: the board is over), visits int32
+    [n,225] root-child visits, root_q float64 [n], trees or None)."""
+    lib = require_gpu()
+    states = np.ascontiguousarray(states, dtype=STATE_DTYPE)
+    n = len(states)
+    S = params.num_simulations
+    d_states = to_dev(states)
+    d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
+    d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_visits = torch.zeros(n * 225, dtype=torch.int32, device="cuda")
+    d_q = torch.zeros(n, dtype=torch.float64, device="cuda")
+    # (an S out of range is the library's error to report: size the workspace for a legal one)
+    ws = torch.empty(lib.gz_puct_workspace_bytes(n, max(0, min(S, _lib.GZ_MAX_SIMULATIONS))), dtype=torch.uint8,
+                     device="cuda")
+    _lib.check(lib.gz_puct_search(ptr(d_states), ptr(d_gids), n, ctypes.byref(params), ptr(pv_weights.tensor),
+                                  ptr(ws), ptr(d_moves), ptr(d_visits), ptr(d_q), stream()), "gz_puct_search")
+    torch.cuda.synchronize()
+    trees = _puct_trees(lib, ws, n, S) if want_trees else None
+    return d_moves.cpu().numpy(), d_visits.cpu().numpy().reshape(n, 225), d_q.cpu().numpy(), trees
+
+
+class PuctStepper:
+    """The step API of the PUCT search, for a caller that evaluates the leaves itself:
+
+        st = PuctStepper(states, game_ids, params)       # gz_puct_begin
+        rows, active = st.leaves()                       # root boards
+        st.backup(prior, value)                          # their evaluation
+        for _ in range(S):
+            st.select(); rows, active = st.leaves(); st.backup(prior, value)
+        moves, visits, root_q = st.finish()
+
+    prior float64 [n,225] and value float32 [n] in gz_pv_forward's layouts (device
+    tensors or arrays); rows of inactive games are ignored."""
+
+    def __init__(self, states, game_ids, params):
+        self.lib = require_gpu()
+        states = np.ascontiguousarray(states, dtype=STATE_DTYPE)
+        self.n = len(states)
+        self.S = params.num_simulations
+        self.params = params
+        d_states = to_dev(states)
+        d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
+        self.d_leaves = torch.zeros(self.n * 16, dtype=torch.int32, device="cuda")
+        self.d_active = torch.zeros(self.n, dtype=torch.int32, device="cuda")
+        nbytes = self.lib.gz_puct_workspace_bytes(self.n, max(0, min(self.S, _lib.GZ_MAX_SIMULATIONS)))
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        _lib.check(self.lib.gz_puct_begin(ptr(d_states), ptr(d_gids), self.n, ctypes.byref(params), ptr(self.ws),
+                                          ptr(self.d_leaves), ptr(self.d_active), stream()), "gz_puct_begin")
+
+    def leaves(self):
+        """(rows uint32 [n,16], active bool [n]) of the current round (synchronising)."""
+        rows = self.d_leaves.cpu().numpy().view(np.uint32).reshape(self.n, 16)
+        return rows, self.d_active.cpu().numpy() != 0
+
+    def select(self):
+        _lib.check(self.lib.gz_puct_select(ptr(self.ws), self.n, self.S, ptr(self.d_leaves), ptr(self.d_active),
+                                           stream()), "gz_puct_select")
+
+    def backup(self, prior, value):
+        if not isinstance(prior, torch.Tensor):
+            prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64).reshape(-1)).cuda()
+        if not isinstance(value, torch.Tensor):
+            value = torch.from_numpy(np.ascontiguousarray(value, np.float32).reshape(-1)).cuda()
+        if prior.dtype != torch.float64 or prior.numel() != self.n * 225 or value.dtype != torch.float32 \
+                or value.numel() != self.n:
+            raise ValueError("backup() wants prior float64 [n,225] and value float32 [n]")
+        _lib.check(self.lib.gz_puct_backup(ptr(self.ws), self.n, self.S, ptr(prior), ptr(value), stream()),
+                   "gz_puct_backup")
+
+    def finish(self):
+        d_moves = torch.zeros(self.n, dtype=torch.int32, device="cuda")
+        d_visits = torch.zeros(self.n * 225, dtype=torch.int32, device="cuda")
+        d_q = torch.zeros(self.n, dtype=torch.float64, device="cuda")
+        _lib.check(self.lib.gz_puct_finish(ptr(self.ws), self.n, self.S, ptr(d_moves), ptr(d_visits), ptr(d_q),
+                                           stream()), "gz_puct_finish")
+        torch.cuda.synchronize()
+        return d_moves.cpu().numpy(), d_visits.cpu().numpy().reshape(self.n, 225), d_q.cpu().numpy()
+
+    def trees(self):
+        torch.cuda.synchronize()
+        return _puct_trees(self.lib, self.ws, self.n, self.S)
+
+
 def planner_move(states, ais, keys, pparams, gn_weights):
     """BGPlannerAI.get_move per state (gz_planner_move): returns (moves, draws)."""
     lib = require_gpu()

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .boards import RECORD_DTYPE, STATE_DTYPE, words_to_cells
-from .device import GNWeights, PVWeights, ptr, require_gpu, search_params, stream
+from .device import GNWeights, PVWeights, ptr, puct_params, require_gpu, search_params, stream
 
 COUNTER_DTYPE = np.dtype([("records", "<i4"), ("leaves", "<i4"), ("records_dropped", "<i4"),
                           ("leaves_dropped", "<i4"), ("moves", "<i8"), ("games", "<i8"),
@@ -27,8 +27,16 @@ class SelfPlayEngine:
     def __init__(self, n_slots=4096, num_simulations=200, c_puct=1.6, exploration=0.05, beta=0.2,
                  seed=0, max_depth=100, pv_weights=None, plies_per_step=1, game_id_base=0,
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
-                 pv_mode="full", game_id_end=None):
-        """game_id_end: a slot whose next game id would be >= game_id_end goes idle
+                 pv_mode="full", game_id_end=None, search="reference", temp_plies=12):
+        """search: "reference" (default) = the reference's search, in which the network's
+        outputs are computed and never read; "puct" = the network-guided search
+        (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
+        rollout, plies below temp_plies sample the move from the root visit counts and
+        the later ones take the most visited cell.  "puct" needs pv_weights (its
+        precision is the forward's) and planner_steps == 0, and ignores beta,
+        exploration, max_depth and pv_mode.  Every record then has a visit row
+        (:meth:`visits`), the policy target; records["move"] is still the move played.
+        game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
         planner_steps > 0: BG-planner rollout plies (config 4); gn_weights = the
@@ -38,11 +46,20 @@ class SelfPlayEngine:
         root's pre-BN accumulators plus the convolution of their input differences
         (within 2e-5 of the full forward), its grandchildren recomputing the windows
         around their new stone; roots and other nodes bit-identical to "full"."""
+        if search not in ("reference", "puct"):
+            raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
+        self.search = search
+        if search == "puct":
+            if pv_weights is None:
+                raise ValueError("search='puct' needs pv_weights (the network guides the search)")
+            if int(planner_steps) != 0:
+                raise ValueError("search='puct' has no rollouts: planner_steps must be 0")
         self.lib = require_gpu()
         self.n_slots = int(n_slots)
         self.n_active = self.n_slots  # the slots the launches run (the first n_active)
         self.plies_per_step = int(plies_per_step)
-        self.gather = pv_weights is not None
+        # (the PUCT search evaluates its own leaves: nothing is gathered for a forward afterwards)
+        self.gather = pv_weights is not None and search != "puct"
         self.planner_steps = int(planner_steps)
         self.params = search_params(num_simulations, c_puct, exploration, beta, seed, max_depth,
                                     self.planner_steps, self.gather)
@@ -69,6 +86,14 @@ class SelfPlayEngine:
         self.record_cap = self.n_slots * (_lib.GZ_MAX_GAME_PLIES + self.plies_per_step)
         self.d_records = torch.zeros(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self.d_counters = torch.zeros(COUNTER_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self.puct = self.d_puct_ws = self.d_visits = None
+        if search == "puct":
+            self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision)
+            self.d_puct_ws = torch.empty(self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S),
+                                         dtype=torch.uint8, device="cuda")
+            # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
+            # has no uint16 arithmetic; a count is at most GZ_MAX_SIMULATIONS)
+            self.d_visits = torch.zeros(self.record_cap * 225, dtype=torch.int16, device="cuda")
         self.leaf_cap = self.n_slots * self.plies_per_step * (S + 1) if self.gather else 0
         if self.gather:
             self.d_leaves = torch.zeros(self.leaf_cap * 16, dtype=torch.int32, device="cuda")
@@ -102,6 +127,9 @@ class SelfPlayEngine:
         """Launch gz_selfplay_compact: the active slots to the front of the slot buffer
         (the two buffers swap).  Returns the device int32 [1] active count; the caller
         sets :attr:`n_active` from it once read (the next launches run that many)."""
+        if self.search == "puct":
+            # the pending visit rows live per slot in the workspace and would have to move too
+            raise ValueError("compact() is not available on a PUCT engine")
         if self.d_slots_alt is None:
             raise ValueError("compact() needs an engine built with game_id_end")
         _lib.check(self.lib.gz_selfplay_compact(ptr(self.d_slots), self.n_slots, ptr(self.d_slots_alt),
@@ -118,6 +146,9 @@ class SelfPlayEngine:
         self.d_counters.zero_()
         if self.n_active == 0:  # every game is done
             return
+        if self.search == "puct":
+            self._puct_run(self.puct, n)
+            return
         if self.planner_steps:
             _lib.check(self.lib.gz_selfplay_plan_run(ptr(self.d_slots), self.n_active, ctypes.byref(self.params),
                                                      ctypes.byref(self.pparams), ptr(self.gn_weights.tensor),
@@ -129,6 +160,12 @@ class SelfPlayEngine:
                                             ptr(self.d_records), self.record_cap, ptr(self.d_leaves),
                                             self.leaf_cap, ptr(self.d_meta), ptr(self.d_counters), stream()),
                    "gz_selfplay_run")
+
+    def _puct_run(self, p, n_plies):
+        _lib.check(self.lib.gz_selfplay_puct_run(ptr(self.d_slots), self.n_slots, ctypes.byref(p),
+                                                 ptr(self.pv_weights.tensor), ptr(self.d_puct_ws), int(n_plies),
+                                                 ptr(self.d_records), self.record_cap, ptr(self.d_visits),
+                                                 ptr(self.d_counters), stream()), "gz_selfplay_puct_run")
 
     def gn_stats(self, reset=False, check=None):
         """Planner-net rows since the last reset: {"full", "incremental", "checked",
@@ -154,7 +191,16 @@ class SelfPlayEngine:
         (continuous refill) before a measurement; records of games finished here are
         not kept.  On a planner engine (config 4) the burn-in plies are searched without
         planner plies (the planner pipeline needs the GN forward per ply): the slots
-        reach a steady-state mix of positions, and the measured plies are planner plies."""
+        reach a steady-state mix of positions, and the measured plies are planner plies.
+        On a PUCT engine the burn-in plies are PUCT plies at 8 simulations (every ply
+        needs its visit row), in the engine's own workspace."""
+        if self.search == "puct":
+            p = _lib.PuctParams.from_buffer_copy(self.puct)
+            p.num_simulations = min(8, p.num_simulations)
+            for _ in range(int(n_plies)):
+                self.d_counters.zero_()
+                self._puct_run(p, 1)
+            return
         p = _lib.SearchParams.from_buffer_copy(self.params)
         p.flags = 0
         p.planner_steps = 0
@@ -218,6 +264,21 @@ class SelfPlayEngine:
         """(device uint8 tensor of records, count) without copying to the host."""
         n = min(int(self.counters()["records"]), self.record_cap)
         return self.d_records[: n * RECORD_DTYPE.itemsize], n
+
+    def visits_device(self):
+        """(device int16 tensor [count, 225] of root visit counts, count): row i belongs to
+        record i of :meth:`records_device` (PUCT engines only)."""
+        if self.search != "puct":
+            raise ValueError("visits are recorded by search='puct' engines only")
+        n = min(int(self.counters()["records"]), self.record_cap)
+        return self.d_visits[: n * 225].view(n, 225), n
+
+    def visits(self):
+        """uint16 [count, 225]: the root visit counts of the search behind each record of
+        :meth:`records` (the policy target; zero at occupied cells, summing to
+        num_simulations)."""
+        d, _ = self.visits_device()
+        return d.cpu().numpy().view(np.uint16)
 
     def boards(self):
         out = torch.zeros(self.n_slots * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")

@@ -293,6 +293,71 @@ int gz_plan_gn_stats(void* d_workspace, int32_t n, int32_t num_simulations, int6
 int gz_selfplay_plan_gn_stats(void* d_workspace, int32_t n_slots, int32_t num_simulations, int64_t* out,
                               int32_t reset, void* stream);
 
+/* ---- network-guided PUCT search (opt-in mode; csrc/gz_puct.hip) ----
+ * The default search reproduces the reference, which never reads the network's
+ * outputs.  In this mode the priors steer selection and the value head replaces
+ * the rollout: per simulation the tree is descended by
+ *   score(c) = q + ((c_puct * prior[c]) * sqrt((double)visits[node])) / (1.0 + n),
+ *   q = n ? W[child] / n : 0.0,  first maximum over the empty cells (fp64, that order),
+ * a new child is created and evaluated by the network ((double)float32 value v for
+ * its side to move) and backup(i, v) runs s = -v; visits[i] += 1; W[i] += s; s = -s
+ * up the parents (W is from the view of the player who moved into the node).  A
+ * terminal node backs up -1 (a five) or 0 (full board / 200 plies, make_move's
+ * rules) on every visit.  The root is evaluated first, so a search of S simulations
+ * is S+1 rounds of (select, forward over the n leaf rows, backup) with no host
+ * synchronisation; a game with no leaf in a round has the empty board in its row.
+ * Move: with n_moves >= temp_plies the empty cell with the most root-child visits
+ * (first maximum); else one draw x of the (seed, game, ply, 0) stream and the first
+ * cell whose running visit sum exceeds (x * total) >> 64.  No opening book,
+ * exploration or noise.  A board that is over returns move -1 and zero visits.
+ * d_visits (optional) int32 [n][225] root-child visits; d_root_q (optional) the
+ * root's mean value for its side to move, -W[0] / visits[0].
+ * Workspace layout, node record (~2.3 KB: 1.9 GB at 4096 games x 200 simulations)
+ * and the export layout of gz_puct_trees are documented in csrc/gz_puct.hip. */
+typedef struct gz_puct_params {
+    int32_t num_simulations; /* S, 1..GZ_MAX_SIMULATIONS */
+    int32_t temp_plies;      /* plies (move counts below this) that sample the move from the visits */
+    double c_puct;
+    uint64_t seed;           /* RNG streams (gzero/rng.py) */
+    int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3: gz_puct_search's forward */
+    int32_t flags;           /* reserved, 0 */
+} gz_puct_params;
+/* includes the forward's workspace and gz_puct_search's leaf / output rows */
+size_t gz_puct_workspace_bytes(int32_t n, int32_t num_simulations);
+/* Step API (the caller supplies the evaluator): begin writes the root boards to
+ * d_leaves [n][16] and d_active [n] (1 = the row wants an evaluation); after the
+ * caller's backup of the roots, S times select (new leaves) and backup; d_prior
+ * [n][225] float64 and d_value [n] in gz_pv_forward's layouts, rows of inactive
+ * games ignored.  finish picks the moves. */
+int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
+                  void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream);
+int gz_puct_select(void* d_workspace, int32_t n, int32_t num_simulations, uint32_t* d_leaves, int32_t* d_active,
+                   void* stream);
+int gz_puct_backup(void* d_workspace, int32_t n, int32_t num_simulations, const double* d_prior,
+                   const float* d_value, void* stream);
+int gz_puct_finish(void* d_workspace, int32_t n, int32_t num_simulations, int32_t* d_moves, int32_t* d_visits,
+                   double* d_root_q, void* stream);
+/* begin, the S+1 rounds with gz_pv_forward(d_pv_weights, p->precision), finish */
+int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
+                   const float* d_pv_weights, void* d_workspace, int32_t* d_moves, int32_t* d_visits,
+                   double* d_root_q, void* stream);
+/* the trees of the last search on this workspace, gz_puct_tree_bytes(S) per game:
+ * int32 n_nodes, evaluated nodes, main-stream draws, move; then in creation order
+ * W f64[S+1], prior f64[S+1][225], visits i32[S+1], leaf value f32[S+1], board
+ * u32[S+1][16], parent i16[S+1], move u8[S+1] (255 = root), term u8[S+1] */
+size_t gz_puct_tree_bytes(int32_t num_simulations);
+int gz_puct_trees(const void* d_workspace, int32_t n, int32_t num_simulations, void* d_out, void* stream);
+/* Self-play with this search (slots as gz_selfplay_init): per ply the slots'
+ * boards, gz_puct_search, then the same record / restart logic as gz_selfplay_run.
+ * The root visit counts are the policy target: a game's rows wait in the workspace
+ * ([n_slots][200][225] uint16) and, when it ends, go to d_visits [record_cap][225]
+ * at the indices of its records (dropped with records that overflow).  Slot
+ * statistics (gz_selfplay_draws): nodes evaluated, main draws (0 or 1 per ply), 0. */
+size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t num_simulations);
+int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
+                         void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
+                         uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);
+
 /* BGPlannerAI.get_move (bg_planner.py:232-269) for each board: d_ai = the
  * planner's colour P, d_keys = RNG stream; d_moves (-1 = None), d_draws.
  * d_workspace: gz_planner_move_workspace_bytes(n) bytes. */
