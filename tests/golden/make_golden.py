@@ -840,6 +840,33 @@ def part_gnet():
                   "p_f32_b64": enc(np.stack(p_all)), "q_f32_b64": enc(np.stack(q_all))})
 
 
+def part_gnet2():
+    """The reference's GraphNet / OpponentDQN at weights that carry signal (tests/gnet_cases.py:
+    conv weights x GAIN) on 32 of that module's boards."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import gnet_cases as gc
+    h = ref()
+    gn_seed, dqn_seed = gc.CASES[gc.GOLDEN_CASE]
+    gn, dq = h.bg.GraphNet(), h.bg.OpponentDQN()
+    gn.load_state_dict(gc.graphnet_state(gn_seed))
+    dq.load_state_dict(gc.dqn_state(dqn_seed))
+    gn.eval()
+    dq.eval()
+    ids = list(gc.GOLDEN_BOARDS)
+    cells = gc.board_cells()[ids]
+    x = gc.planes_of(cells, torch.float32)
+    with torch.no_grad():
+        lg = gn(x)
+        p = torch.softmax(lg, dim=1).numpy()
+        q = dq(x).numpy()
+    dump("gnet2", {"gn_seed": gn_seed, "dqn_seed": dqn_seed, "gain": gc.GAIN, "boards": ids,
+                   "cells": ["".join(str(int(v)) for v in c) for c in cells],
+                   "logits_f32_b64": gc.encode_f32(lg.numpy()), "p_f32_b64": gc.encode_f32(p),
+                   "q_f32_b64": gc.encode_f32(q)})
+
+
 def _threat_position(rng):
     """A position where some side has an open or closed four (so the 1e6 / -1e5 scores occur)."""
     for _ in range(200):
@@ -1180,7 +1207,7 @@ def part_arena():
 
 PARTS = {"board": part_board, "pattern": part_pattern, "policy": part_policy,
          "rollout": part_rollout, "mcts": part_mcts, "mcts2": part_mcts2, "pvnet": part_pvnet, "prior": part_prior, "pvnet2": part_pvnet2, "augment": part_augment,
-         "games": part_games, "gnet": part_gnet, "planner": part_planner, "planner_mcts": part_planner_mcts,
+         "games": part_games, "gnet": part_gnet, "gnet2": part_gnet2, "planner": part_planner, "planner_mcts": part_planner_mcts,
          "planner_mcts200": part_planner_mcts200,
          "sgd": part_sgd, "arena": part_arena, "arena_plans": part_arena_plans}
 
