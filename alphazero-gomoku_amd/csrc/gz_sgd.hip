@@ -1004,8 +1004,15 @@ __device__ __forceinline__ float fc_wave_sum(float x) {
     return x;
 }
 // one 64-thread workgroup per board: softmax cross-entropy about the max, the value
-// head, dlogits (in place of the logits) and dpre1 (in place of the pre-activation)
-__global__ __launch_bounds__(64) void sgd_fc_loss_kernel(gz_sgd_fc fc, const int64_t* __restrict__ y,
+// head, dlogits (in place of the logits) and dpre1 (in place of the pre-activation).
+// SOFT = false: target = const int64_t* class labels [B].  SOFT = true: target = const
+// float* probability rows [B][225]: ce = sum_i pi_i (lse - s_i) and dlogits_i =
+// (softmax_i P - pi_i) g with P = sum_i pi_i (torch's gradient for probability targets,
+// for any non-negative row); both sums lane-strided in index order, then the shuffle tree.
+// For an exactly one-hot row every product and sum below is exact (1 x, x + 0, softmax 1,
+// also as a fused multiply-add), so the soft step equals the hard one bit for bit.
+template <bool SOFT>
+__global__ __launch_bounds__(64) void sgd_fc_loss_kernel(gz_sgd_fc fc, const void* __restrict__ target,
                                                         const float* __restrict__ v, int B, float scale,
                                                         float* __restrict__ save) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -1017,23 +1024,52 @@ __global__ __launch_bounds__(64) void sgd_fc_loss_kernel(gz_sgd_fc fc, const int
     float e = 0.f;
     for (int i = lane; i < FC_P_OUT; i += 64) e += expf(sb[i] - m);
     e = fc_wave_sum(e);
-    const int64_t yt = y[b];
-    // a label outside [0, 225) (torch's CrossEntropyLoss raises) poisons the loss and every
-    // gradient of the step with NaN instead of training on a substituted class
-    const bool bad = !(yt >= 0 && yt < FC_P_OUT);
-    const int t = bad ? 0 : (int)yt;
-    const float ce = m + logf(e) - sb[t], g = bad ? NAN : scale / (float)B;
+    int64_t yt = 0;
+    int t = 0;
+    float ce, g, P = 0.f;
+    const float* pr = nullptr;
+    if constexpr (SOFT) {
+        pr = (const float*)target + (size_t)b * FC_P_OUT;
+        const float lse = m + logf(e);
+        float c = 0.f;
+        bool neg = false;
+        for (int i = lane; i < FC_P_OUT; i += 64) {
+            const float p = pr[i];
+            neg |= !(p >= 0.f && p < INFINITY);
+            c += p * (lse - sb[i]);
+            P += p;
+        }
+        c = fc_wave_sum(c);
+        P = fc_wave_sum(P);
+        // an entry that is not finite or below 0 (torch would train on it) poisons the
+        // loss and every gradient of the step, as a bad label does
+        const bool bad = __any(neg);
+        ce = bad ? NAN : c;
+        g = bad ? NAN : scale / (float)B;
+    } else {
+        yt = ((const int64_t*)target)[b];
+        // a label outside [0, 225) (torch's CrossEntropyLoss raises) poisons the loss and every
+        // gradient of the step with NaN instead of training on a substituted class
+        const bool bad = !(yt >= 0 && yt < FC_P_OUT);
+        t = bad ? 0 : (int)yt;
+        ce = m + logf(e) - sb[t];
+        g = bad ? NAN : scale / (float)B;
+    }
     // value: h = relu(pre1), val = tanh(w2 . h + b2)
     const float pre1 = sb[FC_P_OUT + lane], h = fmaxf(pre1, 0.f);
     const float val = tanhf(fc_wave_sum(fc.value2_weight[lane] * h) + fc.value2_bias[0]), diff = val - v[b];
     const float dpre2 = 2.f * diff * g * (1.f - val * val);
     __syncthreads();  // every lane has read the logits before they are overwritten
-    for (int i = lane; i < FC_P_OUT; i += 64) sb[i] = (expf(sb[i] - m) / e - (i == t ? 1.f : 0.f)) * g;
+    if constexpr (SOFT) {
+        for (int i = lane; i < FC_P_OUT; i += 64) sb[i] = (expf(sb[i] - m) / e * P - pr[i]) * g;
+    } else {
+        for (int i = lane; i < FC_P_OUT; i += 64) sb[i] = (expf(sb[i] - m) / e - (i == t ? 1.f : 0.f)) * g;
+    }
     sb[FC_P_OUT + lane] = pre1 > 0.f ? dpre2 * fc.value2_weight[lane] : 0.f;
     sb[FS_H + lane] = h;
     if (lane == 0) {
         sb[FS_DP2] = dpre2;
-        sb[FS_DP2 + 1] = yt == t ? ce : NAN;
+        sb[FS_DP2 + 1] = SOFT ? ce : (yt == t ? ce : NAN);
         sb[FS_DP2 + 2] = diff * diff;
     }
 }
@@ -1274,16 +1310,20 @@ extern "C" size_t gz_sgd_fc_workspace_bytes(int32_t boards) {
     return boards < 1 ? 0 : (size_t)boards * FC_SAVE * sizeof(float);
 }
 
-extern "C" int gz_sgd_fc_loss(const gz_sgd_fc* fc, int32_t B, const float* d_pin, const float* d_vin,
-                              const int64_t* d_y, const float* d_v, float scale, float* d_dpin, float* d_dvin,
-                              const gz_sgd_fc_grads* gr, float* d_loss, void* d_ws, void* stream) {
+namespace {
+// gz_sgd_fc_loss (SOFT = false: int64 labels) and gz_sgd_fc_loss_soft (probability rows):
+// the same gemm jobs and small kernel, the per-board kernel by target kind
+template <bool SOFT>
+int sgd_fc_loss_impl(const char* who, const gz_sgd_fc* fc, int32_t B, const float* d_pin, const float* d_vin,
+                     const void* d_y, const float* d_v, float scale, float* d_dpin, float* d_dvin,
+                     const gz_sgd_fc_grads* gr, float* d_loss, void* d_ws, void* stream) {
     if (!fc || !gr || B < 1 || B > GZ_SGD_MAX_BOARDS || !d_pin || !d_vin || !d_y || !d_v || !d_dpin || !d_dvin ||
         !d_loss || !d_ws)
-        return sgd_fail(GZ_ERR_ARG, "gz_sgd_fc_loss: bad arguments");
+        return sgd_fail(GZ_ERR_ARG, (std::string(who) + ": bad arguments").c_str());
     if (!fc->policy_weight || !fc->policy_bias || !fc->value1_weight || !fc->value1_bias || !fc->value2_weight ||
         !fc->value2_bias || !gr->policy_weight || !gr->policy_bias || !gr->value1_weight || !gr->value1_bias ||
         !gr->value2_weight || !gr->value2_bias)
-        return sgd_fail(GZ_ERR_ARG, "gz_sgd_fc_loss: NULL parameter or gradient");
+        return sgd_fail(GZ_ERR_ARG, (std::string(who) + ": NULL parameter or gradient").c_str());
     hipStream_t s = (hipStream_t)stream;
     float* save = (float*)d_ws;
     auto job = [](const float* A, int sak, int sam, const float* Bm, int sbk, int sbn, const float* bias, float* C,
@@ -1308,7 +1348,7 @@ extern "C" int gz_sgd_fc_loss(const gz_sgd_fc* fc, int32_t B, const float* d_pin
     f.n = 2;
     launch(f);
     // (2) the loss terms, dlogits, dpre1
-    sgd_fc_loss_kernel<<<B, 64, 0, s>>>(*fc, d_y, d_v, B, scale, save);
+    sgd_fc_loss_kernel<SOFT><<<B, 64, 0, s>>>(*fc, d_y, d_v, B, scale, save);
     // (3) dWp[i][k] = sum_b dl[b][i] pin[b][k];  dW1[j][k] = sum_b dpre1[b][j] vin[b][k];
     //     dpin[b][k] = sum_i dl[b][i] Wp[i][k];  dvin[b][k] = sum_j dpre1[b][j] W1[j][k]
     FcJobs g{};
@@ -1321,5 +1361,20 @@ extern "C" int gz_sgd_fc_loss(const gz_sgd_fc* fc, int32_t B, const float* d_pin
     g.n = 4;
     launch(g);
     sgd_fc_small_kernel<<<(FC_SMALL + 3) / 4, 256, 0, s>>>(save, B, *gr, d_loss);
-    return sgd_check("gz_sgd_fc_loss");
+    return sgd_check(who);
+}
+}  // namespace
+
+extern "C" int gz_sgd_fc_loss(const gz_sgd_fc* fc, int32_t B, const float* d_pin, const float* d_vin,
+                              const int64_t* d_y, const float* d_v, float scale, float* d_dpin, float* d_dvin,
+                              const gz_sgd_fc_grads* gr, float* d_loss, void* d_ws, void* stream) {
+    return sgd_fc_loss_impl<false>("gz_sgd_fc_loss", fc, B, d_pin, d_vin, d_y, d_v, scale, d_dpin, d_dvin, gr, d_loss,
+                                   d_ws, stream);
+}
+
+extern "C" int gz_sgd_fc_loss_soft(const gz_sgd_fc* fc, int32_t B, const float* d_pin, const float* d_vin,
+                                   const float* d_pi, const float* d_v, float scale, float* d_dpin, float* d_dvin,
+                                   const gz_sgd_fc_grads* gr, float* d_loss, void* d_ws, void* stream) {
+    return sgd_fc_loss_impl<true>("gz_sgd_fc_loss_soft", fc, B, d_pin, d_vin, d_pi, d_v, scale, d_dpin, d_dvin, gr,
+                                  d_loss, d_ws, stream);
 }

@@ -9,6 +9,9 @@
 // (counter-clockwise, axes (1, 2)) and np.flip(axis=2) (training.py:44-51);
 // the label follows the reference's _transform_index (training.py:53-61),
 // which rotates the other way -- kept bit for bit unless GZ_AUG_FIX_LABELS.
+// gz_dataset_pi gives the same samples' policy targets from PUCT visit rows: the row
+// always moves exactly as the planes do and is divided by its sum; a distribution has no
+// analogue of the reference's label map, so GZ_AUG_FIX_LABELS does not apply to it.
 //
 // HBM-bound byte work (2,712 B written per sample): one thread per output cell
 // writes its three plane values; the 80-byte record of a sample is read by the
@@ -118,9 +121,90 @@ __global__ void dataset_labels_kernel(const gz_record* __restrict__ recs, int n,
     val[so] = (float)rec->z;
 }
 
+// ---- visit rows -> policy targets (gz_dataset_pi) ----
+// One wavefront per sample; lane l owns output cells l, l + 64, l + 128, l + 192 (the
+// layout of gz_puct.hip's rows).  The row moves exactly as the planes do:
+// pi[cell] = visits[aug_source(cell)] / sum(visits).  A distribution has no analogue of
+// the reference's label map (which rotates the other way), so GZ_AUG_FIX_LABELS does not
+// apply: a one-hot row lands where the planes-consistent label does.  Counts are at most
+// 4095, so count and sum are exact in float32 and the quotient is one correctly rounded
+// division (hipcc's default for `/`), equal to numpy's float32 division bit for bit.
+// 450 B read and 900 B written per sample: launch-bound at training batch sizes.
+constexpr int PI_WAVES = 4;  // wavefronts (samples) per 256-thread workgroup
+
+template <bool NT>
+__global__ __launch_bounds__(64 * PI_WAVES) void dataset_pi_kernel(const uint16_t* __restrict__ visits, int n,
+                                                                   const int32_t* __restrict__ sel,
+                                                                   const int64_t* __restrict__ ids, long long n_all,
+                                                                   long long count, float* __restrict__ pi) {
+    const int lane = threadIdx.x & 63;
+    for (long long so = (long long)blockIdx.x * PI_WAVES + (threadIdx.x >> 6); so < count;
+         so += (long long)gridDim.x * PI_WAVES) {  // uniform per wavefront
+        const long long s = ids ? ids[so] : so;
+        const SampleRef r =
+            (unsigned long long)s < (unsigned long long)n_all ? sample_ref(s, n, sel) : SampleRef{-1, 0, 0};
+        const bool ok = (unsigned)r.rec < (unsigned)n;
+        const uint16_t* row = visits + (size_t)(ok ? r.rec : 0) * POS;
+        int sum = 0;
+        float c[4] = {};
+        if (ok) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int cell = lane + 64 * q;
+                if (cell < POS) {
+                    sum += row[cell];  // the sum is symmetry-invariant: straight (coalesced) reads
+                    c[q] = (float)row[aug_source(cell / N, cell % N, r.k, r.flip)];
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        // an id or a selection out of range, or an empty row: NaN (the analogue of label -1)
+        const bool bad = !ok || sum == 0;
+        const float den = (float)sum;
+        float* o = pi + so * POS;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int cell = lane + 64 * q;
+            if (cell < POS) {
+                const float p = bad ? __builtin_nanf("") : c[q] / den;
+                if (NT) __builtin_nontemporal_store(p, o + cell);
+                else o[cell] = p;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" void gz_internal_set_error(const char* msg);
+
+extern "C" int gz_dataset_pi(const uint16_t* d_visits, int32_t n, const int32_t* d_sel, int32_t m,
+                             const int64_t* d_ids, int64_t count, float* d_pi, void* stream) {
+    if (n < 0 || m < 0 || count < 0 || (n > 0 && !d_visits) || (m > 0 && !d_sel) || (count > 0 && !d_pi)) {
+        gz_internal_set_error("gz_dataset_pi: bad arguments");
+        return GZ_ERR_ARG;
+    }
+    if (m > 0 && n == 0) {
+        gz_internal_set_error("gz_dataset_pi: augmentation of an empty replay");
+        return GZ_ERR_ARG;
+    }
+    if (count == 0) return GZ_OK;
+    const long long n_all = (long long)n + 8LL * m;
+    long long wg = ((long long)count + PI_WAVES - 1) / PI_WAVES;
+    if (wg > (1LL << 22)) wg = 1LL << 22;  // one wavefront per sample up to 16M samples, grid-stride beyond
+    hipStream_t st = (hipStream_t)stream;
+    if (d_ids)
+        dataset_pi_kernel<false><<<(unsigned)wg, 64 * PI_WAVES, 0, st>>>(d_visits, n, d_sel, d_ids, n_all, count, d_pi);
+    else
+        dataset_pi_kernel<true><<<(unsigned)wg, 64 * PI_WAVES, 0, st>>>(d_visits, n, d_sel, d_ids, n_all, count, d_pi);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gz_internal_set_error((std::string("gz_dataset_pi: ") + hipGetErrorString(e)).c_str());
+        return GZ_ERR_HIP;
+    }
+    return GZ_OK;
+}
 
 namespace {
 int launch(const gz_record* d_records, int32_t n, const int32_t* d_sel, int32_t m, const int64_t* d_ids,

@@ -175,6 +175,7 @@ SIGNATURES = {
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
     "gz_dataset_gather": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P]),
+    "gz_dataset_pi": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _I64, _P, _P]),
     "gz_sgd_workspace_bytes": (_SZ, [_I32]),
     "gz_sgd_forward": (ctypes.c_int, [ctypes.POINTER(SgdNet), _I32, _P, _P, _P, _P, _P]),
     "gz_sgd_backward": (ctypes.c_int, [ctypes.POINTER(SgdNet), _I32, _P, _P, _P, ctypes.POINTER(SgdGrads), _P, _P]),
@@ -182,6 +183,8 @@ SIGNATURES = {
     "gz_sgd_fc_workspace_bytes": (_SZ, [_I32]),
     "gz_sgd_fc_loss": (ctypes.c_int, [ctypes.POINTER(SgdFc), _I32, _P, _P, _P, _P, ctypes.c_float, _P, _P,
                                       ctypes.POINTER(SgdFc), _P, _P, _P]),
+    "gz_sgd_fc_loss_soft": (ctypes.c_int, [ctypes.POINTER(SgdFc), _I32, _P, _P, _P, _P, ctypes.c_float, _P, _P,
+                                           ctypes.POINTER(SgdFc), _P, _P, _P]),
 }
 
 _lib = None

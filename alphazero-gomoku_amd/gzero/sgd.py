@@ -162,8 +162,10 @@ class NetStep:
     gz_sgd_forward -> gz_sgd_fc_loss -> gz_sgd_backward.  ``grads`` is one flat
     buffer; every parameter's ``.grad`` is a view of it, overwritten by each step (no
     zero_grad needed; gradients are never accumulated).  ``step(x, y, v, scale)``
-    returns the batch loss (a device scalar, unscaled); ``scale`` multiplies every
-    gradient (a data-parallel rank's share of the global batch)."""
+    (y: integer class labels [B], or floating probability targets [B, 225] such as PUCT
+    visit distributions -- gz_sgd_fc_loss_soft) returns the batch loss (a device scalar,
+    unscaled); ``scale`` multiplies every gradient (a data-parallel rank's share of the
+    global batch)."""
 
     def __init__(self, net):
         _check_net(net)
@@ -238,7 +240,15 @@ class NetStep:
         if not 1 <= B <= _lib.GZ_SGD_MAX_BOARDS or tuple(x.shape[1:]) != (3, 15, 15):
             raise ValueError(f"gz_sgd: input of shape {tuple(x.shape)}")
         xc = x.detach().float().contiguous()
-        yc = y.detach().to(torch.int64).contiguous()
+        # the target kind picks the kernel: class labels [B] or probability rows [B, 225]
+        soft = y.is_floating_point()
+        if soft and tuple(y.shape) == (B, 225):
+            yc = y.detach().float().contiguous()
+        elif not soft and y.dtype != torch.bool and tuple(y.shape) == (B,):
+            yc = y.detach().to(torch.int64).contiguous()
+        else:
+            raise ValueError(f"gz_sgd: targets of shape {tuple(y.shape)} and dtype {y.dtype} for {B} boards "
+                             f"(integer labels [B] or floating probabilities [B, 225])")
         vc = v.detach().float().reshape(B).contiguous()
         ws, fws, pin, vin, dpin, dvin = self._buffers(B, xc.device)
         self._bind()
@@ -247,11 +257,13 @@ class NetStep:
                    "gz_sgd_forward")
         if self.counts:
             torch._foreach_add_(self.counts, 1)
-        _lib.check(self.lib.gz_sgd_fc_loss(ctypes.byref(self.fc), B, _ptr(pin), _ptr(vin), _ptr(yc), _ptr(vc),
-                                           float(scale), _ptr(dpin), _ptr(dvin), ctypes.byref(self.fcg),
-                                           _ptr(self.loss), _ptr(fws), s), "gz_sgd_fc_loss")
+        fc_loss, who = (self.lib.gz_sgd_fc_loss_soft, "gz_sgd_fc_loss_soft") if soft else \
+            (self.lib.gz_sgd_fc_loss, "gz_sgd_fc_loss")
+        _lib.check(fc_loss(ctypes.byref(self.fc), B, _ptr(pin), _ptr(vin), _ptr(yc), _ptr(vc), float(scale),
+                           _ptr(dpin), _ptr(dvin), ctypes.byref(self.fcg), _ptr(self.loss), _ptr(fws), s), who)
         _lib.check(self.lib.gz_sgd_backward(ctypes.byref(self.st), B, _ptr(xc), _ptr(dpin), _ptr(dvin),
                                             ctypes.byref(self.gr), _ptr(ws), s), "gz_sgd_backward")
         # a copy: the loss buffer is overwritten by the next step (a label outside
-        # [0, 225) makes it NaN, and every gradient with it)
+        # [0, 225), or a probability that is negative or not finite, makes it NaN, and
+        # every gradient with it)
         return self.loss[0].clone()

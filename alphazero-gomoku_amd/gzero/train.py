@@ -13,7 +13,8 @@ Semantics follow the reference's training loop:
   shuffle)`` (training.py:453-454), produced by torch's own sampler over an index
   set so the torch RNG is consumed exactly as the reference's loader does.
 * ``DeviceTrainer.train_epoch`` / ``validate_epoch`` = training.py:277-337:
-  CrossEntropy(logits, move) + MSE(value, z), ``clip_grad_norm_`` at
+  CrossEntropy(logits, move) + MSE(value, z) (a soft dataset, DeviceDataset(...,
+  visits=...): CrossEntropy against the visit distribution), ``clip_grad_norm_`` at
   ``grad_clip``, Adam(lr 8e-4, wd 1e-5) and StepLR(2, 0.85) as in main()
   (training.py:387-388,379-381); the loss is the mean of per-batch float
   losses (accumulated on the device in float64, one host sync per epoch).
@@ -59,7 +60,13 @@ class DeviceDataset(Dataset):
     """GomokuSelfPlayDataset over device records (training.py:104-134)."""
 
     def __init__(self, records, use_augmentation=True, augment_ratio=0.5, fix_labels=False, rng=None,
-                 n_records=None):
+                 n_records=None, visits=None):
+        """visits: the PUCT root visit counts of the records ([n, 225], a device int16 /
+        uint16 tensor or a numpy uint16 array, row i belonging to record i;
+        SelfPlayEngine.visits / visits_device).  The dataset is then ``soft``: gather,
+        materialize and __getitem__ return (x, pi, v) with pi float32 [B, 225], the
+        normalised visit row moved by the sample's symmetry exactly as its planes are
+        (gz_dataset_pi), in place of the move label."""
         if isinstance(records, torch.Tensor):
             self.d_records = records
             n = int(n_records if n_records is not None else records.numel() // RECORD_DTYPE.itemsize)
@@ -73,6 +80,18 @@ class DeviceDataset(Dataset):
         self.m = len(sel)
         self.flags = _lib.GZ_AUG_FIX_LABELS if fix_labels else 0
         self.d_sel = torch.tensor(sel if sel else [0], dtype=torch.int32, device="cuda")
+        self.soft = visits is not None
+        self.d_visits = None
+        if self.soft:
+            if isinstance(visits, torch.Tensor):
+                if visits.dtype not in (torch.int16, torch.uint16):
+                    raise ValueError(f"visits must be int16 / uint16 counts, not {visits.dtype}")
+                d = visits.to("cuda")
+            else:
+                d = torch.from_numpy(np.ascontiguousarray(visits, np.uint16).view(np.int16)).to("cuda")
+            if d.numel() < n * 225 or (d.dim() == 2 and d.shape[1] != 225):
+                raise ValueError(f"visits of shape {tuple(d.shape)} for {n} records")
+            self.d_visits = d.reshape(-1)[: n * 225].contiguous()
 
     def __len__(self):
         return self.n + 8 * self.m
@@ -81,7 +100,8 @@ class DeviceDataset(Dataset):
         check_ids(self, d_ids)
 
     def gather(self, d_ids, out=None, check=True):
-        """Samples d_ids (device int64) -> (x [B,3,15,15] f32, y [B] int64, v [B,1] f32) on the device.
+        """Samples d_ids (device int64) -> (x [B,3,15,15] f32, y [B] int64, v [B,1] f32) on the device
+        (a soft dataset: y = pi [B,225] f32).
         ``check`` validates the ids first (one host sync; the trainer checks a whole
         epoch's ids once and passes False)."""
         if check:
@@ -89,13 +109,19 @@ class DeviceDataset(Dataset):
         b = int(d_ids.numel())
         if out is None:
             out = (torch.empty((b,) + SAMPLE_SHAPE, dtype=torch.float32, device="cuda"),
-                   torch.empty(b, dtype=torch.int64, device="cuda"),
+                   torch.empty((b, 225), dtype=torch.float32, device="cuda") if self.soft
+                   else torch.empty(b, dtype=torch.int64, device="cuda"),
                    torch.empty((b, 1), dtype=torch.float32, device="cuda"))
         x, y, v = out
+        # (the planes kernel writes the move labels too: a scratch for a soft dataset)
+        lab = torch.empty(b, dtype=torch.int64, device="cuda") if self.soft else y
         L = _lib.load()
         _lib.check(L.gz_dataset_gather(_dev_ptr(self.d_records), self.n, _dev_ptr(self.d_sel), self.m,
-                                       _dev_ptr(d_ids), b, self.flags, _dev_ptr(x), _dev_ptr(y), _dev_ptr(v),
+                                       _dev_ptr(d_ids), b, self.flags, _dev_ptr(x), _dev_ptr(lab), _dev_ptr(v),
                                        _stream()), "gz_dataset_gather")
+        if self.soft:
+            _lib.check(L.gz_dataset_pi(_dev_ptr(self.d_visits), self.n, _dev_ptr(self.d_sel), self.m,
+                                       _dev_ptr(d_ids), b, _dev_ptr(y), _stream()), "gz_dataset_pi")
         return x, y, v
 
     def materialize(self):
@@ -107,6 +133,11 @@ class DeviceDataset(Dataset):
         L = _lib.load()
         _lib.check(L.gz_dataset_build(_dev_ptr(self.d_records), self.n, _dev_ptr(self.d_sel), self.m, self.flags,
                                       _dev_ptr(x), _dev_ptr(y), _dev_ptr(v), _stream()), "gz_dataset_build")
+        if self.soft:
+            pi = torch.empty((s, 225), dtype=torch.float32, device="cuda")
+            _lib.check(L.gz_dataset_pi(_dev_ptr(self.d_visits), self.n, _dev_ptr(self.d_sel), self.m, None, s,
+                                       _dev_ptr(pi), _stream()), "gz_dataset_pi")
+            return x, pi, v
         return x, y, v
 
     def __getitem__(self, i):

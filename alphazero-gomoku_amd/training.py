@@ -169,8 +169,13 @@ def play_one_game(ai_black, ai_white, step_timeout: float = 10.0,
 def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium", beta: float = 0.2,
              seed: int = 0, n_slots: int = 4096, game_id_base: int = 0, model=None,
              plies_per_step: int = 16, planner_steps: int = 0, planner=None,
-             pv_mode: str = "tree") -> Tuple[SimpleReplay, dict]:
+             pv_mode: str = "tree", search: str = "reference", temp_plies: int = 12) -> Tuple[SimpleReplay, dict]:
     """Play game ids [game_id_base, game_id_base + n_games) concurrently on the GPU.
+
+    ``search="puct"``: the network-guided search (SelfPlayEngine(search="puct",
+    temp_plies=...)); it needs ``model`` and ``planner_steps == 0`` and ignores beta and
+    pv_mode.  stats["visits"] is then uint16 [len(replay), 225], the root visit counts
+    behind every replay entry, in replay order (the policy target).
 
     With ``model`` (a GomokuModel) the policy-value network is evaluated on every
     node the searches create, as the reference does -- by default incrementally
@@ -182,6 +187,7 @@ def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium
     from gzero.selfplay import SelfPlayEngine
     c_puct, expl = {"easy": (1.4, 0.2), "medium": (1.6, 0.05), "hard": (1.8, 0.01)}[difficulty]
     slots = min(n_slots, n_games)
+    puct = _check_search(search, model, planner_steps)
     gnw = None
     if planner_steps:
         if planner is None:
@@ -189,14 +195,15 @@ def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium
             planner = BGPlannerAI(1, difficulty)
         gnw = planner.device_weights()
     pvw = model.device_weights() if model is not None else None
-    tree = pv_mode == "tree" and pvw is not None and pvw.precision == "f16x3"
+    tree = pv_mode == "tree" and pvw is not None and pvw.precision == "f16x3" and not puct
     eng = SelfPlayEngine(n_slots=slots, num_simulations=num_simulations, c_puct=c_puct, exploration=expl,
                          beta=beta, seed=seed, pv_weights=pvw,
                          plies_per_step=min(plies_per_step, 4) if tree else plies_per_step,
                          game_id_base=game_id_base, planner_steps=planner_steps,
-                         planner_difficulty=difficulty, gn_weights=gnw, pv_mode="tree" if tree else "full")
+                         planner_difficulty=difficulty, gn_weights=gnw, pv_mode="tree" if tree else "full",
+                         search=search, temp_plies=temp_plies)
     replay = SimpleReplay()
-    done = {}
+    done, rows = {}, {}
     moves = 0
     t0 = time.time()
     while len(done) < n_games:
@@ -204,17 +211,102 @@ def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium
         c = eng.counters()
         moves += int(c["moves"])
         recs = eng.records()
-        recs = recs[recs["game_id"] < game_id_base + n_games]
+        vis = eng.visits() if puct else None
+        keep = recs["game_id"] < game_id_base + n_games
+        recs = recs[keep]
         for gid in np.unique(recs["game_id"]):
             if int(gid) not in done:
                 g = recs[recs["game_id"] == gid]
-                done[int(gid)] = g[np.argsort(g["ply"])]
+                order = np.argsort(g["ply"])
+                done[int(gid)] = g[order]
+                if puct:
+                    rows[int(gid)] = vis[keep][recs["game_id"] == gid][order]
     slices = {}
     for gid in sorted(done):
         slices[gid] = (len(replay), len(done[gid]))
         replay.extend_records(done[gid])
-    return replay, {"games": len(done), "moves_played": moves, "seconds": time.time() - t0,
-                    "game_slices": slices}
+    stats = {"games": len(done), "moves_played": moves, "seconds": time.time() - t0, "game_slices": slices}
+    if puct:
+        stats["visits"] = np.concatenate([rows[gid] for gid in sorted(done)]).astype(np.uint16).reshape(-1, 225)
+    return replay, stats
+
+
+def _check_search(search, model, planner_steps) -> bool:
+    """True for the PUCT search, whose requirements are checked here."""
+    if search not in ("reference", "puct"):
+        raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
+    if search == "puct":
+        if model is None:
+            raise ValueError("search='puct' needs a model (the network guides the search)")
+        if int(planner_steps) != 0:
+            raise ValueError("search='puct' has no rollouts: planner_steps must be 0")
+    return search == "puct"
+
+
+def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: str = "medium", seed: int = 0,
+                         n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
+                         plies_per_step: int = 4):
+    """training.run_iteration's self-play with search="puct" (one rank): game ids
+    [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
+    visit rows collected on the device.  Every step's finished games are filtered to
+    those ids (a slot refills with id + n_slots, possibly past the range) and appended
+    to the collection by device index arithmetic; one host synchronisation per step
+    reads the engine's counters together with the number of wanted games that finished
+    in the step (counted on the device over the record buffer).  At the end the rows
+    are sorted by (game id, ply), the visit rows following.
+    Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
+    from gzero.selfplay import SelfPlayEngine
+    _check_search("puct", model, 0)
+    c_puct = {"easy": 1.4, "medium": 1.6, "hard": 1.8}[difficulty]
+    slots = min(n_slots, n_games)
+    eng = SelfPlayEngine(n_slots=slots, num_simulations=num_simulations, c_puct=c_puct, seed=seed,
+                         pv_weights=model.device_weights(), plies_per_step=plies_per_step,
+                         game_id_base=game_id_base, search="puct", temp_plies=temp_plies)
+    lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
+    cap = n_games * _MAX_GAME_RECORDS
+    # row `cap` takes the rows of games outside [lo, hi)
+    rows = torch.empty((cap + 1, 10), dtype=torch.int64, device="cuda")
+    vis = torch.empty((cap + 1, 225), dtype=torch.int16, device="cuda")
+    key = torch.zeros(cap + 1, dtype=torch.int64, device="cuda")
+    kept = torch.zeros((), dtype=torch.int64, device="cuda")
+    rec64 = eng.d_records.view(torch.int64).view(eng.record_cap, 10)   # column 8: the game id
+    rec16 = eng.d_records.view(torch.int16).view(eng.record_cap, 40)   # column 36: the ply
+    rvis = eng.d_visits.view(eng.record_cap, 225)
+    slot_idx = torch.arange(eng.record_cap, device="cuda")
+    games = moves = steps = 0
+    max_steps = (-(-n_games // slots) + 1) * 200 // eng.plies_per_step + 8
+    t0 = time.time()
+    while games < n_games:
+        if steps >= max_steps:
+            raise RuntimeError(f"selfplay_puct_device: {games} of {n_games} games after {steps} steps")
+        eng.step()
+        steps += 1
+        cnt = eng.d_counters[0:4].view(torch.int32).to(torch.int64)
+        gid, ply = rec64[:, 8], rec16[:, 36].to(torch.int64)
+        first = ((slot_idx < cnt) & (gid >= lo) & (gid < hi) & (ply == 0)).sum().reshape(1)
+        # the step's one host synchronisation: records, drops, moves, wanted games finished
+        c = torch.cat([eng.d_counters.view(torch.int64), first]).cpu().numpy()
+        head = c[:2].view(np.int32)  # records, leaves, records_dropped, leaves_dropped
+        if head[2]:
+            raise RuntimeError(f"selfplay_puct_device: {int(head[2])} records dropped by the engine buffer")
+        moves += int(c[2])
+        games += int(c[5])
+        n = min(int(head[0]), eng.record_cap)
+        if n == 0:
+            continue
+        want = (gid[:n] >= lo) & (gid[:n] < hi)
+        pos = kept + torch.cumsum(want, 0) - 1
+        dest = torch.where(want & (pos < cap), pos, cap)
+        rows.index_copy_(0, dest, rec64[:n])
+        vis.index_copy_(0, dest, rvis[:n])
+        key.index_copy_(0, dest, (gid[:n] - lo) * 256 + ply[:n])
+        kept = kept + want.sum()
+    n = int(kept.item())
+    if n > cap:
+        raise RuntimeError(f"selfplay_puct_device: {n} records for {n_games} games")
+    order = torch.argsort(key[:n])
+    return (rows[:n][order].view(torch.uint8).view(n, 80), vis[:n][order], n,
+            {"games": games, "moves_played": moves, "steps": steps, "seconds": time.time() - t0})
 
 
 def selfplay_device(n_games: int, id_lo: int, id_hi: int, num_simulations: int = 200, difficulty: str = "medium",
@@ -475,24 +567,40 @@ def _fmt_duration(seconds: float) -> str:
 def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_simulations: int = 200,
                   difficulty: str = "medium", beta: float = 0.2, planner_steps: int = 5, seed: int = 0,
                   train_split: float = 0.9, batch_size: int = 128, epochs: int = 2, augment_ratio: float = 0.35,
-                  planner=None, verbose: bool = True) -> dict:
+                  planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
     35 % 8-fold augmentation, a 90/10 split drawn from ``random``, ``epochs``
-    epochs of the data-parallel SGD step and the StepLR step."""
+    epochs of the data-parallel SGD step and the StepLR step.
+
+    ``search="puct"``: the games are played by the network-guided search on the current
+    model (selfplay_puct_device; beta, planner_steps and planner are not used) and the
+    network trains on the root visit distributions (DeviceDataset(..., visits=...), the
+    soft-target loss) instead of the moves played.  One rank only: the record exchange
+    does not carry visit rows yet."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     rank, ws = gdist.world()
+    if search not in ("reference", "puct"):
+        raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
+    if search == "puct" and ws > 1:
+        raise NotImplementedError("search='puct' collects on one rank only: RecordExchange does not carry visit rows")
     t0 = time.time()
     id_lo = it * ws * games_per_iteration
     replay_base = id_lo + rank * games_per_iteration
-    # every rank's records reach every rank step by step (RecordExchange), sorted by
-    # game id at the end: the same replay on every rank, in the reference's game order
-    d, n_rec, st = selfplay_device(games_per_iteration, id_lo, id_lo + ws * games_per_iteration,
-                                   num_simulations=num_simulations, difficulty=difficulty, beta=beta, seed=seed,
-                                   game_id_base=replay_base, model=model, planner_steps=planner_steps,
-                                   planner=planner)
+    d_vis = None
+    if search == "puct":
+        d, d_vis, n_rec, st = selfplay_puct_device(games_per_iteration, num_simulations=num_simulations,
+                                                   difficulty=difficulty, seed=seed, game_id_base=replay_base,
+                                                   model=model, temp_plies=temp_plies)
+    else:
+        # every rank's records reach every rank step by step (RecordExchange), sorted by
+        # game id at the end: the same replay on every rank, in the reference's game order
+        d, n_rec, st = selfplay_device(games_per_iteration, id_lo, id_lo + ws * games_per_iteration,
+                                       num_simulations=num_simulations, difficulty=difficulty, beta=beta, seed=seed,
+                                       game_id_base=replay_base, model=model, planner_steps=planner_steps,
+                                       planner=planner)
     d = d.reshape(-1)
     moves = torch.tensor([float(st["moves_played"])], dtype=torch.float64, device="cuda")
     if ws > 1:
@@ -502,7 +610,7 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     out = {"iteration": it, "records": n_rec, "selfplay_s": t1 - t0, "moves_played": int(moves.item())}
     if n_rec == 0:
         return dict(out, skipped=True)
-    ds = DeviceDataset(d, use_augmentation=True, augment_ratio=augment_ratio, n_records=n_rec)
+    ds = DeviceDataset(d, use_augmentation=True, augment_ratio=augment_ratio, n_records=n_rec, visits=d_vis)
     if len(ds) < 8:  # training.py:431-433
         return dict(out, skipped=True)
     n = len(ds)
@@ -558,12 +666,15 @@ def _broadcast_int(x: int) -> int:
 
 
 def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int] = None, models_dir: str = "models",
-         num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6):
+         num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
+         temp_plies: int = 8):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
     games) and the same checkpoint names.  Under torchrun every rank plays its
-    own games and trains data-parallel (gzero.train.DeviceTrainer)."""
+    own games and trains data-parallel (gzero.train.DeviceTrainer).
+    ``search="puct"`` (one rank): self-play by the network-guided search, training on
+    its visit distributions (run_iteration)."""
     import math
     import os
     from gzero import dist as gdist
@@ -584,7 +695,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     history = []
     for it in range(1, iterations + 1):
         res = run_iteration(model, trainer, it, games_per_iteration, num_simulations=num_simulations,
-                            planner_steps=planner_steps, seed=seed, verbose=rank == 0)
+                            planner_steps=planner_steps, seed=seed, verbose=rank == 0, search=search,
+                            temp_plies=temp_plies)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

@@ -390,6 +390,18 @@ int gz_dataset_build(const gz_record* d_records, int32_t n, const int32_t* d_sel
  * Ids outside [0, n+8m) give zero planes and label -1. */
 int gz_dataset_gather(const gz_record* d_records, int32_t n, const int32_t* d_sel, int32_t m, const int64_t* d_ids,
                       int64_t count, int32_t flags, float* d_x, int64_t* d_y, float* d_v, void* stream);
+/* The policy targets of the same samples from PUCT root visit counts (gz_selfplay_puct_run's
+ * d_visits, uint16 [n][225], row i belonging to record i): d_pi float32 [count][225],
+ * pi[cell] = visits[source(cell)] / sum(visits), where the row moves exactly as the planes
+ * of that sample do (rot90^k, then the flip).  A distribution has no analogue of the
+ * reference's label map, so GZ_AUG_FIX_LABELS does not apply here: a one-hot row lands on
+ * the label that gz_dataset_gather gives with GZ_AUG_FIX_LABELS.  One correctly rounded
+ * float32 division per cell (counts are at most 4095, so both operands are exact).
+ * d_ids NULL: samples 0..count-1 in order (count = n + 8m is the whole set).  An id
+ * outside [0, n+8m), a selection outside [0, n) or a row whose sum is 0 gives a row of
+ * NaN (the analogue of label -1: it poisons the loss instead of training on nothing). */
+int gz_dataset_pi(const uint16_t* d_visits, int32_t n, const int32_t* d_sel, int32_t m, const int64_t* d_ids,
+                  int64_t count, float* d_pi, void* stream);
 
 /* ---- f1 training step: the policy-value net's convolutional part in training mode
  * (training.py:277-311 over neural_network.py:74-91, 132-159: BatchNorm on batch
@@ -470,6 +482,17 @@ size_t gz_sgd_fc_workspace_bytes(int32_t boards);
 int gz_sgd_fc_loss(const gz_sgd_fc* fc, int32_t boards, const float* d_pin, const float* d_vin, const int64_t* d_y,
                    const float* d_v, float scale, float* d_dpin, float* d_dvin, const gz_sgd_fc_grads* grads,
                    float* d_loss, void* d_ws, void* stream);
+/* The same step against probability targets d_pi float32 [boards][225] (the visit
+ * distribution of a PUCT search, gz_dataset_pi) in place of class labels: per board
+ * ce = sum_i pi_i (logsumexp - logit_i) and dlogits_i = (softmax_i sum(pi) - pi_i) scale /
+ * boards, torch's CrossEntropyLoss with probability targets for any non-negative row
+ * (normalised or not); d_loss[1] is the mean soft cross-entropy.  The value head and
+ * everything else are gz_sgd_fc_loss's, and rows that are exactly one-hot give its outputs
+ * bit for bit.  An entry that is not finite or is below 0 makes the loss and every
+ * gradient of the step NaN (as a label outside [0, 225) does there). */
+int gz_sgd_fc_loss_soft(const gz_sgd_fc* fc, int32_t boards, const float* d_pin, const float* d_vin,
+                        const float* d_pi, const float* d_v, float scale, float* d_dpin, float* d_dvin,
+                        const gz_sgd_fc_grads* grads, float* d_loss, void* d_ws, void* stream);
 /* checkers: a copy of a saved tensor of the last gz_sgd_forward on this workspace:
  * which 0..3 = the inputs of the four residual convs (a0, h1, a1, h2), 4..7 = their
  * outputs y1..y4, 8 = the tower output a2, 9 = y0 = conv0's output (fp32 NHWC) */
