@@ -10,6 +10,8 @@
 // v_mfma_f32_16x16x32_f16 A-fragment order [ks][n-tile 4][lane 64][8]
 // (n = 16*n_tile + lane%16, k = 32*ks + 8*(lane/16) + j).
 #pragma once
+#include <cstddef>
+#include <cstdint>
 
 namespace gzgn {
 constexpr int HID = 64;
@@ -62,7 +64,13 @@ constexpr int TOTAL = D2_P + 16 * 15 * 256;
 //   [0, 450) policy conv output (channel-major flatten), zero to REC_X;
 //   [REC_X, REC_X + 450) the one-hot stone inputs [black 225 | white 225], zero to REC
 constexpr int REC_X = 464;
-constexpr int REC = 928;
+constexpr int REC = 2 * REC_X;  // 928
+// the split heads' scratch behind the records in the caller's workspace: per row the
+// logits (225), h0 and h1 (256 each), HN_LD floats apart
+constexpr int HN_LD = 256;
+constexpr int HN_ROW = 3 * HN_LD;
+// gz_gn_workspace_bytes per row
+constexpr size_t WS_ROW_BYTES = (size_t)(REC + HN_ROW) * sizeof(float);
 
 // Incremental GraphNet (gn_inc_kernel): a map slot holds one board's 4 conv inputs
 // embed, L1, L3, L5 (each [plane hi/lo][cg 8][225][8] halves) and its policy-conv

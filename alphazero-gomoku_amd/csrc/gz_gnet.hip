@@ -19,7 +19,7 @@
 
 #include "gz_f16conv.h"
 #include "gz_gnet.h"
-#include "../../include/gzero.h"
+#include "gz_internal.h"
 
 using namespace gzc;
 using namespace gzgn;
@@ -515,8 +515,6 @@ constexpr int HBS = 16, PFS = 6;  // boards per workgroup; k-blocks of fragments
 // workgroups instead of 32, each with a quarter of a wave's MFMA chain per tile.
 // Products, their order and the epilogues are gn_heads_kernel's, so p and q are the
 // same bits.
-constexpr int HN_LD = 256;  // scratch row stride (logits 225, hidden 256)
-constexpr int HN_ROW = 3 * HN_LD;  // scratch floats per row: logits, h0, h1 (in the caller's workspace)
 
 __device__ __forceinline__ void hn_tile(const float* __restrict__ Wp, int KB, int NTILES, int nt, int lane,
                                         const float* __restrict__ arow, f32x4& acc) {
@@ -1435,51 +1433,32 @@ extern "C" int gz_gn_stamps_read(unsigned long long* out, int reset) {
 }
 #endif
 
-extern "C" void gz_internal_set_error(const char* msg);
-
 extern "C" size_t gz_gn_weight_floats(void) { return (size_t)TOTAL; }
 
 // n records, then the split heads' scratch for n rows
-extern "C" size_t gz_gn_workspace_bytes(int32_t n) { return (size_t)(n < 1 ? 1 : n) * (REC + HN_ROW) * sizeof(float); }
-
-static int gn_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-    return cus;
-}
-
-static int gn_launch_check(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string(what) + ": " + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
-}
+extern "C" size_t gz_gn_workspace_bytes(int32_t n) { return (size_t)(n < 1 ? 1 : n) * WS_ROW_BYTES; }
 
 // the search roots' full forward: maps and policy-conv outputs into slots 0..n-1
 // (gz_plan.hip; d_rec: n record rows of scratch)
-extern "C" int gz_internal_gn_roots(const float* d_weights, const uint32_t* d_rows, int32_t n, void* d_slots,
+int gz_internal_gn_roots(const float* d_weights, const uint32_t* d_rows, int32_t n, void* d_slots,
                                     float* d_rec, void* stream) {
     if (n <= 0) return GZ_OK;
-    const int cus = gn_cus();
+    const int cus = gz_cu_count();
     gn_kernel<<<n < 2 * cus ? n : 2 * cus, NT, 0, (hipStream_t)stream>>>(d_weights, d_rows, n, nullptr, d_rec, nullptr,
                                                                        (char*)d_slots, nullptr);
-    return gn_launch_check("gn_kernel (roots)");
+    return gz_check_launch("gn_kernel (roots)");
 }
 
 // the planner nets over tagged rows (gz_plan.hip's collect kernel): full-forward
 // rows (keeping their maps in their slots) and incremental rows, then the batched
 // heads over all rows
-extern "C" int gz_internal_gn_forward_tagged(const float* d_weights, const uint32_t* d_rows, int32_t max_rows,
-                                             const int32_t* d_count, const int32_t* d_full_list,
-                                             const int32_t* d_full_count, const int32_t* d_inc_list,
-                                             const int32_t* d_inc_count, const void* d_tags, void* d_slots,
-                                             float* d_p, float* d_q, float* d_rec, float* d_hscratch,
-                                             int32_t* d_queue, void* stream) {
+int gz_internal_gn_forward_tagged(const float* d_weights, const uint32_t* d_rows, int32_t max_rows,
+                                  const int32_t* d_count, const int32_t* d_full_list, const int32_t* d_full_count,
+                                  const int32_t* d_inc_list, const int32_t* d_inc_count, const void* d_tags,
+                                  void* d_slots, float* d_p, float* d_q, float* d_rec, float* d_hscratch,
+                                  int32_t* d_queue, void* stream) {
     if (max_rows <= 0) return GZ_OK;
-    const int cus = gn_cus();
+    const int cus = gz_cu_count();
     hipStream_t s = (hipStream_t)stream;
     gn_kernel<<<max_rows < 2 * cus ? max_rows : 2 * cus, NT, 0, s>>>(d_weights, d_rows, max_rows, d_full_count, d_rec,
                                                                      d_full_list, (char*)d_slots, (const GnTag*)d_tags);
@@ -1495,7 +1474,7 @@ extern "C" int gz_internal_gn_forward_tagged(const float* d_weights, const uint3
                                                               (const GnTag*)d_tags, (char*)d_slots, d_rec, per,
                                                               d_queue);
     gn_heads_launch(d_weights, d_rec, max_rows, d_count, d_p, d_q, nullptr, cus, s, d_hscratch);
-    return gn_launch_check("gn_inc_kernel");
+    return gz_check_launch("gn_inc_kernel");
 }
 
 // rows by kind for gz_gn_forward_chain
@@ -1511,27 +1490,23 @@ extern "C" size_t gz_gn_slot_bytes(void) { return SLOT_BYTES; }
 
 extern "C" size_t gz_gn_chain_workspace_bytes(int32_t n) {
     const size_t m = (size_t)(n < 1 ? 1 : n);
-    return m * (REC + HN_ROW) * 4 + 2 * m * 4 + 256;
+    return m * WS_ROW_BYTES + 2 * m * 4 + 256;
 }
 
 extern "C" int gz_gn_forward_chain(const float* d_weights, const uint32_t* d_boards, int32_t n, const void* d_tags,
                                    void* d_slots, float* d_p, float* d_q, void* d_workspace, void* stream) {
-    if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_tags || !d_slots || !d_p || !d_q || !d_workspace))) {
-        gz_internal_set_error("gz_gn_forward_chain: bad arguments");
-        return GZ_ERR_ARG;
-    }
+    if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_tags || !d_slots || !d_p || !d_q || !d_workspace)))
+        return gz_fail(GZ_ERR_ARG, "gz_gn_forward_chain: bad arguments");
     if (n == 0) return GZ_OK;
     hipStream_t s = (hipStream_t)stream;
     float* rec = (float*)d_workspace;
     float* hsc = rec + (size_t)n * REC;
     int32_t* lists = (int32_t*)(hsc + (size_t)n * HN_ROW);
     int32_t* counts = lists + 2 * (size_t)n;
-    if (hipMemsetAsync(counts, 0, 12, s) != hipSuccess) {  // the two list counts, gn_inc_kernel's queue head
-        gz_internal_set_error("gz_gn_forward_chain: memset");
-        return GZ_ERR_HIP;
-    }
+    if (hipMemsetAsync(counts, 0, 12, s) != hipSuccess)  // the two list counts, gn_inc_kernel's queue head
+        return gz_fail(GZ_ERR_HIP, "gz_gn_forward_chain: memset");
     gn_split_kernel<<<(n + 255) / 256, 256, 0, s>>>((const GnTag*)d_tags, n, lists, counts);
-    int rc = gn_launch_check("gn_split_kernel");
+    int rc = gz_check_launch("gn_split_kernel");
     if (rc) return rc;
     return gz_internal_gn_forward_tagged(d_weights, d_boards, n, nullptr, lists, counts, lists + n, counts + 1,
                                          d_tags, d_slots, d_p, d_q, rec, hsc, counts + 2, stream);
@@ -1539,23 +1514,14 @@ extern "C" int gz_gn_forward_chain(const float* d_weights, const uint32_t* d_boa
 
 extern "C" int gz_gn_forward(const float* d_weights, const uint32_t* d_boards, int32_t n, const int32_t* d_count,
                              float* d_p, float* d_q, float* d_logits, void* d_workspace, void* stream) {
-    if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_p || !d_q || !d_workspace))) {
-        gz_internal_set_error("gz_gn_forward: bad arguments (d_workspace: gz_gn_workspace_bytes(n))");
-        return GZ_ERR_ARG;
-    }
+    if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_p || !d_q || !d_workspace)))
+        return gz_fail(GZ_ERR_ARG, "gz_gn_forward: bad arguments (d_workspace: gz_gn_workspace_bytes(n))");
     if (n == 0) return GZ_OK;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+    const int cus = gz_cu_count();
     int grid = n < 2 * cus ? n : 2 * cus;
     hipStream_t s = (hipStream_t)stream;
     gn_kernel<<<grid, NT, 0, s>>>(d_weights, d_boards, n, d_count, (float*)d_workspace, nullptr, nullptr, nullptr);
     gn_heads_launch(d_weights, (const float*)d_workspace, n, d_count, d_p, d_q, d_logits, cus, s,
                     (float*)d_workspace + (size_t)n * REC);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("gn_kernel: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    return gz_check_launch("gn_kernel");
 }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "gz_gnet.h"
+#include "gz_internal.h"
 #include "gz_search.h"
 
 using namespace gz;
@@ -91,9 +92,8 @@ struct GnStats {
 
 __host__ __device__ inline size_t ctx_stride(int S) { return sizeof(PlanCtx) + tree_bytes_for(S); }
 
-constexpr size_t GN_REC_BYTES = 928 * 4;  // a net record (gz_gnet.h REC)
-// gz_gn_workspace_bytes(1): the record + the split heads' scratch (3 x 256 floats), checked at run time
-constexpr size_t GN_WS_BYTES = GN_REC_BYTES + 3 * 256 * 4;
+// gz_gn_forward's workspace per row: the net record + the split heads' scratch
+constexpr size_t GN_WS_BYTES = gzgn::WS_ROW_BYTES;
 
 struct Workspace {
     char* ctx;
@@ -130,7 +130,7 @@ __host__ __device__ inline Workspace carve(void* base, int n, int S) {
     const size_t nj = (size_t)n * (S > 0 ? S : 1), C = chunk_rows(n, S);
     Workspace w;
     w.ctr = (Counters*)p;
-    w.ctr2 = w.ctr + 1;
+    w.ctr2 = &w.ctr[1];
     p += align256(2 * sizeof(Counters));
     w.stats = (GnStats*)p;
     p += align256(sizeof(GnStats));
@@ -810,7 +810,7 @@ __global__ void plan_gn_check_kernel(Workspace w) {
     if (row >= w.ctr->rows) return;
     bool bad = false;
     for (int e = threadIdx.x; e < 450; e += blockDim.x)
-        bad |= __float_as_uint(w.gn_rec[(size_t)row * 928 + e]) != __float_as_uint(w.chk_rec[(size_t)row * 928 + e]);
+        bad |= __float_as_uint(w.gn_rec[(size_t)row * gzgn::REC + e]) != __float_as_uint(w.chk_rec[(size_t)row * gzgn::REC + e]);
     for (int e = threadIdx.x; e < 225; e += blockDim.x) {
         bad |= __float_as_uint(w.gn_p[(size_t)row * 225 + e]) != __float_as_uint(w.chk_p[(size_t)row * 225 + e]);
         bad |= __float_as_uint(w.gn_q[(size_t)row * 225 + e]) != __float_as_uint(w.chk_q[(size_t)row * 225 + e]);
@@ -1180,53 +1180,27 @@ __global__ void boards_to_rows_kernel(const gz_board_state* boards, int n, uint3
 
 }  // namespace
 
-extern "C" void gz_internal_set_error(const char* msg);
-extern "C" int gz_gn_forward(const float* d_weights, const uint32_t* d_boards, int32_t n, const int32_t* d_count,
-                             float* d_p, float* d_q, float* d_logits, void* d_workspace, void* stream);
-extern "C" size_t gz_gn_workspace_bytes(int32_t n);
-extern "C" int gz_internal_gn_roots(const float* d_weights, const uint32_t* d_rows, int32_t n, void* d_slots,
-                                    float* d_rec, void* stream);
-extern "C" int gz_internal_gn_forward_tagged(const float* d_weights, const uint32_t* d_rows, int32_t max_rows,
-                                             const int32_t* d_count, const int32_t* d_full_list,
-                                             const int32_t* d_full_count, const int32_t* d_inc_list,
-                                             const int32_t* d_inc_count, const void* d_tags, void* d_slots,
-                                             float* d_p, float* d_q, float* d_rec, float* d_hscratch,
-                                             int32_t* d_queue, void* stream);
-
-static int plan_fail(int code, const char* msg) {
-    gz_internal_set_error(msg);
-    return code;
-}
-
-static int plan_check(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return plan_fail(GZ_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-    return GZ_OK;
-}
-
 extern "C" size_t gz_plan_workspace_bytes(int32_t n, int32_t num_simulations) {
     return workspace_bytes(n < 1 ? 1 : n, num_simulations);
 }
 
 // gz_plan_search with optional leaf tags (d_leaf_meta, [leaf_cap]: gz_selfplay_plan_run)
-extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n,
-                                       const gz_search_params* p, const gz_planner_params* pp,
-                                       const float* d_gn_weights, void* d_workspace, void* d_trees, int32_t* d_moves,
-                                       gz_search_stats* d_stats, uint32_t* d_leaves, int32_t leaf_cap,
-                                       int32_t* d_leaf_count, int32_t* d_leaf_meta, void* stream) {
-    if (!p || !pp) return plan_fail(GZ_ERR_ARG, "gz_plan_search: params are NULL");
+int gz_internal_plan_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n,
+                            const gz_search_params* p, const gz_planner_params* pp, const float* d_gn_weights,
+                            void* d_workspace, void* d_trees, int32_t* d_moves, gz_search_stats* d_stats,
+                            uint32_t* d_leaves, int32_t leaf_cap, int32_t* d_leaf_count, int32_t* d_leaf_meta,
+                            void* stream) {
+    if (!p || !pp) return gz_fail(GZ_ERR_ARG, "gz_plan_search: params are NULL");
     if (p->num_simulations < 1 || p->num_simulations > GZ_MAX_SIMULATIONS)
-        return plan_fail(GZ_ERR_ARG, "gz_plan_search: num_simulations out of range [1, 4095]");
+        return gz_fail(GZ_ERR_ARG, "gz_plan_search: num_simulations out of range [1, 4095]");
     if (p->planner_steps < 0 || p->planner_steps > 100 || pp->k < 1 || pp->k > 16)
-        return plan_fail(GZ_ERR_ARG, "gz_plan_search: planner_steps must be in [0, 100] and k in [1, 16]");
+        return gz_fail(GZ_ERR_ARG, "gz_plan_search: planner_steps must be in [0, 100] and k in [1, 16]");
     if (n < 0 || (n > 0 && (!d_boards || !d_game_ids || !d_moves || !d_workspace || !d_gn_weights)))
-        return plan_fail(GZ_ERR_ARG, "gz_plan_search: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_plan_search: bad arguments");
     const bool gather = (p->flags & GZ_FLAG_GATHER_LEAVES) != 0;
     if (gather && (!d_leaves || !d_leaf_count || leaf_cap < 0))
-        return plan_fail(GZ_ERR_ARG, "gz_plan_search: leaf gathering needs d_leaves and d_leaf_count");
+        return gz_fail(GZ_ERR_ARG, "gz_plan_search: leaf gathering needs d_leaves and d_leaf_count");
     if (n == 0) return GZ_OK;
-    if (gz_gn_workspace_bytes(1) != GN_WS_BYTES)
-        return plan_fail(GZ_ERR_INTERNAL, "gz_plan_search: planner-net record size mismatch");
     hipStream_t s = (hipStream_t)stream;
     const int S = p->num_simulations;
     Workspace w = carve(d_workspace, n, S);
@@ -1240,14 +1214,14 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
     const bool check = inc && (p->flags & GZ_FLAG_GN_CHECK) != 0;
     int rc;
     if (hipMemsetAsync(w.ctr, 0, 2 * sizeof(Counters), s) != hipSuccess)
-        return plan_fail(GZ_ERR_HIP, "gz_plan_search: memset");
+        return gz_fail(GZ_ERR_HIP, "gz_plan_search: memset");
     if (hipMemsetAsync(w.jobs, 0, sizeof(PlanJob) * (size_t)n_jobs, s) != hipSuccess)
-        return plan_fail(GZ_ERR_HIP, "gz_plan_search: memset");
+        return gz_fail(GZ_ERR_HIP, "gz_plan_search: memset");
     plan_begin_kernel<<<n, WAVE, 0, s>>>(d_boards, d_game_ids, n, *p, w, sink, gather ? 1 : 0);
-    if ((rc = plan_check("plan_begin_kernel"))) return rc;
+    if ((rc = gz_check_launch("plan_begin_kernel"))) return rc;
     if (inc) {  // the roots' maps and policy-conv outputs -> root slots 0..n-1
         boards_to_rows_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_boards, n, w.gn_in);
-        if ((rc = plan_check("boards_to_rows_kernel"))) return rc;
+        if ((rc = gz_check_launch("boards_to_rows_kernel"))) return rc;
         if ((rc = gz_internal_gn_roots(d_gn_weights, w.gn_in, n, w.slots, w.gn_rec, stream))) return rc;
     }
     // one planner step over jobs [j0, j1): collect -> GraphNet + DQN -> planner move
@@ -1264,12 +1238,12 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
         step_no++;
         // rows, nfull, ninc, ihead (pending is left alone: the resume's own memset clears it)
         if (!zeroed && hipMemsetAsync(&wk.ctr->rows, 0, 4 * sizeof(int32_t), s) != hipSuccess)
-            return plan_fail(GZ_ERR_HIP, "memset");
+            return gz_fail(GZ_ERR_HIP, "memset");
         // jobs j0 .. j1-1 (round 0's chunk), or (slot_game) the one job per game at g * S
         const int cnt = slot_game ? n : j1 - j0, stride = slot_game ? S : 1;
         plan_collect_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(wk, S, n, j0, cnt, stride, p->planner_steps, 0,
                                                                inc ? 1 : 0, slot_game);
-        if ((r = plan_check("plan_collect_kernel"))) return r;
+        if ((r = gz_check_launch("plan_collect_kernel"))) return r;
         if (!inc) {
             if ((r = gz_gn_forward(d_gn_weights, w.gn_in, max_rows, &wk.ctr->rows, w.gn_p, w.gn_q, nullptr, w.gn_rec,
                                    stream)))
@@ -1277,7 +1251,7 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
         } else {
             if ((r = gz_internal_gn_forward_tagged(d_gn_weights, w.gn_in, max_rows, &wk.ctr->rows, w.full_list,
                                                    &wk.ctr->nfull, w.inc_list, &wk.ctr->ninc, w.tags, w.slots, w.gn_p,
-                                                   w.gn_q, w.gn_rec, w.gn_rec + (size_t)max_rows * 928, &wk.ctr->ihead,
+                                                   w.gn_q, w.gn_rec, w.gn_rec + (size_t)max_rows * gzgn::REC, &wk.ctr->ihead,
                                                    stream)))
                 return r;
             if (check) {
@@ -1285,7 +1259,7 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
                                        w.chk_rec, stream)))
                     return r;
                 plan_gn_check_kernel<<<max_rows, 256, 0, s>>>(wk);
-                if ((r = plan_check("plan_gn_check_kernel"))) return r;
+                if ((r = gz_check_launch("plan_gn_check_kernel"))) return r;
             }
         }
         // PW waves per row when the launch leaves CUs idle (GZ_PLAN_STEP4: that row cap, A/B)
@@ -1301,7 +1275,7 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
             plan_step_kernel<<<max_rows, WAVE, 0, s>>>(wk, *pp, 0);
             zeroed = false;
         }
-        return plan_check("plan_step_kernel");
+        return gz_check_launch("plan_step_kernel");
     };
     // The pending count is read (one host synchronisation) every `every` rounds only: a
     // round after the last is a no-op (no job is collected, rolled out or resumed when no
@@ -1316,10 +1290,10 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
             int32_t pending = 0;
             if (hipMemcpyAsync(&pending, &w.ctr->pending, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess)
-                return plan_fail(GZ_ERR_HIP, "gz_plan_search: reading the pending count");
+                return gz_fail(GZ_ERR_HIP, "gz_plan_search: reading the pending count");
             if (pending == 0) break;
         }
-        if (round > S + 1 + every) return plan_fail(GZ_ERR_INTERNAL, "gz_plan_search: search did not terminate");
+        if (round > S + 1 + every) return gz_fail(GZ_ERR_INTERNAL, "gz_plan_search: search did not terminate");
         if (round == 0) {  // every job of the parallel phase, C at a time
             for (int j0 = 0; j0 < n_jobs; j0 += C) {
                 const int j1 = j0 + C < n_jobs ? j0 + C : n_jobs;
@@ -1333,15 +1307,15 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
         // after round 0 the only jobs are the sequential simulations' (job g * S)
         const int cnt = round == 0 ? n_jobs : n, stride = round == 0 ? 1 : S;
         plan_collect_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(w, S, n, 0, cnt, stride, p->planner_steps, 1, 0, 0);
-        if ((rc = plan_check("plan_collect_kernel"))) return rc;
+        if ((rc = gz_check_launch("plan_collect_kernel"))) return rc;
         plan_rollout_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(w, cnt, stride, p->max_depth);
-        if ((rc = plan_check("plan_rollout_kernel"))) return rc;
-        if (hipMemsetAsync(&w.ctr->pending, 0, 4, s) != hipSuccess) return plan_fail(GZ_ERR_HIP, "memset");
+        if ((rc = gz_check_launch("plan_rollout_kernel"))) return rc;
+        if (hipMemsetAsync(&w.ctr->pending, 0, 4, s) != hipSuccess) return gz_fail(GZ_ERR_HIP, "memset");
         plan_resume_kernel<<<n, WAVE, 0, s>>>(n, *p, w, sink, gather ? 1 : 0, d_moves, d_stats);
-        if ((rc = plan_check("plan_resume_kernel"))) return rc;
+        if ((rc = gz_check_launch("plan_resume_kernel"))) return rc;
     }
     plan_finish_kernel<<<n, WAVE, 0, s>>>(n, S, w, d_moves, d_stats, (char*)d_trees);
-    return plan_check("plan_finish_kernel");
+    return gz_check_launch("plan_finish_kernel");
 }
 
 // out[4] (host int64) = rows that ran the full forward / the incremental forward /
@@ -1349,21 +1323,21 @@ extern "C" int gz_internal_plan_search(const gz_board_state* d_boards, const int
 // searches since the last reset
 extern "C" int gz_plan_gn_stats(void* d_workspace, int32_t n, int32_t num_simulations, int64_t* out, int32_t reset,
                                 void* stream) {
-    if (!d_workspace || n < 1 || num_simulations < 1) return plan_fail(GZ_ERR_ARG, "gz_plan_gn_stats: bad arguments");
+    if (!d_workspace || n < 1 || num_simulations < 1) return gz_fail(GZ_ERR_ARG, "gz_plan_gn_stats: bad arguments");
     Workspace w = carve(d_workspace, n, num_simulations);
     hipStream_t s = (hipStream_t)stream;
     GnStats h;
     if (out) {
         if (hipMemcpyAsync(&h, w.stats, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
-            return plan_fail(GZ_ERR_HIP, "gz_plan_gn_stats: copy");
+            return gz_fail(GZ_ERR_HIP, "gz_plan_gn_stats: copy");
         out[0] = h.full;
         out[1] = h.inc;
         out[2] = h.checked;
         out[3] = h.mismatch;
     }
     if (reset && hipMemsetAsync(w.stats, 0, sizeof(GnStats), s) != hipSuccess)
-        return plan_fail(GZ_ERR_HIP, "gz_plan_gn_stats: reset");
+        return gz_fail(GZ_ERR_HIP, "gz_plan_gn_stats: reset");
     return GZ_OK;
 }
 
@@ -1380,8 +1354,8 @@ extern "C" int gz_planner_move(const gz_board_state* d_boards, const int32_t* d_
                                int32_t* d_moves, uint32_t* d_draws, void* stream) {
     if (!pp || n < 0 || (n > 0 && (!d_boards || !d_ai || !d_keys || !d_gn_weights || !d_workspace || !d_moves ||
                                    !d_draws)))
-        return plan_fail(GZ_ERR_ARG, "gz_planner_move: bad arguments");
-    if (pp->k < 1 || pp->k > 16) return plan_fail(GZ_ERR_ARG, "gz_planner_move: k must be in [1, 16]");
+        return gz_fail(GZ_ERR_ARG, "gz_planner_move: bad arguments");
+    if (pp->k < 1 || pp->k > 16) return gz_fail(GZ_ERR_ARG, "gz_planner_move: k must be in [1, 16]");
     if (n == 0) return GZ_OK;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
@@ -1391,10 +1365,10 @@ extern "C" int gz_planner_move(const gz_board_state* d_boards, const int32_t* d_
     float* rec = (float*)((char*)base + align256((size_t)n * 64) + align256((size_t)n * 225 * 4 * 2));
     boards_to_rows_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_boards, n, rows);
     int rc;
-    if ((rc = plan_check("boards_to_rows_kernel"))) return rc;
+    if ((rc = gz_check_launch("boards_to_rows_kernel"))) return rc;
     if ((rc = gz_gn_forward(d_gn_weights, rows, n, nullptr, gp, gq, nullptr, rec, stream))) return rc;
     planner_move_kernel<<<n, WAVE, 0, s>>>(d_boards, d_ai, d_keys, n, *pp, gp, gq, d_moves, d_draws);
-    return plan_check("planner_move_kernel");
+    return gz_check_launch("planner_move_kernel");
 }
 
 extern "C" size_t gz_planner_move_workspace_bytes(int32_t n) {
@@ -1405,8 +1379,8 @@ extern "C" size_t gz_planner_move_workspace_bytes(int32_t n) {
 extern "C" int gz_knowledge_scores(const gz_board_state* d_boards, const int32_t* d_player, int32_t n,
                                    double* d_scores, void* stream) {
     if (n < 0 || (n > 0 && (!d_boards || !d_player || !d_scores)))
-        return plan_fail(GZ_ERR_ARG, "gz_knowledge_scores: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_knowledge_scores: bad arguments");
     if (n == 0) return GZ_OK;
     knowledge_scores_kernel<<<n, WAVE, 0, (hipStream_t)stream>>>(d_boards, d_player, n, d_scores);
-    return plan_check("knowledge_scores_kernel");
+    return gz_check_launch("knowledge_scores_kernel");
 }

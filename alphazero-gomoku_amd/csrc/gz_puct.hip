@@ -62,29 +62,12 @@
 #include <climits>
 #include <string>
 
+#include "gz_internal.h"
 #include "gz_search.h"
 
 using namespace gz;
 
-extern "C" void gz_internal_set_error(const char* msg);
-// selfplay_commit_kernel (gz_selfplay.hip) with the optional visit buffers
-extern "C" int gz_internal_selfplay_commit(void* d_slots, int32_t n_slots, const int32_t* d_moves,
-                                           const gz_search_stats* d_stats, gz_record* d_records, int32_t record_cap,
-                                           gz_selfplay_counters* d_counters, const uint16_t* d_pend_visits,
-                                           uint16_t* d_out_visits, void* stream);
-
 namespace {
-
-int fail(int code, const std::string& msg) {
-    gz_internal_set_error(msg.c_str());
-    return code;
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GZ_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return GZ_OK;
-}
 
 __host__ __device__ constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -498,15 +481,15 @@ RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) {
 
 int check_S(const char* who, int32_t n, int32_t S) {
     if (S < 1 || S > GZ_MAX_SIMULATIONS)
-        return fail(GZ_ERR_ARG, std::string(who) + ": num_simulations out of range [1, 4095]");
-    if (n < 0) return fail(GZ_ERR_ARG, std::string(who) + ": n < 0");
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": num_simulations out of range [1, 4095]");
+    if (n < 0) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n < 0");
     return GZ_OK;
 }
 
 int finish_impl(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
                 gz_search_stats* d_stats, void* stream) {
     puct_finish_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q, d_stats);
-    return check_launch("puct_finish_kernel");
+    return gz_check_launch("puct_finish_kernel");
 }
 
 int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
@@ -531,11 +514,11 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
 }
 
 int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
-    if (!p) return fail(GZ_ERR_ARG, std::string(who) + ": params is NULL");
+    if (!p) return gz_fail(GZ_ERR_ARG, std::string(who) + ": params is NULL");
     int rc = check_S(who, n, p->num_simulations);
     if (rc) return rc;
     if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3)
-        return fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
     return GZ_OK;
 }
 
@@ -589,41 +572,41 @@ size_t gz_puct_workspace_bytes(int32_t n, int32_t S) {
 
 int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
                   void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream) {
-    if (!p) return fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
+    if (!p) return gz_fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
     int rc = check_S("gz_puct_begin", n, p->num_simulations);
     if (rc) return rc;
     if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
-        return fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
     if (n == 0) return GZ_OK;
     puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, (char*)d_workspace, d_leaves,
                                                          d_active);
-    return check_launch("puct_begin_kernel");
+    return gz_check_launch("puct_begin_kernel");
 }
 
 int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, int32_t* d_active, void* stream) {
     int rc = check_S("gz_puct_select", n, S);
     if (rc) return rc;
-    if (n > 0 && (!d_workspace || !d_leaves || !d_active)) return fail(GZ_ERR_ARG, "gz_puct_select: bad arguments");
+    if (n > 0 && (!d_workspace || !d_leaves || !d_active)) return gz_fail(GZ_ERR_ARG, "gz_puct_select: bad arguments");
     if (n == 0) return GZ_OK;
     puct_select_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
-    return check_launch("puct_select_kernel");
+    return gz_check_launch("puct_select_kernel");
 }
 
 int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prior, const float* d_value,
                    void* stream) {
     int rc = check_S("gz_puct_backup", n, S);
     if (rc) return rc;
-    if (n > 0 && (!d_workspace || !d_prior || !d_value)) return fail(GZ_ERR_ARG, "gz_puct_backup: bad arguments");
+    if (n > 0 && (!d_workspace || !d_prior || !d_value)) return gz_fail(GZ_ERR_ARG, "gz_puct_backup: bad arguments");
     if (n == 0) return GZ_OK;
     puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_prior, d_value);
-    return check_launch("puct_backup_kernel");
+    return gz_check_launch("puct_backup_kernel");
 }
 
 int gz_puct_finish(void* d_workspace, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
                    void* stream) {
     int rc = check_S("gz_puct_finish", n, S);
     if (rc) return rc;
-    if (n > 0 && (!d_workspace || !d_moves)) return fail(GZ_ERR_ARG, "gz_puct_finish: bad arguments");
+    if (n > 0 && (!d_workspace || !d_moves)) return gz_fail(GZ_ERR_ARG, "gz_puct_finish: bad arguments");
     if (n == 0) return GZ_OK;
     return finish_impl(d_workspace, n, S, d_moves, d_visits, d_root_q, nullptr, stream);
 }
@@ -634,7 +617,7 @@ int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, in
     int rc = check_search_args("gz_puct_search", p, n);
     if (rc) return rc;
     if (n > 0 && (!d_boards || !d_game_ids || !d_pv_weights || !d_workspace || !d_moves))
-        return fail(GZ_ERR_ARG, "gz_puct_search: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_puct_search: bad arguments");
     if (n == 0) return GZ_OK;
     return search_impl(d_boards, d_game_ids, n, p, d_pv_weights, d_workspace, d_moves, d_visits, d_root_q, nullptr,
                        stream);
@@ -643,10 +626,10 @@ int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, in
 int gz_puct_trees(const void* d_workspace, int32_t n, int32_t S, void* d_out, void* stream) {
     int rc = check_S("gz_puct_trees", n, S);
     if (rc) return rc;
-    if (n > 0 && (!d_workspace || !d_out)) return fail(GZ_ERR_ARG, "gz_puct_trees: bad arguments");
+    if (n > 0 && (!d_workspace || !d_out)) return gz_fail(GZ_ERR_ARG, "gz_puct_trees: bad arguments");
     if (n == 0) return GZ_OK;
     puct_export_kernel<<<n, 256, 0, as_stream(stream)>>>((const char*)d_workspace, n, S, (char*)d_out);
-    return check_launch("puct_export_kernel");
+    return gz_check_launch("puct_export_kernel");
 }
 
 size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t S) {
@@ -663,7 +646,7 @@ int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p
     if (rc) return rc;
     if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
         !d_pv_weights || !d_visits)
-        return fail(GZ_ERR_ARG, "gz_selfplay_puct_run: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_run: bad arguments");
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
     hipStream_t st = as_stream(stream);
     for (int it = 0; it < n_plies; it++) {
@@ -673,7 +656,7 @@ int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p
                          stream);
         if (rc) return rc;
         puct_stash_kernel<<<n_slots, WAVE, 0, st>>>(w.boards, w.moves, w.visits, n_slots, w.pend);
-        rc = check_launch("puct_stash_kernel");
+        rc = gz_check_launch("puct_stash_kernel");
         if (rc) return rc;
         rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
                                          d_visits, stream);

@@ -36,15 +36,13 @@
 // passes that read them -- except where the next pass is the next layer of the same
 // first nodes (y1 -> x1 of nodes 0-2, y2 -> x2 of node 2k): those squares go from the
 // epilogue straight into the next pass's LDS image.  A node with grandchildren also
-// writes its CHILD values into its patch slot for pv_sib_kernel<true> (gz_pvinc.hip).
+// writes its CHILD values into its patch slot for pv_sib_kernel (gz_pvinc.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
-#include <string>
 
-#include "gz_f16conv.h"
-#include "gz_pvnet.h"
-#include "../../include/gzero.h"
+#include "gz_internal.h"
+#include "gz_pvtree.h"
 
 using namespace gzpv;
 
@@ -52,16 +50,10 @@ namespace {
 
 using namespace gzc;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
-__device__ uint4 gz_dg_zero16[1];  // zero source of the LDS-DMA fills
-
 constexpr int NTD = 256;  // 4 waves
 #ifndef GZ_DG_NTE
 #define GZ_DG_NTE 1
 #endif
-constexpr int PATCH_HALVES = PV_PATCH_HALVES;
-constexpr int PATCH_OFF[4] = {0, 9 * 256, 34 * 256, 83 * 256};  // x0 r1, y1 r2, x1 r3, y2 r4 (halves)
 __host__ __device__ constexpr int dg_s(int L) { return 2 * L + 3; }  // D-square width (radius L+1)
 __host__ __device__ constexpr int dg_ss(int L) { return dg_s(L) * dg_s(L); }
 __host__ __device__ constexpr int dg_so(int L) { return 2 * L + 5; }  // output-square width (radius L+2)
@@ -156,30 +148,15 @@ struct DgArgs {
     int32_t* queue;  // [8] per-XCD chunk heads, zero at the launch
 };
 
-__device__ inline int iabs(int x) { return x < 0 ? -x : x; }
-
-// Phase stamps (tools/pvinc_bench.py only): -DGZ_PVDG_STAMPS accumulates s_memtime
-// deltas of workgroup 0 / thread 0 per phase (vector atomics); compiled out otherwise.
-// Phases: 0 chunk start (units, conv0, rows of y1), 1 rows of the next pass, 2..5 the
+// Phase stamps (-DGZ_PVDG_STAMPS builds, tools/pvinc_bench.py).  Phases: 0 chunk start (units, conv0, rows of y1), 1 rows of the next pass, 2..5 the
 // k-loops of y1 / x1 / y2 / x2, 6 the barrier after a k-loop, 7..10 the epilogues,
 // 11 store drain + barrier, 12 records, 13 fill + barrier
 #ifdef GZ_PVDG_STAMPS
 __device__ unsigned long long gz_pvdg_stamps[16];
 __device__ unsigned long long gz_pvdg_stamps_n[1];
-struct DgStamp {
-    unsigned long long t = __builtin_amdgcn_s_memtime();
-    __device__ void operator()(int i) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-            atomicAdd(&gz_pvdg_stamps[i], t_ - t);
-            t = t_;
-        }
-    }
-};
+using DgStamp = PhaseStamp<gz_pvdg_stamps>;
 #else
-struct DgStamp {
-    __device__ void operator()(int) {}
-};
+using DgStamp = PhaseStamp<nullptr>;
 #endif
 
 // global-memory accesses through the unit table's pointers as global (not flat)
@@ -629,7 +606,7 @@ __device__ __forceinline__ void dg_fill(char* lds, const DgUnit* U, int g, int t
 #pragma unroll
     for (int blk = 0; blk < NB; blk++) {
         const int idx = blk * 64 + lane;
-        const _Float16* src = (const _Float16*)gz_dg_zero16;
+        const _Float16* src = (const _Float16*)gz_tree_zero16;
         int stride = 0;
         if (idx < g * SS) {
             const int gi = idx / SS, j = idx - gi * SS;
@@ -1015,16 +992,12 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
 
 }  // namespace
 
-extern "C" void gz_internal_set_error(const char* msg);
-
-// the root children (list, list_count entries) of gz_pv_forward_tree
-// through pv_dg_kernel; scratch: 12 patch-sized areas per CU (grid = CUs)
-extern "C" int gz_internal_tree_delta(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta,
-                                      const int32_t* d_pslot, const int32_t* d_cinfo, const _Float16* d_maps,
-                                      const float* d_pres, _Float16* d_patches, float* d_hbuf, _Float16* d_scratch,
-                                      int32_t* d_tiles, int32_t* d_queue, const int32_t* d_children,
-                                      const int32_t* d_nchildren, int grid, void* stream) {
-    DgArgs A{d_cinfo, d_weights, d_boards, d_meta, d_pslot, d_maps, d_pres, d_patches, d_hbuf, d_tiles, d_queue};
+// the root children (t.children, t.ctr[CTR_CHILDREN] entries) of gz_pv_forward_tree
+// through pv_dg_kernel; t.scratch: PV_SCRATCH_PATCHES patch-sized areas per CU (grid = CUs)
+int gz_internal_tree_delta(const TreeWs& t, const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta,
+                           int grid, void* stream) {
+    DgArgs A{t.cinfo, d_weights, d_boards, d_meta, t.pslot, t.maps, t.pres, t.patches, t.hbuf,
+             t.ctr + CTR_TILES, t.ctr + CTR_DG_QUEUE};
     // K::WPS workgroups per grid entry (CU), K::C patch-sized scratch areas each
     static_assert(K::WPS * SCR_HALVES <= PV_SCRATCH_PATCHES * PATCH_HALVES, "scratch");
 #ifdef GZ_PVDG_STAMPS
@@ -1035,19 +1008,14 @@ extern "C" int gz_internal_tree_delta(const float* d_weights, const uint32_t* d_
 #endif
 #ifdef GZ_DG_CHK
     {
-        const char* lo = (const char*)d_hbuf;
-        const char* hi = (const char*)(d_scratch + (size_t)grid * PV_SCRATCH_PATCHES * PATCH_HALVES);
+        const char* lo = (const char*)t.hbuf;
+        const char* hi = (const char*)(t.scratch + (size_t)grid * PV_SCRATCH_PATCHES * PATCH_HALVES);
         hipMemcpyToSymbolAsync(HIP_SYMBOL(gz_dg_lo), &lo, sizeof(lo), 0, hipMemcpyHostToDevice, (hipStream_t)stream);
         hipMemcpyToSymbolAsync(HIP_SYMBOL(gz_dg_hi), &hi, sizeof(hi), 0, hipMemcpyHostToDevice, (hipStream_t)stream);
     }
 #endif
-    pv_dg_kernel<<<grid * wps, NTD, 0, (hipStream_t)stream>>>(A, d_scratch, d_children, d_nchildren);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("tree delta: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    pv_dg_kernel<<<grid * wps, NTD, 0, (hipStream_t)stream>>>(A, t.scratch, t.children, t.ctr + CTR_CHILDREN);
+    return gz_check_launch("tree delta");
 }
 
 #ifdef GZ_PVDG_STAMPS

@@ -21,14 +21,9 @@
 // partial sums per wave).  Given the parent's patch they are the full forward's
 // values; the patch itself carries the delta's rounding (tests/test_gpu_pvinc.py).
 #include <hip/hip_runtime.h>
-#include <type_traits>
 
-#include <cstdlib>
-#include <string>
-
-#include "gz_f16conv.h"
-#include "gz_pvnet.h"
-#include "../../include/gzero.h"
+#include "gz_internal.h"
+#include "gz_pvtree.h"
 
 using namespace gzpv;
 
@@ -36,11 +31,13 @@ namespace {
 
 using namespace gzc;
 
-// Phase stamps (tools/pvinc_bench.py only): -DGZ_PVINC_STAMPS accumulates s_memtime
-// deltas of workgroup 0 / thread 0 per phase (vector atomics); compiled out otherwise.
+// phase stamps of pv_sib_kernel (-DGZ_PVINC_STAMPS builds, tools/pvinc_bench.py)
 #ifdef GZ_PVINC_STAMPS
 __device__ unsigned long long gz_pvinc_stamps[32];  // [0, 16): pv_sib_kernel
 __device__ unsigned long long gz_pvinc_stamps_n[2];
+using SibStamp = PhaseStamp<gz_pvinc_stamps>;
+#else
+using SibStamp = PhaseStamp<nullptr>;
 #endif
 constexpr int P_X0 = 49, P_Y1 = 81, P_X1 = 121, P_Y2 = 169;  // window positions, radius 3..6
 constexpr int wbytes(int P) { return 2 * 16 * P * 16; }       // hi + lo planes
@@ -57,22 +54,6 @@ struct Win {
     __device__ static constexpr int plane() { return 16 * P * 8; }
     __device__ static constexpr int off(int ch0, int loc) { return ((ch0 >> 3) * P + loc) * 8 + (ch0 & 7); }
 };
-
-// the recomputed rows of one layer: the square of radius rl around (cr, cc),
-// clipped, row-major
-struct Rows {
-    int r0, c0, wr, n;
-};
-__device__ inline Rows make_rows(int cr, int cc, int rl) {
-    Rows q;
-    q.r0 = cr - rl < 0 ? 0 : cr - rl;
-    const int r1 = cr + rl > BN - 1 ? BN - 1 : cr + rl;
-    q.c0 = cc - rl < 0 ? 0 : cc - rl;
-    const int c1 = cc + rl > BN - 1 ? BN - 1 : cc + rl;
-    q.wr = c1 - q.c0 + 1;
-    q.n = (r1 - q.r0 + 1) * q.wr;
-    return q;
-}
 
 template <int NMAX>
 struct TilePos {
@@ -104,11 +85,6 @@ __device__ __forceinline__ void tile_centres(const TilePos<NMAX>& tp, int cr, in
 
 __device__ inline int bit_of_board(int r, int c) { return r * 16 + c; }
 
-// A parent's patch for its grandchildren: the recomputed squares of its maps
-// (x0 r1, y1 r2, x1 r3, y2 r4), [plane][16 cg][(2r+1)^2][8] each, in that order
-constexpr int PATCH_OFF[4] = {0, 9 * 256, 34 * 256, 83 * 256};  // halves
-constexpr int PATCH_HALVES = PV_PATCH_HALVES;
-
 
 struct TreeArgs {
     const int32_t* cinfo;  // per leaf (tree_lists_kernel): -1, or (GC << 30) | (root map slot << 8) | stone cell
@@ -125,20 +101,19 @@ struct TreeArgs {
 };
 
 // ============================================================ sibling-batched incremental forward
-// pv_sib_kernel: the same node computation as tree_node, scheduled so that one pass
-// over a layer's weights serves several nodes.  tree_node streams each layer's 576 KB
-// of hi/lo weight fragments from L2 once per node (twice on the pair layers) for 25-121
-// output rows, which made pv_child_kernel bound by the L2 -> CU rate (3.86 MB per node,
-// MFMA busy 0.44).  Here a workgroup takes a chunk of up to SIB_G consecutive nodes (a
-// root's children are adjacent leaves, so a chunk usually shares one root) and runs the
-// tower layer-major over the chunk:
+// pv_sib_kernel: each node's recomputed squares, scheduled so that one pass over a
+// layer's weights serves several nodes.  A layer's hi/lo weight fragments are 576 KB
+// for only 25-121 output rows per node, so a node at a time is bound by the L2 -> CU
+// rate (3.86 MB per node, MFMA busy 0.44).  Instead a workgroup takes a chunk of up to
+// SIB_G consecutive list entries (a parent's grandchildren are adjacent in the list, so
+// a chunk usually shares one root) and runs the tower layer-major over the chunk:
 //   y1: one pass over all 6 nodes (6 X0 r3 windows in LDS, up to 150 rows)
 //   x1: two passes of 3 (Y1 r4 windows), y2: three passes of 2 (X1 r5), x2 + heads: 1 (Y2 r6)
 // The rows of a pass are the nodes' recomputed squares packed back to back in 16-row
 // M tiles (no per-node tile padding).  Each node's recomputed squares (x0 r1, y1 r2, x1
-// r3, y2 r4: the patch layout) go to global memory between layers -- into its patch
-// slot if it has grandchildren, else into the workgroup's scratch -- and the next
-// layer's windows are filled from the root's maps overlaid with them.  Four waves, one
+// r3, y2 r4: the patch layout) go to the workgroup's scratch in global memory between
+// layers, and the next layer's windows are filled from the root's maps overlaid with the
+// parent's patch and with them.  Four waves, one
 // per SIMD: wave np owns n-tiles {2np, 2np+1} over ALL M tiles of the pass, so each
 // weight fragment is read once per pass and each activation fragment feeds 6 MFMAs.
 // Weight bytes per node: 576 KB x (1/6 + 1/3 + 1/2 + 1) = 1.15 MB (was 3.7 MB).
@@ -146,7 +121,11 @@ struct TreeArgs {
 // (the full kernel's k-loop and epilogues), so results stay bitwise those of the full
 // forward.  (Two waves per SIMD splitting the M tiles, reading each fragment twice,
 // measured 1.5 % slower with the position-major fills.)
-constexpr int NTS = 256, SIB_MH = 1;  // 4 waves; SIB_MH: M halves per n-tile pair
+// SIB_MH (M halves per n-tile pair), sib_tiles and the wave's mh are what is left of a
+// two-waves-per-SIMD schedule (see below).  With SIB_MH = 1 they compute nothing, but the
+// compiler cannot see that mh = wave >> 2 is 0, and pv_sib_kernel's register allocation
+// hangs on it: without them the tree forward measured 0.15 % slower, so they stay.
+constexpr int NTS = 256, SIB_MH = 1;  // 4 waves
 constexpr int sib_tiles(int t) { return t; }
 constexpr int SIB_G = 6;
 static_assert(SIB_G <= PV_SCRATCH_PATCHES, "tree scratch: one workgroup per grid entry");
@@ -158,23 +137,6 @@ constexpr int SIB_POS = SIB_U + SIB_G * 128;  // SibUnit: 128 B; then the chunk'
 constexpr int LDS_S = SIB_POS + 16;
 static_assert(LDS_S <= 160 * 1024, "LDS budget");
 
-// phase stamps of pv_sib_kernel (workgroup 0, thread 0; -DGZ_PVINC_STAMPS builds only)
-template <int BASE = 0>
-struct SibStamp {
-#ifdef GZ_PVINC_STAMPS
-    unsigned long long t = __builtin_amdgcn_s_memtime();
-    __device__ void operator()(int i) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-            atomicAdd(&gz_pvinc_stamps[BASE + i], t_ - t);
-            t = t_;
-        }
-    }
-#else
-    __device__ void operator()(int) {}
-#endif
-};
-
 struct SibUnit {
     const _Float16* gm;   // the root's maps x0, y1, x1, y2
     _Float16* own;        // this node's recomputed squares (patch layout)
@@ -184,8 +146,6 @@ struct SibUnit {
     uint32_t board[16];   // the node's bit-plane board (conv0's input)
 };
 static_assert(sizeof(SibUnit) == 128, "unit size");
-
-__device__ inline int iabs(int x) { return x < 0 ? -x : x; }
 
 // Where map MAP (0..3 = x0, y1, x1, y2) holds on-board position (pr, pc) for unit u:
 // the node's own recomputed square (radius MAP+1 around its stone), a grandchild's
@@ -227,9 +187,6 @@ __device__ __forceinline__ MapLoc map_loc(const SibUnit& u, int pr, int pc) {
 // it.  Unit by unit, with the unit's fields in scalar registers.  The x0 windows (MAP
 // 0) load the root's values at the node's own square too; conv0 overwrites them
 // after the barrier.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
-__device__ uint4 gz_sib_zero16[1];  // zero-initialised
 
 // uniform copy of a unit's fields (SGPRs)
 struct SibU {
@@ -273,7 +230,7 @@ __device__ __forceinline__ void sib_fill(char* lds, const SibUnit* U, int u0, in
         const int pr = u.cr + dr, pc = u.cc + dc;
         const bool on = pr >= 0 && pr < BN && pc >= 0 && pc < BN;
         const bool own = on && iabs(dr) <= rc && iabs(dc) <= rc;
-        const _Float16* src = (const _Float16*)gz_sib_zero16;
+        const _Float16* src = (const _Float16*)gz_tree_zero16;
         int stride = 0;  // halves between channel-group planes at the source
         if (on) {
             src = u.gm + MAP * PV_MAP_HALVES + (pr * BN + pc) * 8;
@@ -425,8 +382,9 @@ __device__ __forceinline__ void sib_conv(const _Float16* act, const int (&ctr)[N
 // but were 2.6 % slower.)
 __device__ __forceinline__ void sq_store(_Float16* p, h4 v) { *(h4*)p = v; }
 
-// conv0's im2col for every unit (16 rows x 32 k fp16 each, the columns tree_node
-// stages), all units in parallel, into col (the head-partials area, dead during y1)
+// conv0's im2col for every unit (16 rows x 32 k fp16 each: the <= 9 positions of the
+// radius-1 square, k = tap * 3 + cin), all units in parallel, into col (the head-partials
+// area, dead during y1)
 template <class UT>
 __device__ __forceinline__ void sib_col(_Float16* col, const UT* U, int ng, int tid) {
     for (int e = tid; e < ng * 512; e += NTS) {
@@ -567,7 +525,7 @@ __device__ __forceinline__ int sib_positions(const SibUnit* U, int ng, int ro, i
 // each node's own square (global)
 template <int LAYER, int NMAX, int G, class Mid>
 __device__ __forceinline__ void sib_map_layer(char* lds, const SibUnit* U, int ng, const float* __restrict__ W, int np,
-                                              int mh, int lane, int32_t* tiles, SibStamp<>& st, int si, Mid&& mid) {
+                                              int mh, int lane, int32_t* tiles, SibStamp& st, int si, Mid&& mid) {
     constexpr int R = LAYER + 3, Wd = 2 * R + 1, P = Wd * Wd, ro = R - 1;
     constexpr int MAPOUT = LAYER + 1, S = 2 * ro + 1, SS = S * S;
     constexpr bool SKIP = LAYER == 1;
@@ -653,12 +611,12 @@ __device__ __forceinline__ void sib_map_layer(char* lds, const SibUnit* U, int n
 }
 
 // x2 + the 1x1 head convs for one unit (Y2 r6 window at LDS 0): wave np = n-tile pair
-// over all the unit's M tiles; the head partial sums in tree_node's per-lane chain
+// over all the unit's M tiles; the head partial sums in the full kernel's per-lane chain
 // (n-tile 2np then 2np+1, channels in order) and cross-lane order, to hpart
 template <class Mid>
 __device__ __forceinline__ void sib_head_layer(char* lds, const SibUnit& u, const float* __restrict__ W, int np,
                                                int mh, int lane, float* __restrict__ hpart, int32_t* tiles,
-                                               SibStamp<>& st, int si, Mid&& mid) {
+                                               SibStamp& st, int si, Mid&& mid) {
     constexpr int layer = 3, NMAX = sib_tiles(8);
     const int cr = u.cell / BN, cc = u.cell - (u.cell / BN) * BN;
     const Rows rows = make_rows(cr, cc, 5);
@@ -810,8 +768,8 @@ __global__ __launch_bounds__(NTS, 1) void pv_sib_kernel(TreeArgs A, _Float16* __
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), np = wave & 3, mh = wave >> 2;
     const float* W = A.W;
-    int32_t* tiles = A.tiles ? A.tiles + 1 : nullptr;
-    SibStamp<> st;
+    int32_t* tiles = A.tiles ? A.tiles + 1 : nullptr;  // (the grandchildren's count)
+    SibStamp st;
     // the units of the chunk at pos_ (wave 0, one lane per node)
     auto build = [&](SibUnit* Ud, int pos_, int ng_) {
         if (wave == 0 && lane < ng_) {  // the chunk's nodes
@@ -958,7 +916,7 @@ __global__ void tree_roots_kernel(const int32_t* __restrict__ meta, int n, const
     if (i >= count) return;
     int o = -1;
     if (meta[i] == -1) {
-        o = atomicAdd(&ctr[0], 1);
+        o = atomicAdd(&ctr[CTR_ROOTS_SEEN], 1);
         if (o >= root_cap) o = -1;
     }
     ord[i] = o;
@@ -993,7 +951,7 @@ __global__ void tree_patch_kernel(const int32_t* __restrict__ meta, int n, const
     const int m = meta[i];
     if (m < 0 || m >= count || !is_child(ord, boards, m, meta[m], count) || !one_cell(boards, i, m)) return;
     if (atomicCAS(&pslot[m], -1, -2) == -1) {
-        const int s = atomicAdd(&ctr[5], 1);
+        const int s = atomicAdd(&ctr[CTR_PATCHES], 1);
         pslot[m] = s < patch_cap ? s : -3;
     }
 }
@@ -1041,8 +999,8 @@ __global__ void tree_lists_kernel(const int32_t* __restrict__ meta, int n, const
     const bool child = valid && is_child(ord, boards, i, m, count);
     const bool gc = valid && !child && m >= 0 && m < count && pslot[m] >= 0 && is_child(ord, boards, m, meta[m], count) &&
                     one_cell(boards, i, m);
-    wave_append(root, i, ctr + 1, roots);
-    wave_append(valid && !root && !child && !gc, i, ctr + 3, full);
+    wave_append(root, i, ctr + CTR_ROOTS, roots);
+    wave_append(valid && !root && !child && !gc, i, ctr + CTR_FULL, full);
     if (gc) gnext[i] = atomicExch(&ghead[pslot[m]], i);  // per parent, any order
     if (valid) {  // the incremental kernels' per-leaf word: root map slot and stone cell
         int ci = -1;
@@ -1054,7 +1012,7 @@ __global__ void tree_lists_kernel(const int32_t* __restrict__ meta, int n, const
     }
     // root children: counted here, listed in leaf order by tree_children_kernel
     const uint64_t c = __ballot(child);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(ctr + 2, __popcll(c));
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(ctr + CTR_CHILDREN, __popcll(c));
     if ((threadIdx.x & 63) == 0 && i < n) wcount[i >> 6] = __popcll(c);  // lane 0: i = 64 w
 }
 
@@ -1124,8 +1082,8 @@ __global__ __launch_bounds__(1024) void tree_children_scatter_kernel(int n, cons
 // appends its grandchildren (its ghead / gnext chain), a wave's parents in lane
 // order.  A root's children are adjacent leaves, so a root's grandchildren end up
 // adjacent in the list (the search reserves them one by one during its sequential
-// phase, interleaved with every other game's), and pv_grandchild_kernel's
-// XCD-contiguous chunks then keep each root's maps in one L2
+// phase, interleaved with every other game's), and pv_sib_kernel's XCD-contiguous
+// eighths of the list then keep each root's maps in one L2
 __global__ void tree_grand_order_kernel(int n, const int32_t* __restrict__ d_count, const int32_t* __restrict__ pslot,
                                         const int32_t* __restrict__ ghead, const int32_t* __restrict__ gnext,
                                         int32_t* __restrict__ ctr, int32_t* __restrict__ grand) {
@@ -1144,7 +1102,7 @@ __global__ void tree_grand_order_kernel(int n, const int32_t* __restrict__ d_cou
     }
     const int total = __shfl(incl, 63);
     int base = 0;
-    if (lane == 63 && total) base = atomicAdd(ctr + 4, total);
+    if (lane == 63 && total) base = atomicAdd(ctr + CTR_GRAND, total);
     base = __shfl(base, 63);
     int at = base + incl - k;
     for (int g = h; g >= 0; g = gnext[g]) grand[at++] = g;
@@ -1152,65 +1110,37 @@ __global__ void tree_grand_order_kernel(int n, const int32_t* __restrict__ d_cou
 
 }  // namespace
 
-extern "C" void gz_internal_set_error(const char* msg);
-extern "C" int gz_internal_tree_delta(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta,
-                                      const int32_t* d_pslot, const int32_t* d_cinfo, const _Float16* d_maps,
-                                      const float* d_pres, _Float16* d_patches, float* d_hbuf, _Float16* d_scratch,
-                                      int32_t* d_tiles, int32_t* d_queue, const int32_t* d_children,
-                                      const int32_t* d_nchildren, int grid, void* stream);
-
 // Launches of the incremental forward's own kernels (called by gz_pv_forward_tree in
 // gz_pvnet.hip, which runs the full kernel on the root and full lists in between).
-extern "C" int gz_internal_tree_classify(const int32_t* d_meta, int32_t n, const int32_t* d_count, int32_t root_cap,
-                                         int32_t patch_cap, int32_t* d_ord, int32_t* d_pslot, int32_t* d_ctr,
-                                         int32_t* d_roots, int32_t* d_full, int32_t* d_grand, int32_t* d_ghead,
-                                         int32_t* d_gnext, const uint32_t* d_boards, int32_t* d_cinfo,
-                                         int32_t* d_children, void* stream) {
+int gz_internal_tree_classify(const TreeWs& t, const uint32_t* d_boards, const int32_t* d_meta, int32_t n,
+                              const int32_t* d_count, int32_t root_cap, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(d_ctr, 0, 32 * sizeof(int32_t), s) != hipSuccess ||  // (ctr[16..32): the queue heads)
-        (patch_cap > 0 && hipMemsetAsync(d_ghead, 0xff, (size_t)patch_cap * sizeof(int32_t), s) != hipSuccess)) {
-        gz_internal_set_error("gz_pv_forward_tree: memset");
-        return GZ_ERR_HIP;
-    }
+    if (hipMemsetAsync(t.ctr, 0, CTR_COUNT * sizeof(int32_t), s) != hipSuccess ||  // (the queue heads too)
+        (t.patch_cap > 0 && hipMemsetAsync(t.ghead, 0xff, (size_t)t.patch_cap * sizeof(int32_t), s) != hipSuccess))
+        return gz_fail(GZ_ERR_HIP, "gz_pv_forward_tree: memset");
     const int g = (n + 255) / 256;
-    tree_roots_kernel<<<g, 256, 0, s>>>(d_meta, n, d_count, root_cap, d_ord, d_pslot, d_ctr);
-    tree_patch_kernel<<<g, 256, 0, s>>>(d_meta, n, d_count, d_ord, d_boards, patch_cap, d_pslot, d_ctr);
-    // per-wave child counts: past the list's n entries (d_children has n + n / 64 + 1)
-    int32_t* wcount = d_children + n;
-    tree_lists_kernel<<<g, 256, 0, s>>>(d_meta, n, d_count, d_ord, d_pslot, d_boards, d_ctr, d_roots, d_full, d_ghead,
-                                        d_gnext, d_cinfo, wcount);
-    tree_children_kernel<<<1, 1024, 0, s>>>(n, d_count, d_cinfo, wcount, d_children);
-    tree_children_scatter_kernel<<<(n + 1023) / 1024, 1024, 0, s>>>(n, d_count, d_cinfo, wcount, d_children);
-    tree_grand_order_kernel<<<g, 256, 0, s>>>(n, d_count, d_pslot, d_ghead, d_gnext, d_ctr, d_grand);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("tree classify: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    tree_roots_kernel<<<g, 256, 0, s>>>(d_meta, n, d_count, root_cap, t.ord, t.pslot, t.ctr);
+    tree_patch_kernel<<<g, 256, 0, s>>>(d_meta, n, d_count, t.ord, d_boards, t.patch_cap, t.pslot, t.ctr);
+    // per-wave child counts: past the list's n entries (t.children has n + n / 64 + 1)
+    int32_t* wcount = t.children + n;
+    tree_lists_kernel<<<g, 256, 0, s>>>(d_meta, n, d_count, t.ord, t.pslot, d_boards, t.ctr, t.roots, t.full, t.ghead,
+                                        t.gnext, t.cinfo, wcount);
+    tree_children_kernel<<<1, 1024, 0, s>>>(n, d_count, t.cinfo, wcount, t.children);
+    tree_children_scatter_kernel<<<(n + 1023) / 1024, 1024, 0, s>>>(n, d_count, t.cinfo, wcount, t.children);
+    tree_grand_order_kernel<<<g, 256, 0, s>>>(n, d_count, t.pslot, t.ghead, t.gnext, t.ctr, t.grand);
+    return gz_check_launch("tree classify");
 }
 
-// the root children through pv_dg_kernel (gz_pvdg.hip; d_pres: the roots' pre-BN
-// accumulators), then the grandchildren through pv_sib_kernel
-extern "C" int gz_internal_tree_children(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta,
-                                         const int32_t* d_ord, const int32_t* d_pslot, int32_t n,
-                                         const int32_t* d_count, const _Float16* d_maps, _Float16* d_patches,
-                                         float* d_hbuf, const int32_t* d_grand, const int32_t* d_ngrand,
-                                         const int32_t* d_cinfo, _Float16* d_scratch, int32_t* d_tiles,
-                                         const int32_t* d_children, const int32_t* d_nchildren, int grid,
-                                         const float* d_pres, int32_t* d_queue, void* stream) {
-    TreeArgs A{d_cinfo, d_weights, d_boards, d_meta, d_ord, d_pslot, d_maps, d_patches, d_hbuf, d_tiles, d_queue + 8};
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = gz_internal_tree_delta(d_weights, d_boards, d_meta, d_pslot, d_cinfo, d_maps, d_pres, d_patches,
-                                          d_hbuf, d_scratch, d_tiles, d_queue, d_children, d_nchildren, grid, stream);
+// the root children through pv_dg_kernel (gz_pvdg.hip), then the grandchildren through
+// pv_sib_kernel
+int gz_internal_tree_children(const TreeWs& t, const float* d_weights, const uint32_t* d_boards,
+                              const int32_t* d_meta, int32_t n, const int32_t* d_count, int grid, void* stream) {
+    const int rc = gz_internal_tree_delta(t, d_weights, d_boards, d_meta, grid, stream);
     if (rc) return rc;
-    pv_sib_kernel<<<grid, NTS, 0, s>>>(A, d_scratch, n, d_count, d_grand, d_ngrand);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("tree children: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    TreeArgs A{t.cinfo, d_weights, d_boards, d_meta, t.ord, t.pslot, t.maps, t.patches, t.hbuf,
+               t.ctr + CTR_TILES, t.ctr + CTR_SIB_QUEUE};
+    pv_sib_kernel<<<grid, NTS, 0, (hipStream_t)stream>>>(A, t.scratch, n, d_count, t.grand, t.ctr + CTR_GRAND);
+    return gz_check_launch("tree children");
 }
 
 #ifdef GZ_PVINC_STAMPS

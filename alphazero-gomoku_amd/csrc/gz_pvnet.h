@@ -10,6 +10,9 @@
 // Head weights: 1x1 convs as [out][128]; FCs stored transposed ([in][out]) so a
 // thread per output reads coalesced rows.
 #pragma once
+#include <cstddef>
+#include <cstdint>
+#include <initializer_list>
 
 namespace gzpv {
 constexpr int CH = 128;
@@ -55,7 +58,7 @@ constexpr int TOTAL = V1_P + V1_KB * V1_NT * 256;
 // [256 rows][8] then the lo plane -- PV_MAP_HALVES halves per map
 constexpr int PV_MAP_PLANE = CH * 256;
 constexpr int PV_MAP_HALVES = 2 * PV_MAP_PLANE;
-// delta tree forward (gz_pvinc.hip, pv_delta_kernel): a root board's pre-ReLU values
+// delta tree forward (gz_pvdg.hip, pv_dg_kernel): a root board's pre-ReLU values
 // of the 4 residual layers (y1, x1, y2, x2: z = BN(conv) [+ skip input]), fp32
 // position-major [256 positions][128 channels] -- PV_PRE_FLOATS floats per layer
 constexpr int PV_PRE_FLOATS = 256 * CH;
@@ -70,7 +73,88 @@ constexpr int PV_SCRATCH_PATCHES = 12;
 // (gz_pvnet.hip / gz_pvinc.hip -> pv_heads_kernel): hp [0, 450) channel-major, zero to
 // HP_K; hv [HV_OFF, HV_OFF + 225), zero to HSTRIDE
 constexpr int HP_K = 464, HV_OFF = HP_K, HV_K = 240, HSTRIDE = HV_OFF + HV_K;
+// the f16x3 heads' fp16 B fragments (gz_pvnet.hip, pv_heads_pack_kernel): policy_fc
+// then value_fc1, [kb][n-tile][lane][8], a hi plane then a lo plane
+constexpr int HF_PKB = 15, HF_VKB = 8;  // k-blocks: policy 480 >= 450 inputs, value 256 >= 225
+constexpr int HF_VAL = HF_PKB * PF_NT * 64 * 8;             // halves: value_fc1's fragments
+constexpr int HF_PLANE = HF_VAL + HF_VKB * V1_NT * 64 * 8;  // halves per plane (hi, lo)
+constexpr size_t HF_BYTES = 2 * (size_t)HF_PLANE * sizeof(_Float16);
 
 // algorithmic work of one forward (neural_network.py:132-159), MACs
 constexpr long long MACS = 133690114LL;
+
+// ---------------------------------------------------------------- tree forward (host)
+// The counter block of a tree forward (TreeWs::ctr, zeroed by gz_internal_tree_classify):
+// list counts, then the 16-row MFMA tile-taps the incremental kernels executed, then the
+// per-XCD chunk queue heads of pv_dg_kernel and pv_sib_kernel
+enum TreeCtr {
+    CTR_ROOTS_SEEN = 0,  // leaves tagged as roots (with or without a map slot)
+    CTR_ROOTS = 1,       // roots with a map slot: full forward, maps stored
+    CTR_CHILDREN = 2,    // root children (pv_dg_kernel)
+    CTR_FULL = 3,        // every other board without a stored root or patch: full forward
+    CTR_GRAND = 4,       // grandchildren (pv_sib_kernel)
+    CTR_PATCHES = 5,     // patch slots claimed
+    CTR_STATS = 6,       // gz_pv_tree_stats copies [0, CTR_STATS)
+    CTR_TILES = 8,       // [2] executed tile-taps: root children, grandchildren
+    CTR_DG_QUEUE = 16,   // [8] pv_dg_kernel's queue heads
+    CTR_SIB_QUEUE = 24,  // [8] pv_sib_kernel's queue heads
+    CTR_COUNT = 32
+};
+static_assert(CTR_STATS <= CTR_TILES && CTR_TILES + 2 <= CTR_DG_QUEUE && CTR_DG_QUEUE + 8 == CTR_SIB_QUEUE &&
+                  CTR_SIB_QUEUE + 8 == CTR_COUNT, "counter slots");
+
+constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+constexpr int32_t patch_cap_of(int32_t root_cap) { return 16 * (root_cap < 0 ? 0 : root_cap); }
+
+// The tree-forward workspace, described once: byte offsets of its regions for n leaves,
+// root_cap root map slots and `grid` scratch entries (one per CU), in order; `end` is
+// gz_pv_tree_workspace_bytes.  tree_carve (gz_pvnet.hip) applies them to the base pointer.
+struct TreeLayout {
+    size_t hbuf;      // [n][HSTRIDE] f32 head-conv records
+    size_t ord, pslot, roots, full, grand, gnext, cinfo;  // [n] i32 each
+    size_t children;  // [n] i32 + the per-wave counts of tree_lists_kernel [n / 64 + 1]
+    size_t ctr;       // [CTR_COUNT] i32
+    size_t ghead;     // [patch_cap] i32
+    size_t maps;      // [root_cap][4][PV_MAP_HALVES] f16
+    size_t pres;      // [root_cap][4][PV_PRE_FLOATS] f32
+    size_t patches;   // [patch_cap][PV_PATCH_HALVES] f16
+    size_t scratch;   // [grid][PV_SCRATCH_PATCHES][PV_PATCH_HALVES] f16
+    size_t hf;        // HF_BYTES
+    size_t end;
+};
+constexpr TreeLayout tree_layout(int32_t n, int32_t root_cap, int grid) {
+    const size_t m = (size_t)(n < 1 ? 1 : n), rc = (size_t)(root_cap < 0 ? 0 : root_cap);
+    const size_t pc = (size_t)patch_cap_of(root_cap);
+    TreeLayout l{};
+    size_t p = 0;
+    const auto take = [&p](size_t bytes) {
+        const size_t at = p;
+        p += bytes;
+        return at;
+    };
+    l.hbuf = take(al256(m * HSTRIDE * sizeof(float)));
+    for (size_t* a : {&l.ord, &l.pslot, &l.roots, &l.full, &l.grand, &l.gnext, &l.cinfo}) *a = take(al256(m * 4));
+    l.children = take(al256((m + m / 64 + 1) * 4));
+    l.ctr = take(al256(CTR_COUNT * sizeof(int32_t)));
+    l.ghead = take(al256(pc * 4));
+    l.maps = take(rc * 4 * PV_MAP_HALVES * sizeof(_Float16));
+    l.pres = take(rc * 4 * PV_PRE_FLOATS * sizeof(float));
+    l.patches = take(pc * PV_PATCH_HALVES * sizeof(_Float16));
+    l.scratch = take((size_t)grid * PV_SCRATCH_PATCHES * PV_PATCH_HALVES * sizeof(_Float16));
+    l.hf = take(HF_BYTES);
+    l.end = p;
+    return l;
+}
+
+// the carved workspace: what gz_internal_tree_classify / _children / _delta work on
+struct TreeWs {
+    float* hbuf;
+    int32_t *ord, *pslot, *roots, *full, *grand, *gnext, *cinfo, *children, *ghead, *ctr;
+    _Float16* maps;
+    float* pres;        // the roots' pre-BN accumulators (pv_dg_kernel)
+    _Float16* patches;
+    _Float16* scratch;  // pv_sib_kernel / pv_dg_kernel: PV_SCRATCH_PATCHES patch-sized areas per grid entry
+    _Float16* hf;       // the heads' fp16 fragments
+    int32_t patch_cap;
+};
 }  // namespace gzpv

@@ -25,8 +25,8 @@
 #include <string>
 
 #include "gz_f16conv.h"
+#include "gz_internal.h"
 #include "gz_pvnet.h"
-#include "../../include/gzero.h"
 
 using namespace gzpv;
 
@@ -705,10 +705,6 @@ static_assert(HP_K == 16 * PF_KB && HV_K == 16 * V1_KB && HP_K % 16 == 0 && HV_K
 // halves out of fp16's subnormals), split into fp16 hi / lo -- are cut from the fp32
 // fragments once per forward (pv_heads_pack_kernel) into the workspace: [kb][n-tile][lane]
 // [8] hi plane, then the lo plane.  The exact-fp32 path keeps the fp32-MFMA heads.
-constexpr int HF_PKB = 15, HF_VKB = 8;  // k-blocks: policy 480 >= 450 inputs, value 256 >= 225
-constexpr int HF_VAL = HF_PKB * PF_NT * 64 * 8;           // halves: value_fc1's fragments
-constexpr int HF_PLANE = HF_VAL + HF_VKB * V1_NT * 64 * 8;  // halves per plane (hi, lo)
-constexpr size_t HF_BYTES = 2 * (size_t)HF_PLANE * sizeof(_Float16);
 constexpr float HF_SCALE = 256.f, HF_UNSCALE = 1.f / 256.f;
 static_assert(HF_PKB * 32 >= HP_K - 8 && HF_VKB * 32 >= HV_K, "k-blocks");
 
@@ -1019,14 +1015,10 @@ extern "C" int gz_pv_stamps_read(unsigned long long* out, int reset) {
 }
 #endif
 
-extern "C" void gz_internal_set_error(const char* msg);
-
 extern "C" size_t gz_pv_weight_floats(void) { return (size_t)TOTAL; }
 
 static int pv_grid(int n) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+    const int cus = gz_cu_count();
     return n < cus ? n : cus;
 }
 
@@ -1052,22 +1044,13 @@ static void pv_heads_launch(const float* d_weights, const float* hbuf, int32_t n
 extern "C" int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, int32_t n, const int32_t* d_count,
                              float* d_logits, float* d_value, float* d_probs, double* d_prior, void* d_workspace,
                              int32_t precision, void* stream) {
-    if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_logits || !d_value))) {
-        gz_internal_set_error("gz_pv_forward: bad arguments");
-        return GZ_ERR_ARG;
-    }
-    if (precision != GZ_PV_FP32 && precision != GZ_PV_F16X3) {
-        gz_internal_set_error("gz_pv_forward: unknown precision");
-        return GZ_ERR_ARG;
-    }
-    if (!d_workspace) {
-        gz_internal_set_error("gz_pv_forward: d_workspace is required");
-        return GZ_ERR_ARG;
-    }
-    if (d_prior && !d_probs) {
-        gz_internal_set_error("gz_pv_forward: d_prior needs d_probs (the prior is renormalised from the softmax)");
-        return GZ_ERR_ARG;
-    }
+    if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_logits || !d_value)))
+        return gz_fail(GZ_ERR_ARG, "gz_pv_forward: bad arguments");
+    if (precision != GZ_PV_FP32 && precision != GZ_PV_F16X3)
+        return gz_fail(GZ_ERR_ARG, "gz_pv_forward: unknown precision");
+    if (!d_workspace) return gz_fail(GZ_ERR_ARG, "gz_pv_forward: d_workspace is required");
+    if (d_prior && !d_probs)
+        return gz_fail(GZ_ERR_ARG, "gz_pv_forward: d_prior needs d_probs (the prior is renormalised from the softmax)");
     if (n == 0) return GZ_OK;
     int grid = pv_grid(n);
     hipStream_t s = (hipStream_t)stream;
@@ -1082,142 +1065,95 @@ extern "C" int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, i
                         (_Float16*)((char*)d_workspace + pv_hf_offset(n)), s);
     }
     if (d_prior) pv_prior_kernel<<<(n + PR_B - 1) / PR_B, 256, 0, s>>>(d_boards, n, d_count, d_probs, d_prior);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("pv_kernel: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    return gz_check_launch("pv_kernel");
 }
 
-// ============================================================ incremental forward (gz_pvinc.hip)
-extern "C" int gz_internal_tree_classify(const int32_t* d_meta, int32_t n, const int32_t* d_count, int32_t root_cap,
-                                         int32_t patch_cap, int32_t* d_ord, int32_t* d_pslot, int32_t* d_ctr,
-                                         int32_t* d_roots, int32_t* d_full, int32_t* d_grand, int32_t* d_ghead,
-                                         int32_t* d_gnext, const uint32_t* d_boards, int32_t* d_cinfo,
-                                         int32_t* d_children, void* stream);
-extern "C" int gz_internal_tree_children(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta,
-                                         const int32_t* d_ord, const int32_t* d_pslot, int32_t n,
-                                         const int32_t* d_count, const _Float16* d_maps, _Float16* d_patches,
-                                         float* d_hbuf, const int32_t* d_grand, const int32_t* d_ngrand,
-                                         const int32_t* d_cinfo, _Float16* d_scratch, int32_t* d_tiles,
-                                         const int32_t* d_children, const int32_t* d_nchildren, int grid,
-                                         const float* d_pres, int32_t* d_queue, void* stream);
+// ============================================================ tree forward (gz_pvinc.hip, gz_pvdg.hip)
+// The layout (gz_pvnet.h tree_layout) is evaluated at compile time here: regions in
+// order, and the totals of two shapes the workspace test pins (256 CUs)
+static_assert(tree_layout(1, 0, 256).hbuf == 0 && tree_layout(1, 0, 256).ord == 2816 &&
+                  tree_layout(1, 0, 256).end == 258481152, "tree workspace of (1, 0)");
+constexpr bool tree_layout_ordered(const TreeLayout& l) {
+    return l.hbuf < l.ord && l.ord < l.pslot && l.pslot < l.roots && l.roots < l.full && l.full < l.grand &&
+           l.grand < l.gnext && l.gnext < l.cinfo && l.cinfo < l.children && l.children < l.ctr && l.ctr < l.ghead &&
+           l.ghead < l.maps && l.maps < l.pres && l.pres < l.patches && l.patches < l.scratch &&
+           l.scratch < l.hf && l.hf + HF_BYTES == l.end;
+}
+static_assert(tree_layout_ordered(tree_layout(1000, 3, 256)) && tree_layout(1000, 3, 256).end == 268501504,
+              "tree workspace of (1000, 3)");
+static_assert(tree_layout_ordered(tree_layout(819200, 4096, 256)) && tree_layout(819200, 4096, 256).end == 12389765632,
+              "tree workspace of the bench's shape");
 
-namespace {
-constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-// per grid entry (gz_pvnet.h): pv_sib_kernel's workgroup x 6 nodes, pv_dg_kernel's 2 x 6
-constexpr size_t SIB_SCRATCH_HALVES = PV_SCRATCH_PATCHES * (size_t)PV_PATCH_HALVES;
-inline int32_t patch_cap_of(int32_t root_cap) { return 16 * (root_cap < 0 ? 0 : root_cap); }
-struct TreeWs {
-    float* hbuf;
-    int32_t *ord, *pslot, *roots, *full, *grand, *gnext, *cinfo, *children, *ghead, *ctr;
-    _Float16* maps;
-    float* pres;        // the roots' pre-BN accumulators (pv_dg_kernel)
-    _Float16* patches;
-    _Float16* scratch;  // pv_sib_kernel / pv_dg_kernel: 12 patch-sized areas per workgroup
-    _Float16* hf;       // the heads' fp16 fragments (HF_BYTES)
-};
-TreeWs tree_carve(void* ws, int32_t n, int32_t root_cap) {
-    const size_t m = (size_t)(n < 1 ? 1 : n);
+// the scratch is sized for every CU, whatever n
+static TreeWs tree_carve(void* ws, int32_t n, int32_t root_cap) {
+    const TreeLayout l = tree_layout(n, root_cap, gz_cu_count());
     char* p = (char*)ws;
     TreeWs t;
-    t.hbuf = (float*)p;
-    p += al256(m * HSTRIDE * sizeof(float));
-    int32_t** arrays[7] = {&t.ord, &t.pslot, &t.roots, &t.full, &t.grand, &t.gnext, &t.cinfo};
-    for (auto a : arrays) {
-        *a = (int32_t*)p;
-        p += al256(m * 4);
-    }
-    t.children = (int32_t*)p;  // n entries + the per-wave counts of tree_children_kernel
-    p += al256((m + m / 64 + 1) * 4);
-    t.ctr = (int32_t*)p;
-    p += 256;
-    t.ghead = (int32_t*)p;
-    p += al256((size_t)patch_cap_of(root_cap) * 4);
-    t.maps = (_Float16*)p;
-    p += (size_t)(root_cap < 0 ? 0 : root_cap) * 4 * PV_MAP_HALVES * sizeof(_Float16);
-    t.pres = (float*)p;
-    p += (size_t)(root_cap < 0 ? 0 : root_cap) * 4 * PV_PRE_FLOATS * sizeof(float);
-    t.patches = (_Float16*)p;
-    p += (size_t)patch_cap_of(root_cap) * PV_PATCH_HALVES * sizeof(_Float16);
-    t.scratch = (_Float16*)p;
-    p += (size_t)pv_grid(1 << 30) * SIB_SCRATCH_HALVES * sizeof(_Float16);
-    t.hf = (_Float16*)p;
+    t.hbuf = (float*)(p + l.hbuf);
+    t.ord = (int32_t*)(p + l.ord);
+    t.pslot = (int32_t*)(p + l.pslot);
+    t.roots = (int32_t*)(p + l.roots);
+    t.full = (int32_t*)(p + l.full);
+    t.grand = (int32_t*)(p + l.grand);
+    t.gnext = (int32_t*)(p + l.gnext);
+    t.cinfo = (int32_t*)(p + l.cinfo);
+    t.children = (int32_t*)(p + l.children);
+    t.ctr = (int32_t*)(p + l.ctr);
+    t.ghead = (int32_t*)(p + l.ghead);
+    t.maps = (_Float16*)(p + l.maps);
+    t.pres = (float*)(p + l.pres);
+    t.patches = (_Float16*)(p + l.patches);
+    t.scratch = (_Float16*)(p + l.scratch);
+    t.hf = (_Float16*)(p + l.hf);
+    t.patch_cap = patch_cap_of(root_cap);
     return t;
 }
-}  // namespace
 
 extern "C" size_t gz_pv_tree_workspace_bytes(int32_t n, int32_t root_cap) {
-    const size_t m = (size_t)(n < 1 ? 1 : n);
-    return al256(m * HSTRIDE * sizeof(float)) + 7 * al256(m * 4) + al256((m + m / 64 + 1) * 4) + 256 +
-           al256((size_t)patch_cap_of(root_cap) * 4) +
-           (size_t)(root_cap < 0 ? 0 : root_cap) * 4 * PV_MAP_HALVES * sizeof(_Float16) +
-           (size_t)(root_cap < 0 ? 0 : root_cap) * 4 * PV_PRE_FLOATS * sizeof(float) +
-           (size_t)patch_cap_of(root_cap) * PV_PATCH_HALVES * sizeof(_Float16) +
-           (size_t)pv_grid(1 << 30) * SIB_SCRATCH_HALVES * sizeof(_Float16) + HF_BYTES;
+    return tree_layout(n, root_cap, gz_cu_count()).end;
 }
 
 extern "C" int gz_pv_forward_tree(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta, int32_t n,
                                   const int32_t* d_count, int32_t root_cap, float* d_logits, float* d_value,
                                   float* d_probs, double* d_prior, void* d_workspace, void* stream) {
-    if (n < 0 || root_cap < 0 || (n > 0 && (!d_weights || !d_boards || !d_meta || !d_logits || !d_value || !d_workspace))) {
-        gz_internal_set_error("gz_pv_forward_tree: bad arguments");
-        return GZ_ERR_ARG;
-    }
-    if (d_prior && !d_probs) {
-        gz_internal_set_error("gz_pv_forward_tree: d_prior needs d_probs");
-        return GZ_ERR_ARG;
-    }
+    if (n < 0 || root_cap < 0 || (n > 0 && (!d_weights || !d_boards || !d_meta || !d_logits || !d_value || !d_workspace)))
+        return gz_fail(GZ_ERR_ARG, "gz_pv_forward_tree: bad arguments");
+    if (d_prior && !d_probs) return gz_fail(GZ_ERR_ARG, "gz_pv_forward_tree: d_prior needs d_probs");
     if (n == 0) return GZ_OK;
     hipStream_t s = (hipStream_t)stream;
-    TreeWs t = tree_carve(d_workspace, n, root_cap);
-    int rc = gz_internal_tree_classify(d_meta, n, d_count, root_cap, patch_cap_of(root_cap), t.ord, t.pslot, t.ctr,
-                                       t.roots, t.full, t.grand, t.ghead, t.gnext, d_boards, t.cinfo, t.children,
-                                       stream);
+    const TreeWs t = tree_carve(d_workspace, n, root_cap);
+    int rc = gz_internal_tree_classify(t, d_boards, d_meta, n, d_count, root_cap, stream);
     if (rc) return rc;
     const int grid = pv_grid(n);
     // roots (full forward, maps stored), then every board without a stored root or
-    // patch (full forward), then the roots' children and their children (incremental);
-    // ctr = [roots seen, #roots, #children, #full, #grandchildren, patch slots claimed, .., .,
-    //        executed tile-taps (children, grandchildren) at 8, 9, pv_dg_kernel's / pv_sib_kernel's XCD queue heads at 16..23 / 24..31]
-    pv_kernel_f16x3<true, true><<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, t.hbuf, t.roots, t.ctr + 1,
-                                                     t.ord, t.maps, root_cap, t.pres);
-    pv_kernel_f16x3<true, false><<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, t.hbuf, t.full, t.ctr + 3,
-                                                      nullptr, nullptr, 0);
-    rc = gz_internal_tree_children(d_weights, d_boards, d_meta, t.ord, t.pslot, n, d_count, t.maps, t.patches, t.hbuf,
-                                   t.grand, t.ctr + 4, t.cinfo, t.scratch, t.ctr + 8, t.children, t.ctr + 2, grid,
-                                   t.pres, t.ctr + 16, stream);
+    // patch (full forward), then the roots' children and their children (incremental)
+    pv_kernel_f16x3<true, true><<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, t.hbuf, t.roots,
+                                                     t.ctr + CTR_ROOTS, t.ord, t.maps, root_cap, t.pres);
+    pv_kernel_f16x3<true, false><<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, t.hbuf, t.full,
+                                                      t.ctr + CTR_FULL, nullptr, nullptr, 0);
+    rc = gz_internal_tree_children(t, d_weights, d_boards, d_meta, n, d_count, grid, stream);
     if (rc) return rc;
     pv_heads_launch(d_weights, t.hbuf, n, d_count, d_logits, d_value, d_probs, t.hf, s);
     if (d_prior) pv_prior_kernel<<<(n + PR_B - 1) / PR_B, 256, 0, s>>>(d_boards, n, d_count, d_probs, d_prior);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("gz_pv_forward_tree: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    return gz_check_launch("gz_pv_forward_tree");
 }
-
 
 // the 16-row MFMA tiles of the residual convs the last tree forward's incremental
 // kernels executed: [root children, grandchildren]
 extern "C" int gz_pv_tree_exec_tiles(const void* d_workspace, int32_t n, int32_t* d_out2, void* stream) {
-    TreeWs t = tree_carve((void*)d_workspace, n, 0);
-    if (hipMemcpyAsync(d_out2, t.ctr + 8, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-        gz_internal_set_error("gz_pv_tree_exec_tiles: copy");
-        return GZ_ERR_HIP;
-    }
+    const TreeWs t = tree_carve((void*)d_workspace, n, 0);
+    if (hipMemcpyAsync(d_out2, t.ctr + CTR_TILES, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+        hipSuccess)
+        return gz_fail(GZ_ERR_HIP, "gz_pv_tree_exec_tiles: copy");
     return GZ_OK;
 }
 
 // counts of the last tree forward's lists: [roots seen, roots with maps, children, full,
 // grandchildren, patch slots claimed]
 extern "C" int gz_pv_tree_stats(const void* d_workspace, int32_t n, int32_t* d_out6, void* stream) {
-    TreeWs t = tree_carve((void*)d_workspace, n, 0);
-    if (hipMemcpyAsync(d_out6, t.ctr, 6 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-        gz_internal_set_error("gz_pv_tree_stats: copy");
-        return GZ_ERR_HIP;
-    }
+    const TreeWs t = tree_carve((void*)d_workspace, n, 0);
+    if (hipMemcpyAsync(d_out6, t.ctr, CTR_STATS * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+        hipSuccess)
+        return gz_fail(GZ_ERR_HIP, "gz_pv_tree_stats: copy");
     return GZ_OK;
 }

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <string>
 
+#include "gz_internal.h"
 #include "gz_search.h"
 
 using namespace gz;
@@ -31,17 +32,6 @@ using namespace gz;
 namespace {
 
 thread_local std::string g_last_error;
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GZ_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return GZ_OK;
-}
 
 struct SearchOut {
     int n_nodes;
@@ -860,11 +850,11 @@ __global__ __launch_bounds__(WAVE) void pattern_kernel(const gz_board_state* boa
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
 int validate_params(const gz_search_params* p) {
-    if (!p) return fail(GZ_ERR_ARG, "params is NULL");
+    if (!p) return gz_fail(GZ_ERR_ARG, "params is NULL");
     if (p->num_simulations < 0 || p->num_simulations > GZ_MAX_SIMULATIONS)
-        return fail(GZ_ERR_ARG, "num_simulations out of range [0, 4095]");
+        return gz_fail(GZ_ERR_ARG, "num_simulations out of range [0, 4095]");
     if (p->planner_steps != 0)
-        return fail(GZ_ERR_UNSUPPORTED, "planner_steps > 0 runs through gz_plan_search / gz_selfplay_plan_run");
+        return gz_fail(GZ_ERR_UNSUPPORTED, "planner_steps > 0 runs through gz_plan_search / gz_selfplay_plan_run");
     return GZ_OK;
 }
 
@@ -876,7 +866,7 @@ extern "C" {
 
 const char* gz_last_error(void) { return g_last_error.c_str(); }
 
-// shared by the other translation units of libgzero (not part of gzero.h)
+// shared by the other translation units of libgzero (gz_internal.h)
 void gz_internal_set_error(const char* msg) { g_last_error = msg ? msg : ""; }
 
 int gz_version(void) { return 1; }
@@ -890,38 +880,38 @@ size_t gz_slot_bytes(int32_t num_simulations) {
 
 int gz_board_step(gz_board_state* d_boards, const int32_t* d_moves, int32_t n, int32_t* d_ok, uint64_t* d_legal,
                   void* stream) {
-    if (n < 0 || (n > 0 && (!d_boards || !d_moves))) return fail(GZ_ERR_ARG, "gz_board_step: bad arguments");
+    if (n < 0 || (n > 0 && (!d_boards || !d_moves))) return gz_fail(GZ_ERR_ARG, "gz_board_step: bad arguments");
     if (n == 0) return GZ_OK;
     board_step_kernel<<<(n + 255) / 256, 256, 0, as_stream(stream)>>>(d_boards, d_moves, n, d_ok, d_legal);
-    return check_launch("board_step_kernel");
+    return gz_check_launch("board_step_kernel");
 }
 
 int gz_policy_move(const gz_board_state* d_boards, const uint64_t* d_keys, int32_t n, int32_t* d_moves,
                    uint32_t* d_draws, void* stream) {
     if (n < 0 || (n > 0 && (!d_boards || !d_keys || !d_moves || !d_draws)))
-        return fail(GZ_ERR_ARG, "gz_policy_move: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_policy_move: bad arguments");
     if (n == 0) return GZ_OK;
     policy_kernel<<<(n + 255) / 256, 256, 0, as_stream(stream)>>>(d_boards, d_keys, n, d_moves, d_draws);
-    return check_launch("policy_kernel");
+    return gz_check_launch("policy_kernel");
 }
 
 int gz_rollout(const gz_board_state* d_boards, const int32_t* d_ai, const uint64_t* d_keys, int32_t n,
                int32_t max_depth, double* d_values, gz_board_state* d_final, uint32_t* d_draws, void* stream) {
     if (n < 0 || (n > 0 && (!d_boards || !d_ai || !d_keys || !d_values || !d_draws)))
-        return fail(GZ_ERR_ARG, "gz_rollout: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_rollout: bad arguments");
     if (n == 0) return GZ_OK;
     rollout_kernel<<<(n + 255) / 256, 256, 0, as_stream(stream)>>>(d_boards, d_ai, d_keys, n, max_depth, d_values,
                                                                    d_final, d_draws);
-    return check_launch("rollout_kernel");
+    return gz_check_launch("rollout_kernel");
 }
 
 int gz_pattern_score(const gz_board_state* d_boards, const int32_t* d_player, int32_t n, int64_t* d_score,
                      double* d_bg, void* stream) {
     if (n < 0 || (n > 0 && (!d_boards || !d_player || !d_score || !d_bg)))
-        return fail(GZ_ERR_ARG, "gz_pattern_score: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_pattern_score: bad arguments");
     if (n == 0) return GZ_OK;
     pattern_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_player, n, d_score, d_bg);
-    return check_launch("pattern_kernel");
+    return gz_check_launch("pattern_kernel");
 }
 
 int gz_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_search_params* p,
@@ -930,25 +920,25 @@ int gz_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t
     int rc = validate_params(p);
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!d_boards || !d_game_ids || !d_moves)))
-        return fail(GZ_ERR_ARG, "gz_search: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_search: bad arguments");
     bool gather = (p->flags & GZ_FLAG_GATHER_LEAVES) != 0;
     if (gather && (!d_leaves || !d_leaf_count || leaf_cap < 0))
-        return fail(GZ_ERR_ARG, "gz_search: leaf gathering needs d_leaves and d_leaf_count");
+        return gz_fail(GZ_ERR_ARG, "gz_search: leaf gathering needs d_leaves and d_leaf_count");
     if (n == 0) return GZ_OK;
     LeafSink sink{d_leaves, leaf_cap, d_leaf_count, nullptr};
     size_t tb = tree_bytes_for(p->num_simulations);
     search_kernel<<<n, WAVE, smem_bytes(p->num_simulations), as_stream(stream)>>>(
         d_boards, d_game_ids, n, *p, (char*)d_trees, tb, d_moves, d_stats, sink, gather ? 1 : 0);
-    return check_launch("search_kernel");
+    return gz_check_launch("search_kernel");
 }
 
 int gz_selfplay_init(void* d_slots, int32_t n_slots, int32_t num_simulations, int64_t game_id_base,
                      int64_t game_id_stride, void* stream) {
     (void)num_simulations;
-    if (!d_slots || n_slots <= 0) return fail(GZ_ERR_ARG, "gz_selfplay_init: bad arguments");
+    if (!d_slots || n_slots <= 0) return gz_fail(GZ_ERR_ARG, "gz_selfplay_init: bad arguments");
     selfplay_init_kernel<<<(n_slots + 255) / 256, 256, 0, as_stream(stream)>>>((char*)d_slots, n_slots, game_id_base,
                                                                                game_id_stride);
-    return check_launch("selfplay_init_kernel");
+    return gz_check_launch("selfplay_init_kernel");
 }
 
 int gz_selfplay_run(void* d_slots, int32_t n_slots, const gz_search_params* p, int32_t n_plies,
@@ -957,14 +947,14 @@ int gz_selfplay_run(void* d_slots, int32_t n_slots, const gz_search_params* p, i
     int rc = validate_params(p);
     if (rc) return rc;
     if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0)
-        return fail(GZ_ERR_ARG, "gz_selfplay_run: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_run: bad arguments");
     bool gather = (p->flags & GZ_FLAG_GATHER_LEAVES) != 0;
-    if (gather && (!d_leaves || leaf_cap < 0)) return fail(GZ_ERR_ARG, "gz_selfplay_run: leaf buffer missing");
+    if (gather && (!d_leaves || leaf_cap < 0)) return gz_fail(GZ_ERR_ARG, "gz_selfplay_run: leaf buffer missing");
     if (n_plies == 0) return GZ_OK;
     LeafSink sink{d_leaves, leaf_cap, &d_counters->leaves, gather ? d_leaf_meta : nullptr};
     selfplay_kernel<<<n_slots, WAVE, smem_bytes(p->num_simulations), as_stream(stream)>>>(
         (char*)d_slots, n_slots, *p, n_plies, d_records, record_cap, sink, gather ? 1 : 0, d_counters);
-    return check_launch("selfplay_kernel");
+    return gz_check_launch("selfplay_kernel");
 }
 
 size_t gz_selfplay_plan_workspace_bytes(int32_t n_slots, int32_t num_simulations) {
@@ -975,22 +965,15 @@ size_t gz_selfplay_plan_workspace_bytes(int32_t n_slots, int32_t num_simulations
     return a + b + c + d + gz_plan_workspace_bytes(n_slots, num_simulations);
 }
 
-// gz_plan_search with leaf tags (gz_plan.hip)
-int gz_internal_plan_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n,
-                            const gz_search_params* p, const gz_planner_params* pp, const float* d_gn_weights,
-                            void* d_workspace, void* d_trees, int32_t* d_moves, gz_search_stats* d_stats,
-                            uint32_t* d_leaves, int32_t leaf_cap, int32_t* d_leaf_count, int32_t* d_leaf_meta,
-                            void* stream);
-
 int gz_selfplay_plan_run(void* d_slots, int32_t n_slots, const gz_search_params* p, const gz_planner_params* pp,
                          const float* d_gn_weights, void* d_workspace, int32_t n_plies, gz_record* d_records,
                          int32_t record_cap, uint32_t* d_leaves, int32_t leaf_cap, int32_t* d_leaf_meta,
                          gz_selfplay_counters* d_counters, void* stream) {
     if (!p || !pp || !d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 ||
         !d_workspace || !d_gn_weights)
-        return fail(GZ_ERR_ARG, "gz_selfplay_plan_run: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_plan_run: bad arguments");
     bool gather = (p->flags & GZ_FLAG_GATHER_LEAVES) != 0;
-    if (gather && (!d_leaves || leaf_cap < 0)) return fail(GZ_ERR_ARG, "gz_selfplay_plan_run: leaf buffer missing");
+    if (gather && (!d_leaves || leaf_cap < 0)) return gz_fail(GZ_ERR_ARG, "gz_selfplay_plan_run: leaf buffer missing");
     char* ws = (char*)d_workspace;
     gz_board_state* d_boards = (gz_board_state*)ws;
     ws += ((size_t)n_slots * sizeof(gz_board_state) + 255) & ~(size_t)255;
@@ -1003,7 +986,7 @@ int gz_selfplay_plan_run(void* d_slots, int32_t n_slots, const gz_search_params*
     hipStream_t st = as_stream(stream);
     for (int it = 0; it < n_plies; it++) {
         selfplay_boards_kernel<<<(n_slots + 255) / 256, 256, 0, st>>>((const char*)d_slots, n_slots, d_boards, d_gids);
-        int rc = check_launch("selfplay_boards_kernel");
+        int rc = gz_check_launch("selfplay_boards_kernel");
         if (rc) return rc;
         rc = gz_internal_plan_search(d_boards, d_gids, n_slots, p, pp, d_gn_weights, ws, nullptr, d_moves, d_stats,
                                      gather ? d_leaves : nullptr, leaf_cap, gather ? &d_counters->leaves : nullptr,
@@ -1011,7 +994,7 @@ int gz_selfplay_plan_run(void* d_slots, int32_t n_slots, const gz_search_params*
         if (rc) return rc;
         selfplay_commit_kernel<<<n_slots, WAVE, 0, st>>>((char*)d_slots, n_slots, d_moves, d_stats, d_records,
                                                          record_cap, d_counters, nullptr, nullptr);
-        rc = check_launch("selfplay_commit_kernel");
+        rc = gz_check_launch("selfplay_commit_kernel");
         if (rc) return rc;
     }
     return GZ_OK;
@@ -1024,14 +1007,12 @@ int gz_internal_selfplay_commit(void* d_slots, int32_t n_slots, const int32_t* d
     selfplay_commit_kernel<<<n_slots, WAVE, 0, as_stream(stream)>>>((char*)d_slots, n_slots, d_moves, d_stats,
                                                                     d_records, record_cap, d_counters, d_pend_visits,
                                                                     d_out_visits);
-    return check_launch("selfplay_commit_kernel");
+    return gz_check_launch("selfplay_commit_kernel");
 }
-
-int gz_plan_gn_stats(void* d_workspace, int32_t n, int32_t num_simulations, int64_t* out, int32_t reset, void* stream);
 
 int gz_selfplay_plan_gn_stats(void* d_workspace, int32_t n_slots, int32_t num_simulations, int64_t* out,
                               int32_t reset, void* stream) {
-    if (!d_workspace || n_slots <= 0) return fail(GZ_ERR_ARG, "gz_selfplay_plan_gn_stats: bad arguments");
+    if (!d_workspace || n_slots <= 0) return gz_fail(GZ_ERR_ARG, "gz_selfplay_plan_gn_stats: bad arguments");
     char* ws = (char*)d_workspace;
     ws += ((size_t)n_slots * sizeof(gz_board_state) + 255) & ~(size_t)255;
     ws += ((size_t)n_slots * 8 + 255) & ~(size_t)255;
@@ -1106,9 +1087,9 @@ __global__ void selfplay_draws_kernel(const char* slots, int n_slots, int64_t* o
 }
 
 int gz_selfplay_set_game_end(void* d_slots, int32_t n_slots, int64_t game_id_end, void* stream) {
-    if (!d_slots || n_slots <= 0) return fail(GZ_ERR_ARG, "gz_selfplay_set_game_end: bad arguments");
+    if (!d_slots || n_slots <= 0) return gz_fail(GZ_ERR_ARG, "gz_selfplay_set_game_end: bad arguments");
     selfplay_limit_kernel<<<(n_slots + 255) / 256, 256, 0, as_stream(stream)>>>((char*)d_slots, n_slots, game_id_end);
-    return check_launch("selfplay_limit_kernel");
+    return gz_check_launch("selfplay_limit_kernel");
 }
 
 size_t gz_selfplay_compact_workspace_bytes(int32_t n_slots) { return (size_t)(n_slots > 0 ? n_slots : 0) * 4; }
@@ -1116,28 +1097,28 @@ size_t gz_selfplay_compact_workspace_bytes(int32_t n_slots) { return (size_t)(n_
 int gz_selfplay_compact(const void* d_slots, int32_t n_slots, void* d_dst, int32_t* d_n_active, void* d_workspace,
                         void* stream) {
     if (!d_slots || n_slots <= 0 || !d_dst || d_dst == d_slots || !d_n_active || !d_workspace)
-        return fail(GZ_ERR_ARG, "gz_selfplay_compact: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_compact: bad arguments");
     int32_t* order = (int32_t*)d_workspace;
     selfplay_order_kernel<<<1, 1024, 0, as_stream(stream)>>>((const char*)d_slots, n_slots, order, d_n_active);
-    int rc = check_launch("selfplay_order_kernel");
+    int rc = gz_check_launch("selfplay_order_kernel");
     if (rc) return rc;
     selfplay_move_kernel<<<n_slots, 256, 0, as_stream(stream)>>>((const char*)d_slots, order, (char*)d_dst);
-    return check_launch("selfplay_move_kernel");
+    return gz_check_launch("selfplay_move_kernel");
 }
 
 int gz_selfplay_draws(const void* d_slots, int32_t n_slots, int64_t* d_out, void* stream) {
-    if (!d_slots || n_slots <= 0 || !d_out) return fail(GZ_ERR_ARG, "gz_selfplay_draws: bad arguments");
+    if (!d_slots || n_slots <= 0 || !d_out) return gz_fail(GZ_ERR_ARG, "gz_selfplay_draws: bad arguments");
     selfplay_draws_kernel<<<(n_slots + 255) / 256, 256, 0, as_stream(stream)>>>((const char*)d_slots, n_slots, d_out);
-    return check_launch("selfplay_draws_kernel");
+    return gz_check_launch("selfplay_draws_kernel");
 }
 
 int gz_selfplay_boards(const void* d_slots, int32_t n_slots, int32_t num_simulations, gz_board_state* d_out,
                        int64_t* d_game_ids, void* stream) {
     (void)num_simulations;
-    if (!d_slots || n_slots <= 0 || !d_out) return fail(GZ_ERR_ARG, "gz_selfplay_boards: bad arguments");
+    if (!d_slots || n_slots <= 0 || !d_out) return gz_fail(GZ_ERR_ARG, "gz_selfplay_boards: bad arguments");
     selfplay_boards_kernel<<<(n_slots + 255) / 256, 256, 0, as_stream(stream)>>>((const char*)d_slots, n_slots, d_out,
                                                                                  d_game_ids);
-    return check_launch("selfplay_boards_kernel");
+    return gz_check_launch("selfplay_boards_kernel");
 }
 
 }  // extern "C"

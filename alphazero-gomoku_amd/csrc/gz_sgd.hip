@@ -29,10 +29,8 @@
 #include <cmath>
 #include <string>
 
-#include "../../include/gzero.h"
 #include "gz_f16conv.h"
-
-extern "C" void gz_internal_set_error(const char* msg);
+#include "gz_internal.h"
 
 namespace {
 using namespace gzc;
@@ -1156,28 +1154,17 @@ size_t ws_layout(int B, Ws* w, char* base) {
     return off;
 }
 
-int sgd_fail(int code, const std::string& msg) {
-    gz_internal_set_error(msg.c_str());
-    return code;
-}
-
-int sgd_check(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sgd_fail(GZ_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return GZ_OK;
-}
-
 int check_net(const gz_sgd_net* net, int B, const void* ws) {
-    if (!net || B < 1 || B > GZ_SGD_MAX_BOARDS || !ws) return sgd_fail(GZ_ERR_ARG, "gz_sgd: bad arguments");
+    if (!net || B < 1 || B > GZ_SGD_MAX_BOARDS || !ws) return gz_fail(GZ_ERR_ARG, "gz_sgd: bad arguments");
     for (int i = 0; i < NBN; i++)
-        if (!net->bn_weight[i] || !net->bn_bias[i]) return sgd_fail(GZ_ERR_ARG, "gz_sgd: BatchNorm parameters are NULL");
+        if (!net->bn_weight[i] || !net->bn_bias[i]) return gz_fail(GZ_ERR_ARG, "gz_sgd: BatchNorm parameters are NULL");
     for (int i = 0; i < LAYERS; i++)
-        if (!net->conv_weight[i] || !net->conv_bias[i]) return sgd_fail(GZ_ERR_ARG, "gz_sgd: conv parameters are NULL");
+        if (!net->conv_weight[i] || !net->conv_bias[i]) return gz_fail(GZ_ERR_ARG, "gz_sgd: conv parameters are NULL");
     if (!net->conv0_weight || !net->conv0_bias || !net->policy_weight || !net->policy_bias || !net->value_weight ||
         !net->value_bias)
-        return sgd_fail(GZ_ERR_ARG, "gz_sgd: conv0 / head conv parameters are NULL");
+        return gz_fail(GZ_ERR_ARG, "gz_sgd: conv0 / head conv parameters are NULL");
     if (!(net->eps > 0.f) || !(net->momentum >= 0.f && net->momentum <= 1.f))
-        return sgd_fail(GZ_ERR_ARG, "gz_sgd: eps must be > 0 and momentum in [0, 1]");
+        return gz_fail(GZ_ERR_ARG, "gz_sgd: eps must be > 0 and momentum in [0, 1]");
     return GZ_OK;
 }
 
@@ -1188,13 +1175,13 @@ int check_net(const gz_sgd_net* net, int B, const void* ws) {
 // (conv0's output); fp32 NHWC [boards][225][128]
 extern "C" int gz_sgd_saved(const void* d_ws, int32_t B, int32_t which, float* d_out, void* stream) {
     if (!d_ws || !d_out || B < 1 || B > GZ_SGD_MAX_BOARDS || which < 0 || which > 9)
-        return sgd_fail(GZ_ERR_ARG, "gz_sgd_saved: bad arguments");
+        return gz_fail(GZ_ERR_ARG, "gz_sgd_saved: bad arguments");
     Ws w;
     ws_layout(B, &w, (char*)d_ws);
     const float* src = which < 4 ? w.act[which] : which < 8 ? w.y[which - 3] : which == 8 ? w.out : w.y[0];
     if (hipMemcpyAsync(d_out, src, (size_t)B * NPOS * CH * sizeof(float), hipMemcpyDeviceToDevice,
                        (hipStream_t)stream) != hipSuccess)
-        return sgd_fail(GZ_ERR_HIP, "gz_sgd_saved: copy");
+        return gz_fail(GZ_ERR_HIP, "gz_sgd_saved: copy");
     return GZ_OK;
 }
 
@@ -1206,14 +1193,14 @@ extern "C" int gz_sgd_forward(const gz_sgd_net* net, int32_t B, const float* d_x
                               void* d_ws, void* stream) {
     int rc;
     if ((rc = check_net(net, B, d_ws))) return rc;
-    if (!d_x || !d_pin || !d_vin) return sgd_fail(GZ_ERR_ARG, "gz_sgd_forward: x / outputs are NULL");
+    if (!d_x || !d_pin || !d_vin) return gz_fail(GZ_ERR_ARG, "gz_sgd_forward: x / outputs are NULL");
     hipStream_t s = (hipStream_t)stream;
     Ws w;
     ws_layout(B, &w, (char*)d_ws);
     PackArgs pa;
     for (int i = 0; i < LAYERS; i++) pa.w[i] = net->conv_weight[i];
     if (hipMemsetAsync(w.wsc, 0, 8 * sizeof(float), s) != hipSuccess)
-        return sgd_fail(GZ_ERR_HIP, "gz_sgd_forward: memset");
+        return gz_fail(GZ_ERR_HIP, "gz_sgd_forward: memset");
     sgd_wmax_kernel<<<dim3(32, LAYERS), 256, 0, s>>>(pa, (unsigned*)w.wsc);
     sgd_pack_kernel<<<(LAYERS * 2 * FRAG_HALVES + 255) / 256, 256, 0, s>>>(pa, w.wsc, w.frag);
     // y0 = conv0(x) and its BN0 partials
@@ -1221,7 +1208,7 @@ extern "C" int gz_sgd_forward(const gz_sgd_net* net, int32_t B, const float* d_x
     sgd_bn_fwd_reduce_kernel<<<1, RED_THREADS, 0, s>>>(w.fpart, B, net->bn_weight[0], net->bn_bias[0],
                                                       net->bn_running_mean[0], net->bn_running_var[0], net->momentum,
                                                       net->eps, w.coef);
-    if ((rc = sgd_check("gz_sgd_forward: conv0"))) return rc;
+    if ((rc = gz_check_launch("gz_sgd_forward: conv0"))) return rc;
     // conv L (1..4): input = relu(BN_{L-1}(y_{L-1}) (+ skip)), skip a0 for conv 3's input a1
     for (int L = 1; L <= LAYERS; L++) {
         ConvArgs a{};
@@ -1239,28 +1226,28 @@ extern "C" int gz_sgd_forward(const gz_sgd_net* net, int32_t B, const float* d_x
         sgd_bn_fwd_reduce_kernel<<<1, RED_THREADS, 0, s>>>(a.part, B, net->bn_weight[L], net->bn_bias[L],
                                                           net->bn_running_mean[L], net->bn_running_var[L],
                                                           net->momentum, net->eps, w.coef + (size_t)L * CO_FLOATS);
-        if ((rc = sgd_check("gz_sgd_forward: conv"))) return rc;
+        if ((rc = gz_check_launch("gz_sgd_forward: conv"))) return rc;
     }
     // a2 = relu(BN4(y4) + a1), then the heads' 1x1 convs
     const int rows = B * NPOS;
     sgd_out_heads_kernel<<<(rows + 255) / 256, 256, 0, s>>>(w.y[4], w.coef + 4 * CO_FLOATS, w.act[2],
                                                             net->policy_weight, net->policy_bias, net->value_weight,
                                                             net->value_bias, w.out, d_pin, d_vin, rows);
-    return sgd_check("gz_sgd_forward: output");
+    return gz_check_launch("gz_sgd_forward: output");
 }
 
 extern "C" int gz_sgd_backward(const gz_sgd_net* net, int32_t B, const float* d_x, const float* d_dpin,
                                const float* d_dvin, const gz_sgd_grads* gr, void* d_ws, void* stream) {
     int rc;
     if ((rc = check_net(net, B, d_ws))) return rc;
-    if (!d_x || !d_dpin || !d_dvin || !gr) return sgd_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL argument");
+    if (!d_x || !d_dpin || !d_dvin || !gr) return gz_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL argument");
     for (int i = 0; i < NBN; i++)
-        if (!gr->bn_weight[i] || !gr->bn_bias[i]) return sgd_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL gradient");
+        if (!gr->bn_weight[i] || !gr->bn_bias[i]) return gz_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL gradient");
     for (int i = 0; i < LAYERS; i++)
-        if (!gr->conv_weight[i] || !gr->conv_bias[i]) return sgd_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL gradient");
+        if (!gr->conv_weight[i] || !gr->conv_bias[i]) return gz_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL gradient");
     if (!gr->conv0_weight || !gr->conv0_bias || !gr->policy_weight || !gr->policy_bias || !gr->value_weight ||
         !gr->value_bias)
-        return sgd_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL gradient");
+        return gz_fail(GZ_ERR_ARG, "gz_sgd_backward: NULL gradient");
     hipStream_t s = (hipStream_t)stream;
     Ws w;
     ws_layout(B, &w, (char*)d_ws);
@@ -1295,7 +1282,7 @@ extern "C" int gz_sgd_backward(const gz_sgd_net* net, int32_t B, const float* d_
         sgd_wgrad16_kernel<<<4 * w.NG, WG_THREADS, 0, s>>>(w.act[L - 1], w.dy, w.xmax + (size_t)(L - 1) * B,
                                                            w.dymax + (size_t)(L - 1) * B, B, w.G, w.NG, w.wpart);
         sgd_wreduce_kernel<<<(9 * CH * CH + 255) / 256, 256, 0, s>>>(w.wpart, w.NG, gr->conv_weight[L - 1]);
-        if ((rc = sgd_check("gz_sgd_backward: conv"))) return rc;
+        if ((rc = gz_check_launch("gz_sgd_backward: conv"))) return rc;
     }
     // BN0, then conv0's weight and bias gradients (its input gradient is not needed)
     sgd_bn_bwd_reduce_kernel<<<1, RED_THREADS, 0, s>>>(w.bpart, B, net->bn_weight[0], w.coef, gr->bn_weight[0],
@@ -1303,7 +1290,7 @@ extern "C" int gz_sgd_backward(const gz_sgd_net* net, int32_t B, const float* d_
     sgd_conv0_wgrad_kernel<<<B, PB_THREADS, 0, s>>>(w.g[0], w.y[0], w.coef, d_x, w.c0part);
     sgd_conv0_reduce_kernel<<<(CH * (C0K + 1) + 255) / 256, 256, 0, s>>>(w.c0part, B, gr->conv0_weight,
                                                                          gr->conv0_bias);
-    return sgd_check("gz_sgd_backward: conv0");
+    return gz_check_launch("gz_sgd_backward: conv0");
 }
 
 extern "C" size_t gz_sgd_fc_workspace_bytes(int32_t boards) {
@@ -1319,11 +1306,11 @@ int sgd_fc_loss_impl(const char* who, const gz_sgd_fc* fc, int32_t B, const floa
                      const gz_sgd_fc_grads* gr, float* d_loss, void* d_ws, void* stream) {
     if (!fc || !gr || B < 1 || B > GZ_SGD_MAX_BOARDS || !d_pin || !d_vin || !d_y || !d_v || !d_dpin || !d_dvin ||
         !d_loss || !d_ws)
-        return sgd_fail(GZ_ERR_ARG, (std::string(who) + ": bad arguments").c_str());
+        return gz_fail(GZ_ERR_ARG, (std::string(who) + ": bad arguments").c_str());
     if (!fc->policy_weight || !fc->policy_bias || !fc->value1_weight || !fc->value1_bias || !fc->value2_weight ||
         !fc->value2_bias || !gr->policy_weight || !gr->policy_bias || !gr->value1_weight || !gr->value1_bias ||
         !gr->value2_weight || !gr->value2_bias)
-        return sgd_fail(GZ_ERR_ARG, (std::string(who) + ": NULL parameter or gradient").c_str());
+        return gz_fail(GZ_ERR_ARG, (std::string(who) + ": NULL parameter or gradient").c_str());
     hipStream_t s = (hipStream_t)stream;
     float* save = (float*)d_ws;
     auto job = [](const float* A, int sak, int sam, const float* Bm, int sbk, int sbn, const float* bias, float* C,
@@ -1361,7 +1348,7 @@ int sgd_fc_loss_impl(const char* who, const gz_sgd_fc* fc, int32_t B, const floa
     g.n = 4;
     launch(g);
     sgd_fc_small_kernel<<<(FC_SMALL + 3) / 4, 256, 0, s>>>(save, B, *gr, d_loss);
-    return sgd_check(who);
+    return gz_check_launch(who);
 }
 }  // namespace
 

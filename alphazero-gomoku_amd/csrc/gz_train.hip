@@ -23,7 +23,7 @@
 
 #include <string>
 
-#include "../../include/gzero.h"
+#include "gz_internal.h"
 
 namespace {
 
@@ -177,18 +177,11 @@ __global__ __launch_bounds__(64 * PI_WAVES) void dataset_pi_kernel(const uint16_
 
 }  // namespace
 
-extern "C" void gz_internal_set_error(const char* msg);
-
 extern "C" int gz_dataset_pi(const uint16_t* d_visits, int32_t n, const int32_t* d_sel, int32_t m,
                              const int64_t* d_ids, int64_t count, float* d_pi, void* stream) {
-    if (n < 0 || m < 0 || count < 0 || (n > 0 && !d_visits) || (m > 0 && !d_sel) || (count > 0 && !d_pi)) {
-        gz_internal_set_error("gz_dataset_pi: bad arguments");
-        return GZ_ERR_ARG;
-    }
-    if (m > 0 && n == 0) {
-        gz_internal_set_error("gz_dataset_pi: augmentation of an empty replay");
-        return GZ_ERR_ARG;
-    }
+    if (n < 0 || m < 0 || count < 0 || (n > 0 && !d_visits) || (m > 0 && !d_sel) || (count > 0 && !d_pi))
+        return gz_fail(GZ_ERR_ARG, "gz_dataset_pi: bad arguments");
+    if (m > 0 && n == 0) return gz_fail(GZ_ERR_ARG, "gz_dataset_pi: augmentation of an empty replay");
     if (count == 0) return GZ_OK;
     const long long n_all = (long long)n + 8LL * m;
     long long wg = ((long long)count + PI_WAVES - 1) / PI_WAVES;
@@ -198,26 +191,16 @@ extern "C" int gz_dataset_pi(const uint16_t* d_visits, int32_t n, const int32_t*
         dataset_pi_kernel<false><<<(unsigned)wg, 64 * PI_WAVES, 0, st>>>(d_visits, n, d_sel, d_ids, n_all, count, d_pi);
     else
         dataset_pi_kernel<true><<<(unsigned)wg, 64 * PI_WAVES, 0, st>>>(d_visits, n, d_sel, d_ids, n_all, count, d_pi);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("gz_dataset_pi: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    return gz_check_launch("gz_dataset_pi");
 }
 
 namespace {
 int launch(const gz_record* d_records, int32_t n, const int32_t* d_sel, int32_t m, const int64_t* d_ids,
            long long count, int32_t flags, float* d_x, int64_t* d_y, float* d_v, hipStream_t st, const char* who) {
     if (n < 0 || m < 0 || count < 0 || (n > 0 && !d_records) || (m > 0 && !d_sel) ||
-        (count > 0 && (!d_x || !d_y || !d_v)) || (flags & ~GZ_AUG_FIX_LABELS)) {
-        gz_internal_set_error((std::string(who) + ": bad arguments").c_str());
-        return GZ_ERR_ARG;
-    }
-    if (m > 0 && n == 0) {
-        gz_internal_set_error((std::string(who) + ": augmentation of an empty replay").c_str());
-        return GZ_ERR_ARG;
-    }
+        (count > 0 && (!d_x || !d_y || !d_v)) || (flags & ~GZ_AUG_FIX_LABELS))
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": bad arguments");
+    if (m > 0 && n == 0) return gz_fail(GZ_ERR_ARG, std::string(who) + ": augmentation of an empty replay");
     if (count == 0) return GZ_OK;
     const long long n_all = (long long)n + 8LL * m;
     const int bs = 256;
@@ -231,12 +214,7 @@ int launch(const gz_record* d_records, int32_t n, const int32_t* d_sel, int32_t 
                                                                                   count, d_x);
     dataset_labels_kernel<<<(unsigned)((count + bs - 1) / bs), bs, 0, st>>>(
         d_records, n, d_sel, d_ids, n_all, count, (flags & GZ_AUG_FIX_LABELS) ? 1 : 0, d_y, d_v);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string(who) + ": " + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    return gz_check_launch(who);
 }
 }  // namespace
 
@@ -249,10 +227,7 @@ extern "C" int gz_dataset_build(const gz_record* d_records, int32_t n, const int
 extern "C" int gz_dataset_gather(const gz_record* d_records, int32_t n, const int32_t* d_sel, int32_t m,
                                  const int64_t* d_ids, int64_t count, int32_t flags, float* d_x, int64_t* d_y,
                                  float* d_v, void* stream) {
-    if (count > 0 && !d_ids) {
-        gz_internal_set_error("gz_dataset_gather: d_ids is required");
-        return GZ_ERR_ARG;
-    }
+    if (count > 0 && !d_ids) return gz_fail(GZ_ERR_ARG, "gz_dataset_gather: d_ids is required");
     return launch(d_records, n, d_sel, m, d_ids, count, flags, d_x, d_y, d_v, (hipStream_t)stream,
                   "gz_dataset_gather");
 }
@@ -353,19 +328,15 @@ extern "C" size_t gz_adam_workspace_bytes(void) { return ADAM_BLOCKS * sizeof(do
 extern "C" int gz_adam_step(const gz_adam_tensor* tensors, int32_t n_tensors, float lr, float beta1, float beta2,
                             float eps, float weight_decay, int64_t step, float max_norm, float* d_norm,
                             void* d_workspace, void* stream) {
-    if (!tensors || n_tensors < 1 || n_tensors > GZ_ADAM_MAX_TENSORS || step < 1 || !d_workspace) {
-        gz_internal_set_error("gz_adam_step: bad arguments");
-        return GZ_ERR_ARG;
-    }
+    if (!tensors || n_tensors < 1 || n_tensors > GZ_ADAM_MAX_TENSORS || step < 1 || !d_workspace)
+        return gz_fail(GZ_ERR_ARG, "gz_adam_step: bad arguments");
     AdamTable T;
     T.n = n_tensors;
     T.start[0] = 0;
     for (int k = 0; k < n_tensors; k++) {
         const gz_adam_tensor& t = tensors[k];
-        if (t.numel < 0 || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))) {
-            gz_internal_set_error("gz_adam_step: bad tensor");
-            return GZ_ERR_ARG;
-        }
+        if (t.numel < 0 || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)))
+            return gz_fail(GZ_ERR_ARG, "gz_adam_step: bad tensor");
         T.t[k] = t;
         T.start[k + 1] = T.start[k] + t.numel;
     }
@@ -379,10 +350,5 @@ extern "C" int gz_adam_step(const gz_adam_tensor* tensors, int32_t n_tensors, fl
     if (max_norm > 0.f) adam_norm_kernel<<<ADAM_BLOCKS, ADAM_THREADS, 0, st>>>(T, partial);
     adam_update_kernel<<<ADAM_BLOCKS, ADAM_THREADS, 0, st>>>(T, partial, lr, beta1, beta2, eps, weight_decay, bc1,
                                                              bc2s, max_norm, d_norm);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gz_internal_set_error((std::string("gz_adam_step: ") + hipGetErrorString(e)).c_str());
-        return GZ_ERR_HIP;
-    }
-    return GZ_OK;
+    return gz_check_launch("gz_adam_step");
 }
