@@ -54,6 +54,30 @@
 //   gz_pv_workspace_bytes(n) for the forward.
 // About 2.3 KB per node: 1.9 GB at 4096 games x 200 simulations.
 //
+// Tree reuse between plies (opt-in: gz_puct_reroot, gz_selfplay_puct_rounds).  A search
+// ends when visits[0] == S+1.  After the move m the next ply's tree is the subtree of
+// child[0][m]: reroot() keeps its nodes in creation order, renumbers them densely and
+// moves every array's rows down in place (a node's new index is below its old one and
+// rows are moved in ascending order, so no row is overwritten before it is read; the
+// remap table lives in LDS).  W, visits, prior, value, board and term are carried bit
+// for bit, so the tree is the one a search from the new root would have built from the
+// same evaluations, with visits[0] of its S+1 visits already made.  In
+// gz_selfplay_puct_rounds every slot keeps its own clock: a round is
+//
+//   1. puct_advance_kernel     a slot whose root is at budget picks its move (pick_move,
+//                              as puct_finish_kernel), stashes the visit row and, unless
+//                              the move ends the game, re-roots its tree under it (one
+//                              workgroup of 1024 per slot; the others leave at once);
+//   2. selfplay_commit_kernel  plays the move (move -1: the slot is left alone);
+//   3. puct_round_kernel       a tree that is not the slot's (a new game, a reset) gives
+//                              way to a fresh root from the slot header, whose board is
+//                              its leaf; every other slot descends as in step 1 above;
+//   4. gz_pv_forward, 5. puct_backup_kernel as above,
+//
+// so every live slot has exactly one leaf in every forward.  A tree belongs to a slot
+// while its header says so (reuse == REUSE_MAGIC) and its root is the slot's game id,
+// move count and position; gz_selfplay_puct_reset clears the mark.
+//
 // Export (gz_puct_trees, gz_puct_tree_bytes(S) = al256(16 + 1884 M) per game):
 //   i32 n_nodes, n_evals, main_draws, move; then W, prior, visits, value, board,
 //   parent, move, term as above (no child table), nodes in creation order.
@@ -90,8 +114,12 @@ struct PuctHdr {  // 128 bytes
     int32_t main_draws;  // draws on the (game, ply, 0) stream (0 or 1)
     int32_t pending;     // node waiting for its prior and value, -1 = none
     int32_t move;
-    int32_t pad[6];
+    int32_t new_evals;   // evaluations since the last move (gz_selfplay_puct_rounds' slot statistics)
+    int32_t reuse;       // REUSE_MAGIC: a tree of gz_selfplay_puct_rounds (0: gz_puct_begin, a reset)
+    int32_t rounds;      // rounds of gz_selfplay_puct_rounds since the last move
+    int32_t pad[3];
 };
+constexpr int32_t REUSE_MAGIC = 0x52455553;
 static_assert(sizeof(PuctHdr) == 128, "puct header");
 
 __host__ __device__ inline size_t game_stride_for(int S) {
@@ -179,6 +207,28 @@ __device__ inline void new_node(const PuctTree& t, int j, int parent, int move, 
     }
 }
 
+// a one-node tree: the root waits for its evaluation (pending 0) unless the game is over
+__device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& white, int64_t game_id, int n_moves,
+                                  int player, bool over, int32_t reuse) {
+    new_node(t, 0, -1, 255, 0, black, white);
+    if (lane_id() == 0) {
+        PuctHdr* h = t.h;
+        store_bb(h->black, black);
+        store_bb(h->white, white);
+        h->game_id = game_id;
+        h->n_moves = n_moves;
+        h->player = player;
+        h->over = over ? 1 : 0;
+        h->n_nodes = 1;
+        h->n_evals = 0;
+        h->main_draws = 0;
+        h->pending = over ? -1 : 0;
+        h->move = -1;
+        h->new_evals = 0;
+        h->reuse = reuse;
+    }
+}
+
 // ---------------------------------------------------------------- begin
 __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* boards, const int64_t* game_ids, int n,
                                                           gz_puct_params p, char* ws, uint32_t* leaves,
@@ -200,36 +250,23 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
     load_bb(black, bs.black);
     load_bb(white, bs.white);
     const bool over = bs.over != 0 || !bb_any(empties(black, white));
-    new_node(t, 0, -1, 255, 0, black, white);
-    if (lane == 0) {
-        PuctHdr* h = t.h;
-        store_bb(h->black, black);
-        store_bb(h->white, white);
-        h->game_id = game_ids[g];
-        h->n_moves = bs.n_moves;
-        h->player = bs.player;
-        h->over = over ? 1 : 0;
-        h->n_nodes = 1;
-        h->n_evals = 0;
-        h->main_draws = 0;
-        h->pending = over ? -1 : 0;
-        h->move = -1;
-    }
+    begin_root(t, black, white, game_ids[g], bs.n_moves, bs.player, over, 0);
     write_leaf(leaves, active, g, black, white, !over);
 }
 
 // ---------------------------------------------------------------- select
-__global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int S, uint32_t* leaves, int32_t* active) {
-    const int g = blockIdx.x;
-    if (g >= n) return;
+// One simulation's descent of game g's tree: the new leaf's board into row g, or an
+// empty row (a terminal node backed up, a game that is over, waits for a backup or
+// whose root already has its S+1 visits -- the last only with tree reuse, where a
+// game can reach its budget before the others).
+__device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, uint32_t* leaves, int32_t* active) {
     const int lane = lane_id();
-    const PuctCfg cfg = *(const PuctCfg*)ws;
-    PuctTree t = tree_of(ws, g, S);
     PuctHdr* h = t.h;
     BB black, white;
     load_bb(black, h->black);
     load_bb(white, h->white);
-    if (h->over || h->pending >= 0) {  // (pending: the caller skipped a backup; keep the tree as it is)
+    // (pending: the caller skipped a backup; keep the tree as it is)
+    if (h->over || h->pending >= 0 || t.visits[0] > S) {
         write_leaf(leaves, active, g, black, white, false);
         return;
     }
@@ -259,7 +296,7 @@ __global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int 
                     nn = t.visits[cj];
                     q = nn ? t.W[cj] / (double)nn : 0.0;
                 }
-                const double u = ((cfg.c_puct * pr[c]) * sq) / (1.0 + (double)nn);
+                const double u = ((c_puct * pr[c]) * sq) / (1.0 + (double)nn);
                 const double sc = q + u;
                 if (sc > bv) {
                     bv = sc;
@@ -308,6 +345,13 @@ __global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int 
     }
 }
 
+__global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int S, uint32_t* leaves, int32_t* active) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const PuctCfg cfg = *(const PuctCfg*)ws;
+    descend(tree_of(ws, g, S), cfg.c_puct, S, g, leaves, active);
+}
+
 // ---------------------------------------------------------------- backup
 __global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int S, const double* prior,
                                                            const float* value) {
@@ -324,10 +368,83 @@ __global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int 
         backup(t, j, (double)v);
         t.h->pending = -1;
         t.h->n_evals += 1;
+        t.h->new_evals += 1;
     }
 }
 
 // ---------------------------------------------------------------- finish
+// the root-child visit counts of this lane's cells (v[k]: cell lane + 64 k); returns their sum
+__device__ inline long long root_visits(const PuctTree& t, bool over, int v[4]) {
+    const int lane = lane_id();
+    long long tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int c = lane + WAVE * k;
+        v[k] = 0;
+        if (c < GZ_CELLS) {
+            const int cj = over ? -1 : t.child[c];
+            if (cj >= 0) v[k] = t.visits[cj];
+        }
+        tot += v[k];
+    }
+    return wave_sum_ll(tot);
+}
+
+// the move of a live root from its visit counts (root_visits); draws: main-stream draws used
+__device__ inline int pick_move(const PuctHdr* h, const PuctCfg& cfg, const BB& E, const int v[4], long long total,
+                                int& draws) {
+    const int lane = lane_id();
+    int mv = -1;
+    draws = 0;
+    if (h->n_moves >= cfg.temp_plies || total == 0) {
+        // most visits, first maximum (occupied cells never win: -1)
+        int bv = -2, bi = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = lane + WAVE * k;
+            if (c < GZ_CELLS) {
+                const int x = bb_test(E, cell_to_bit(c)) ? v[k] : -1;
+                if (x > bv) {
+                    bv = x;
+                    bi = c;
+                }
+            }
+        }
+        wave_argmax_int(bv, bi);
+        mv = bi;
+    } else {
+        // one draw of the game's main stream; the first cell whose running visit
+        // sum exceeds pick = (draw * total) >> 64
+        const uint64_t key = stream_key(cfg.seed, h->game_id, h->n_moves, 0);
+        const uint64_t pick = __umul64hi(draw(key, 0), (uint64_t)total);
+        draws = 1;
+        long long base = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            long long inc = v[k];
+#pragma unroll
+            for (int off = 1; off < WAVE; off <<= 1) {
+                const long long o = __shfl_up(inc, off);
+                if (lane >= off) inc += o;
+            }
+            const uint64_t hit = ballot((uint64_t)(base + inc) > pick);
+            if (mv < 0 && hit) mv = WAVE * k + (int)__builtin_ctzll(hit);
+            base += __shfl(inc, WAVE - 1);
+        }
+    }
+    return mv;
+}
+
+__device__ inline gz_search_stats search_stats(int n_nodes, int predicts, int draws, long long sim_draws) {
+    gz_search_stats st;
+    st.n_nodes = n_nodes;
+    st.predicts = predicts;
+    st.main_draws = draws;
+    st.pad = 0;
+    st.sim_draws = sim_draws;
+    return st;
+}
+
 __global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int S, int32_t* moves, int32_t* visits,
                                                            double* root_q, gz_search_stats* stats) {
     const int g = blockIdx.x;
@@ -342,74 +459,289 @@ __global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int 
     const BB E = empties(black, white);
     const bool over = h->over != 0;
     int v[4];
-    long long tot = 0;
+    const long long total = root_visits(t, over, v);
+    if (visits) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int c = lane + WAVE * k;
-        v[k] = 0;
-        if (c < GZ_CELLS) {
-            const int cj = over ? -1 : t.child[c];
-            if (cj >= 0) v[k] = t.visits[cj];
-            if (visits) visits[(size_t)g * GZ_CELLS + c] = v[k];
-        }
-        tot += v[k];
+        for (int k = 0; k < 4; k++)
+            if (lane + WAVE * k < GZ_CELLS) visits[(size_t)g * GZ_CELLS + lane + WAVE * k] = v[k];
     }
-    const long long total = wave_sum_ll(tot);
     int mv = -1, draws = 0;
-    if (!over) {
-        if (h->n_moves >= cfg.temp_plies || total == 0) {
-            // most visits, first maximum (occupied cells never win: -1)
-            int bv = -2, bi = INT_MAX;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int c = lane + WAVE * k;
-                if (c < GZ_CELLS) {
-                    const int x = bb_test(E, cell_to_bit(c)) ? v[k] : -1;
-                    if (x > bv) {
-                        bv = x;
-                        bi = c;
-                    }
-                }
-            }
-            wave_argmax_int(bv, bi);
-            mv = bi;
-        } else {
-            // one draw of the game's main stream; the first cell whose running visit
-            // sum exceeds pick = (draw * total) >> 64
-            const uint64_t key = stream_key(cfg.seed, h->game_id, h->n_moves, 0);
-            const uint64_t pick = __umul64hi(draw(key, 0), (uint64_t)total);
-            draws = 1;
-            long long base = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                long long inc = v[k];
-#pragma unroll
-                for (int off = 1; off < WAVE; off <<= 1) {
-                    const long long o = __shfl_up(inc, off);
-                    if (lane >= off) inc += o;
-                }
-                const uint64_t hit = ballot((uint64_t)(base + inc) > pick);
-                if (mv < 0 && hit) mv = WAVE * k + (int)__builtin_ctzll(hit);
-                base += __shfl(inc, WAVE - 1);
-            }
-        }
-    }
+    if (!over) mv = pick_move(h, cfg, E, v, total, draws);
     if (lane == 0) {
         moves[g] = mv;
         // the root's mean value for the side to move (W[0] is the opponent's view)
         if (root_q) root_q[g] = (over || t.visits[0] == 0) ? 0.0 : -t.W[0] / (double)t.visits[0];
         h->move = mv;
         h->main_draws = draws;
-        if (stats) {
-            gz_search_stats st;
-            st.n_nodes = over ? 0 : h->n_nodes;
-            st.predicts = h->n_evals;
-            st.main_draws = draws;
-            st.pad = 0;
-            st.sim_draws = 0;
-            stats[g] = st;
+        if (stats) stats[g] = search_stats(over ? 0 : h->n_nodes, h->n_evals, draws, 0);
+    }
+}
+
+// ---------------------------------------------------------------- tree reuse
+// Re-root game t at its node c (1 <= c < n_nodes): the subtree of c becomes the tree, the
+// header's position advances by c's move.  The whole workgroup (RR_THREADS; every thread
+// calls) works on the one game; map [S+1], list [S+1]: LDS.
+//   mark    wave 0: keep[j] = j == c || keep[parent[j]], 64 nodes at a time in ascending
+//           order (parents precede children; inside a chunk the flags are propagated
+//           until they stand), new index = rank among the kept: map[old] = new or -1,
+//           list[new] = old;
+//   move    every array's kept rows to their new places in ascending order.  new < old
+//           for every kept node, so a batch reads [U x RR_THREADS elements at or above
+//           their old places], waits for them (every wave, then a barrier), then writes
+//           places below everything still to be read: in place, no second tree.
+constexpr int RR_THREADS = 1024;
+
+template <typename T, int W, int U, typename F>
+__device__ inline void move_rows(T* a, const int16_t* list, int kept, F f) {
+    const int tid = threadIdx.x;
+    const int total = kept * W;
+    for (int i0 = 0; i0 < total; i0 += U * RR_THREADS) {
+        T v[U] = {};
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const int idx = i0 + k * RR_THREADS + tid;
+            if (idx < total) {
+                const int nj = idx / W;
+                v[k] = a[(size_t)list[nj] * W + (idx - nj * W)];
+            }
+        }
+        // every load of the batch has returned before its first store leaves
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const int idx = i0 + k * RR_THREADS + tid;
+            if (idx < total) a[idx] = f(v[k]);
         }
     }
+}
+
+__device__ inline void reroot(const PuctTree& t, int c, int S, int16_t* map, int16_t* list) {
+    __shared__ int info[2];  // kept nodes, evaluated ones among them
+    const int tid = threadIdx.x, lane = lane_id();
+    PuctHdr* h = t.h;
+    const int n = h->n_nodes < S + 1 ? h->n_nodes : S + 1;
+    const int pend = h->pending;
+    if (tid < WAVE) {
+        int kept = 0, evals = 0;
+        for (int base = 0; base < n; base += WAVE) {
+            const int j = base + lane;
+            const bool in = j < n;
+            const int p = in ? t.parent[j] : -1;
+            const int sh = p >= base ? p - base : 0;  // the parent's lane when it is in this chunk
+            bool k = in && (j == c || (p >= 0 && p < base && map[p] >= 0));
+            uint64_t m = ballot(k);
+            while (true) {
+                k = k || (in && p >= base && ((m >> sh) & 1));
+                const uint64_t nm = ballot(k);
+                if (nm == m) break;
+                m = nm;
+            }
+            const int nj = kept + rank_in(m);
+            if (in) map[j] = k ? (int16_t)nj : (int16_t)-1;
+            if (k) list[nj] = (int16_t)j;
+            evals += __popcll(ballot(k && j != pend && t.term[j] == 0));
+            kept += __popcll(m);
+            __threadfence_block();  // this wave's map is written before the next chunk reads it
+        }
+        if (lane == 0) {
+            info[0] = kept;
+            info[1] = evals;
+        }
+    }
+    __syncthreads();
+    const int kept = info[0], evals = info[1];
+    for (int nb = 0; nb < kept; nb += RR_THREADS) {  // the scalars, one node per thread
+        const int nj = nb + tid;
+        const bool in = nj < kept;
+        double w = 0.0;
+        float va = 0.0f;
+        int vi = 0, pa = 0;
+        uint8_t mo = 0, te = 0;
+        if (in) {
+            const int j = list[nj];
+            w = t.W[j];
+            vi = t.visits[j];
+            va = t.value[j];
+            pa = t.parent[j];
+            mo = t.move[j];
+            te = t.term[j];
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (in) {
+            t.W[nj] = w;
+            t.visits[nj] = vi;
+            t.value[nj] = va;
+            t.parent[nj] = nj == 0 ? (int16_t)-1 : map[pa];
+            t.move[nj] = nj == 0 ? (uint8_t)255 : mo;
+            t.term[nj] = te;
+        }
+    }
+    move_rows<uint32_t, 16, 4>(t.board, list, kept, [](uint32_t x) { return x; });
+    move_rows<double, GZ_CELLS, 8>(t.prior, list, kept, [](double x) { return x; });
+    move_rows<int16_t, GZ_CELLS, 8>(t.child, list, kept,
+                                    [map](int16_t x) { return x >= 0 ? map[x] : (int16_t)-1; });
+    __syncthreads();
+    if (tid < 16) ((uint32_t*)h)[tid] = t.board[tid];  // black[8], white[8]: the new root's board
+    if (tid == 0) {
+        h->n_moves += 1;
+        h->player = 3 - h->player;
+        h->over = t.term[0] != 0;
+        h->n_nodes = kept;
+        h->n_evals = evals;
+        h->main_draws = 0;
+        h->pending = pend >= 0 ? map[pend] : -1;
+        h->move = -1;
+    }
+    __syncthreads();
+}
+
+// gz_puct_reroot: the step API's move between two searches
+__global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n, int S, const int32_t* moves,
+                                                                 uint32_t* leaves, int32_t* active,
+                                                                 int32_t* remaining) {
+    extern __shared__ __attribute__((aligned(16))) int16_t remap[];
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    const BB E = empties(black, white);
+    const int m = moves[g];
+    const bool play = m >= 0 && m < GZ_CELLS && !h->over && bb_test(E, cell_to_bit(m));
+    int c = play ? t.child[m] : -1;
+    if (c >= h->n_nodes) c = -1;
+    __syncthreads();  // (every thread has read the header before any of it changes)
+    if (c > 0) reroot(t, c, S, remap, remap + S + 1);
+    if (threadIdx.x >= WAVE) return;
+    bool live = false;
+    if (play && c <= 0) {
+        // no node under the move: a fresh root that waits for its evaluation
+        const int bit = cell_to_bit(m), mover = h->player, cnt = h->n_moves + 1;
+        const bool win = bb_test(threats(mover == 1 ? black : white).win, bit);
+        const bool over = win || bb_count(E) == 1 || cnt >= GZ_MAX_GAME_PLIES;
+        if (mover == 1) bb_set(black, bit);
+        else bb_set(white, bit);
+        const int64_t gid = h->game_id;
+        const int32_t reuse = h->reuse;
+        begin_root(t, black, white, gid, cnt, 3 - mover, over, reuse);
+        live = !over;
+        __threadfence_block();
+    }
+    write_leaf(leaves, active, g, black, white, live);
+    if (remaining && threadIdx.x == 0) remaining[g] = h->over ? 0 : S + 1 - t.visits[0];
+}
+
+// a tree of gz_selfplay_puct_rounds whose root is the slot's game and position
+__device__ inline bool tree_matches(const PuctHdr* h, const SlotHeader* sh) {
+    const int lane = lane_id();
+    bool ne = false;
+    if (lane < 16) ne = ((const uint32_t*)h)[lane] != ((const uint32_t*)sh)[lane];  // black[8], white[8] in both
+    return ballot(ne) == 0 && h->reuse == REUSE_MAGIC && h->game_id == sh->game_id && h->n_moves == sh->n_moves;
+}
+
+__device__ inline const SlotHeader* slot_of(const char* slots, int s) {
+    return (const SlotHeader*)(slots + (size_t)s * slot_stride_bytes());
+}
+
+// Round step 1: a slot whose search is at its budget picks its move (wave 0), stashes
+// the visit row of the ply and hands move and statistics to selfplay_commit_kernel
+// (move -1 leaves the slot alone); then the workgroup re-roots the tree under the move,
+// unless the move ends the game -- the tree of a move that ends it no longer matches
+// its slot after the commit, and puct_round_kernel begins a fresh one.
+__global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* slots, int n, gz_puct_params p,
+                                                                  char* ws, int32_t* moves, gz_search_stats* stats,
+                                                                  uint16_t* pend) {
+    extern __shared__ __attribute__((aligned(16))) int16_t remap[];
+    __shared__ int next_root;
+    const int s = blockIdx.x;
+    if (s >= n) return;
+    const int S = p.num_simulations;
+    PuctTree t = tree_of(ws, s, S);
+    PuctHdr* h = t.h;
+    if (threadIdx.x < WAVE) {
+        const int lane = lane_id();
+        const SlotHeader* sh = slot_of(slots, s);
+        const bool due = sh->game_id < sh->game_id_end && tree_matches(h, sh) && !h->over && h->pending < 0 &&
+                         t.visits[0] == S + 1 && h->n_moves >= 0 && h->n_moves < GZ_MAX_GAME_PLIES;
+        int mv = -1, c = -1;
+        if (due) {
+            PuctCfg cfg;
+            cfg.c_puct = p.c_puct;
+            cfg.seed = p.seed;
+            cfg.temp_plies = p.temp_plies;
+            cfg.S = S;
+            BB black, white;
+            load_bb(black, h->black);
+            load_bb(white, h->white);
+            int v[4], draws;
+            const long long total = root_visits(t, false, v);
+            mv = pick_move(h, cfg, empties(black, white), v, total, draws);
+            uint16_t* row = pend + ((size_t)s * GZ_MAX_GAME_PLIES + h->n_moves) * GZ_CELLS;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (lane + WAVE * k < GZ_CELLS) row[lane + WAVE * k] = (uint16_t)v[k];
+            if (mv >= 0 && mv < GZ_CELLS) {
+                c = t.child[mv];
+                if (c <= 0 || c >= h->n_nodes || c > S || t.term[c]) c = -1;
+            }
+            if (lane == 0) {
+                // (the third statistic, RNG draws of the simulations elsewhere: the rounds the move took)
+                stats[s] = search_stats(h->n_nodes, h->new_evals, draws, h->rounds);
+                h->move = mv;
+                h->main_draws = draws;
+                h->new_evals = 0;
+                h->rounds = 0;
+            }
+        }
+        if (lane == 0) {
+            moves[s] = mv;
+            next_root = c;
+        }
+    }
+    __syncthreads();
+    if (next_root > 0) reroot(t, next_root, S, remap, remap + S + 1);
+}
+
+// Round step 3: a tree that is not the slot's (a new game, a reset, a move that ended
+// the game) gives way to a fresh root, whose board is its leaf of this round; every
+// other slot descends once.
+__global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int n, gz_puct_params p, char* ws,
+                                                          uint32_t* leaves, int32_t* active) {
+    const int s = blockIdx.x;
+    if (s >= n) return;
+    const int S = p.num_simulations;
+    const SlotHeader* sh = slot_of(slots, s);
+    PuctTree t = tree_of(ws, s, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, sh->black);
+    load_bb(white, sh->white);
+    if (sh->game_id >= sh->game_id_end) {  // idle: its games are done
+        write_leaf(leaves, active, s, black, white, false);
+        return;
+    }
+    const int rounds = h->reuse == REUSE_MAGIC ? h->rounds : 0;
+    if (tree_matches(h, sh)) {
+        descend(t, p.c_puct, S, s, leaves, active);
+    } else {
+        begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC);
+        write_leaf(leaves, active, s, black, white, true);
+    }
+    if (lane_id() == 0) h->rounds = rounds + 1;
+}
+
+__global__ void puct_reset_kernel(char* ws, int n, int S) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    PuctHdr* h = tree_of(ws, g, S).h;
+    h->reuse = 0;
+    h->n_nodes = 0;
+    h->pending = -1;
+    h->move = -1;
 }
 
 // ---------------------------------------------------------------- export
@@ -457,6 +789,9 @@ struct RoundBufs {
     double* prior;
     void* pvws;
 };
+
+// reroot()'s LDS: map and list, int16 [S+1] each
+size_t remap_bytes(int32_t S) { return (4 * ((size_t)S + 1) + 15) & ~(size_t)15; }
 
 size_t rounds_offset(int32_t n, int32_t S) { return 256 + (size_t)n * game_stride_for(S); }
 
@@ -660,6 +995,60 @@ int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p
         if (rc) return rc;
         rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
                                          d_visits, stream);
+        if (rc) return rc;
+    }
+    return GZ_OK;
+}
+
+int gz_puct_reroot(void* d_workspace, int32_t n, int32_t S, const int32_t* d_moves, uint32_t* d_leaves,
+                   int32_t* d_active, int32_t* d_remaining, void* stream) {
+    int rc = check_S("gz_puct_reroot", n, S);
+    if (rc) return rc;
+    if (n > 0 && (!d_workspace || !d_moves || !d_leaves || !d_active))
+        return gz_fail(GZ_ERR_ARG, "gz_puct_reroot: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_reroot_kernel<<<n, RR_THREADS, remap_bytes(S), as_stream(stream)>>>((char*)d_workspace, n, S, d_moves, d_leaves,
+                                                                      d_active, d_remaining);
+    return gz_check_launch("puct_reroot_kernel");
+}
+
+int gz_selfplay_puct_reset(void* d_workspace, int32_t n_slots, int32_t S, void* stream) {
+    int rc = check_S("gz_selfplay_puct_reset", n_slots, S);
+    if (rc) return rc;
+    if (!d_workspace || n_slots <= 0) return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_reset: bad arguments");
+    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
+    puct_reset_kernel<<<(n_slots + 255) / 256, 256, 0, as_stream(stream)>>>((char*)w.puct, n_slots, S);
+    return gz_check_launch("puct_reset_kernel");
+}
+
+int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
+                            void* d_workspace, int32_t n_rounds, gz_record* d_records, int32_t record_cap,
+                            uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
+    int rc = check_search_args("gz_selfplay_puct_rounds", p, n_slots);
+    if (rc) return rc;
+    if (!d_slots || n_slots <= 0 || n_rounds < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
+        !d_pv_weights || !d_visits)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_rounds: bad arguments");
+    const int S = p->num_simulations;
+    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
+    const RoundBufs r = carve_rounds(w.puct, n_slots, S);
+    hipStream_t st = as_stream(stream);
+    for (int it = 0; it < n_rounds; it++) {
+        puct_advance_kernel<<<n_slots, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n_slots, *p, (char*)w.puct, w.moves,
+                                                      w.stats, w.pend);
+        rc = gz_check_launch("puct_advance_kernel");
+        if (rc) return rc;
+        rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
+                                         d_visits, stream);
+        if (rc) return rc;
+        puct_round_kernel<<<n_slots, WAVE, 0, st>>>((const char*)d_slots, n_slots, *p, (char*)w.puct,
+                                                                r.leaves, r.active);
+        rc = gz_check_launch("puct_round_kernel");
+        if (rc) return rc;
+        rc = gz_pv_forward(d_pv_weights, r.leaves, n_slots, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
+                           p->precision, stream);
+        if (rc) return rc;
+        rc = gz_puct_backup(w.puct, n_slots, S, r.prior, r.value, stream);
         if (rc) return rc;
     }
     return GZ_OK;

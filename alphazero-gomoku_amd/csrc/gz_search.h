@@ -1,6 +1,6 @@
 // gz_search.h -- device pieces shared by the search kernels (gz_selfplay.hip,
-// gz_plan.hip): the SoA tree, wave helpers, the pattern-score grid, the leaf
-// sink and MCTSNode.ucb1.
+// gz_plan.hip, gz_puct.hip): the SoA tree, wave helpers, the pattern-score grid, the
+// leaf sink, MCTSNode.ucb1 and the self-play slot header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -211,6 +211,33 @@ __device__ inline void load_bb(BB& x, const uint32_t* src) {
 __device__ inline void store_bb(uint32_t* dst, const BB& x) {
 #pragma unroll
     for (int i = 0; i < GZ_W; i++) dst[i] = x.w[i];
+}
+
+// ---------------------------------------------------------------- self-play slots
+// A slot of the self-play engines (gz_selfplay.hip; gz_puct.hip reads the header to
+// follow a slot's game): the header, then the records of the game in progress.
+struct SlotHeader {  // 128 bytes
+    uint32_t black[8];
+    uint32_t white[8];
+    int64_t game_id;
+    int64_t game_id_stride;
+    int32_t n_moves;
+    int32_t player;
+    int64_t game_id_end;  // the slot is idle once game_id >= game_id_end (no new game starts)
+    int64_t games_done;
+    // totals over every search this slot ran since init: predict() calls and RNG
+    // draws (main stream, simulation streams).  The checker compares them with the
+    // oracle's per-ply counts (gz_selfplay_draws): they see the rollout and planner
+    // decisions a game's moves hide
+    int64_t predicts;
+    int64_t main_draws;
+    int64_t sim_draws;
+};
+static_assert(sizeof(SlotHeader) == 128, "slot header");
+
+__host__ __device__ inline size_t slot_stride_bytes() {
+    size_t b = sizeof(SlotHeader) + (size_t)GZ_MAX_GAME_PLIES * sizeof(gz_record);
+    return (b + 255) & ~(size_t)255;
 }
 
 }  // namespace gz

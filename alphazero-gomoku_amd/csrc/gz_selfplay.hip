@@ -481,30 +481,6 @@ __global__ __launch_bounds__(WAVE, 4) void search_kernel(const gz_board_state* b
     }
 }
 
-struct SlotHeader {  // 128 bytes
-    uint32_t black[8];
-    uint32_t white[8];
-    int64_t game_id;
-    int64_t game_id_stride;
-    int32_t n_moves;
-    int32_t player;
-    int64_t game_id_end;  // the slot is idle once game_id >= game_id_end (no new game starts)
-    int64_t games_done;
-    // totals over every search this slot ran since init: predict() calls and RNG
-    // draws (main stream, simulation streams).  The checker compares them with the
-    // oracle's per-ply counts (gz_selfplay_draws): they see the rollout and planner
-    // decisions a game's moves hide
-    int64_t predicts;
-    int64_t main_draws;
-    int64_t sim_draws;
-};
-static_assert(sizeof(SlotHeader) == 128, "slot header");
-
-__host__ __device__ inline size_t slot_stride_bytes() {
-    size_t b = sizeof(SlotHeader) + (size_t)GZ_MAX_GAME_PLIES * sizeof(gz_record);
-    return (b + 255) & ~(size_t)255;
-}
-
 __global__ void selfplay_init_kernel(char* slots, int n_slots, int64_t base, int64_t stride) {
     int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_slots) return;

@@ -172,6 +172,10 @@ SIGNATURES = {
     "gz_selfplay_puct_workspace_bytes": (_SZ, [_I32, _I32]),
     "gz_selfplay_puct_run": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32, _P, _P,
                                             _P]),
+    "gz_puct_reroot": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "gz_selfplay_puct_reset": (ctypes.c_int, [_P, _I32, _I32, _P]),
+    "gz_selfplay_puct_rounds": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32, _P,
+                                               _P, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
     "gz_dataset_gather": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P]),

@@ -435,6 +435,22 @@ class PuctStepper:
         torch.cuda.synchronize()
         return d_moves.cpu().numpy(), d_visits.cpu().numpy().reshape(self.n, 225), d_q.cpu().numpy()
 
+    def reroot(self, moves):
+        """Play moves[g] (row-major cell, -1: leave the game as it is) at every root and
+        keep the subtree under it as the next search's tree (gz_puct_reroot).  Returns
+        the simulations left to each game's budget, int32 [n] (0: the game is over).
+        The next search is then: while any game has simulations left, select(),
+        leaves(), backup() -- a game at its budget has an inactive row.  A move
+        without a node gives a fresh root whose board is in leaves() right away: back
+        it up before the first select()."""
+        d_moves = torch.as_tensor(np.asarray(moves, np.int32).reshape(-1)).cuda()
+        if d_moves.numel() != self.n:
+            raise ValueError("reroot() wants one move per game")
+        d_rem = torch.zeros(self.n, dtype=torch.int32, device="cuda")
+        _lib.check(self.lib.gz_puct_reroot(ptr(self.ws), self.n, self.S, ptr(d_moves), ptr(self.d_leaves),
+                                           ptr(self.d_active), ptr(d_rem), stream()), "gz_puct_reroot")
+        return d_rem.cpu().numpy()
+
     def trees(self):
         torch.cuda.synchronize()
         return _puct_trees(self.lib, self.ws, self.n, self.S)

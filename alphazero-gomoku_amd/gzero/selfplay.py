@@ -27,7 +27,8 @@ class SelfPlayEngine:
     def __init__(self, n_slots=4096, num_simulations=200, c_puct=1.6, exploration=0.05, beta=0.2,
                  seed=0, max_depth=100, pv_weights=None, plies_per_step=1, game_id_base=0,
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
-                 pv_mode="full", game_id_end=None, search="reference", temp_plies=12):
+                 pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
+                 rounds_per_step=None):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -36,6 +37,14 @@ class SelfPlayEngine:
         precision is the forward's) and planner_steps == 0, and ignores beta,
         exploration, max_depth and pv_mode.  Every record then has a visit row
         (:meth:`visits`), the policy target; records["move"] is still the move played.
+        tree_reuse (search="puct" only): the subtree under the move played is the next
+        ply's tree and every slot keeps its own clock (gz_selfplay_puct_rounds): a
+        search ends when its root has num_simulations + 1 visits, so a root that
+        inherits v visits plays after num_simulations + 1 - v rounds, and every round is
+        one forward in which every live slot has a leaf.  :meth:`step` then runs
+        rounds_per_step rounds (default num_simulations + 1, the rounds of one lock-step
+        ply), so the moves per step vary; a game's moves and visit rows do not depend on
+        the slot count or on rounds_per_step.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -49,6 +58,9 @@ class SelfPlayEngine:
         if search not in ("reference", "puct"):
             raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
         self.search = search
+        self.tree_reuse = bool(tree_reuse)
+        if self.tree_reuse and search != "puct":
+            raise ValueError("tree_reuse needs search='puct'")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -82,8 +94,13 @@ class SelfPlayEngine:
         S = self.params.num_simulations
         slot_bytes = self.lib.gz_slot_bytes(S)
         self.d_slots = torch.zeros(self.n_slots * slot_bytes, dtype=torch.uint8, device="cuda")
-        # a slot can finish one 200-ply game plus any games played inside a step
-        self.record_cap = self.n_slots * (_lib.GZ_MAX_GAME_PLIES + self.plies_per_step)
+        self.rounds_per_step = (S + 1 if rounds_per_step is None else int(rounds_per_step)) if self.tree_reuse else 0
+        if self.tree_reuse and self.rounds_per_step < 1:
+            raise ValueError("rounds_per_step must be at least 1")
+        # a slot can finish one 200-ply game plus any games played inside a step (with
+        # tree reuse: at most 199 earlier plies plus one per round)
+        self.record_cap = self.n_slots * (_lib.GZ_MAX_GAME_PLIES +
+                                          (self.rounds_per_step if self.tree_reuse else self.plies_per_step))
         self.d_records = torch.zeros(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self.d_counters = torch.zeros(COUNTER_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self.puct = self.d_puct_ws = self.d_visits = None
@@ -94,6 +111,8 @@ class SelfPlayEngine:
             # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
             # has no uint16 arithmetic; a count is at most GZ_MAX_SIMULATIONS)
             self.d_visits = torch.zeros(self.record_cap * 225, dtype=torch.int16, device="cuda")
+            if self.tree_reuse:
+                self._puct_reset()
         self.leaf_cap = self.n_slots * self.plies_per_step * (S + 1) if self.gather else 0
         if self.gather:
             self.d_leaves = torch.zeros(self.leaf_cap * 16, dtype=torch.int32, device="cuda")
@@ -146,6 +165,10 @@ class SelfPlayEngine:
         self.d_counters.zero_()
         if self.n_active == 0:  # every game is done
             return
+        if self.tree_reuse:
+            # n_plies counts steps of rounds_per_step rounds here
+            self._puct_rounds(self.rounds_per_step * (1 if n_plies is None else int(n_plies)))
+            return
         if self.search == "puct":
             self._puct_run(self.puct, n)
             return
@@ -166,6 +189,16 @@ class SelfPlayEngine:
                                                  ptr(self.pv_weights.tensor), ptr(self.d_puct_ws), int(n_plies),
                                                  ptr(self.d_records), self.record_cap, ptr(self.d_visits),
                                                  ptr(self.d_counters), stream()), "gz_selfplay_puct_run")
+
+    def _puct_rounds(self, n_rounds):
+        _lib.check(self.lib.gz_selfplay_puct_rounds(ptr(self.d_slots), self.n_slots, ctypes.byref(self.puct),
+                                                    ptr(self.pv_weights.tensor), ptr(self.d_puct_ws), int(n_rounds),
+                                                    ptr(self.d_records), self.record_cap, ptr(self.d_visits),
+                                                    ptr(self.d_counters), stream()), "gz_selfplay_puct_rounds")
+
+    def _puct_reset(self):
+        _lib.check(self.lib.gz_selfplay_puct_reset(ptr(self.d_puct_ws), self.n_slots, self.puct.num_simulations,
+                                                   stream()), "gz_selfplay_puct_reset")
 
     def gn_stats(self, reset=False, check=None):
         """Planner-net rows since the last reset: {"full", "incremental", "checked",
@@ -193,13 +226,17 @@ class SelfPlayEngine:
         planner plies (the planner pipeline needs the GN forward per ply): the slots
         reach a steady-state mix of positions, and the measured plies are planner plies.
         On a PUCT engine the burn-in plies are PUCT plies at 8 simulations (every ply
-        needs its visit row), in the engine's own workspace."""
+        needs its visit row), in the engine's own workspace; with tree_reuse they are
+        lock-step plies too, and the trees are reset afterwards (the next round begins
+        every slot with a fresh root)."""
         if self.search == "puct":
             p = _lib.PuctParams.from_buffer_copy(self.puct)
             p.num_simulations = min(8, p.num_simulations)
             for _ in range(int(n_plies)):
                 self.d_counters.zero_()
                 self._puct_run(p, 1)
+            if self.tree_reuse:
+                self._puct_reset()
             return
         p = _lib.SearchParams.from_buffer_copy(self.params)
         p.flags = 0

@@ -245,7 +245,7 @@ def _check_search(search, model, planner_steps) -> bool:
 
 def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: str = "medium", seed: int = 0,
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
-                         plies_per_step: int = 4):
+                         plies_per_step: int = 4, tree_reuse: bool = False):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -254,6 +254,9 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     reads the engine's counters together with the number of wanted games that finished
     in the step (counted on the device over the record buffer).  At the end the rows
     are sorted by (game id, ply), the visit rows following.
+    tree_reuse: the engine keeps the subtree under each move played and runs every slot
+    on its own clock (SelfPlayEngine(tree_reuse=True)); a step is then plies_per_step x
+    (num_simulations + 1) rounds, in which a slot plays at least plies_per_step moves.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -261,7 +264,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     slots = min(n_slots, n_games)
     eng = SelfPlayEngine(n_slots=slots, num_simulations=num_simulations, c_puct=c_puct, seed=seed,
                          pv_weights=model.device_weights(), plies_per_step=plies_per_step,
-                         game_id_base=game_id_base, search="puct", temp_plies=temp_plies)
+                         game_id_base=game_id_base, search="puct", temp_plies=temp_plies, tree_reuse=tree_reuse,
+                         rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -274,6 +278,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     rvis = eng.d_visits.view(eng.record_cap, 225)
     slot_idx = torch.arange(eng.record_cap, device="cuda")
     games = moves = steps = 0
+    # (with tree reuse a move takes at most num_simulations + 1 rounds, so a step of
+    # plies_per_step x that many rounds plays at least plies_per_step moves: the same bound)
     max_steps = (-(-n_games // slots) + 1) * 200 // eng.plies_per_step + 8
     t0 = time.time()
     while games < n_games:
@@ -567,7 +573,8 @@ def _fmt_duration(seconds: float) -> str:
 def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_simulations: int = 200,
                   difficulty: str = "medium", beta: float = 0.2, planner_steps: int = 5, seed: int = 0,
                   train_split: float = 0.9, batch_size: int = 128, epochs: int = 2, augment_ratio: float = 0.35,
-                  planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8) -> dict:
+                  planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8,
+                  tree_reuse: bool = False) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -578,7 +585,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     model (selfplay_puct_device; beta, planner_steps and planner are not used) and the
     network trains on the root visit distributions (DeviceDataset(..., visits=...), the
     soft-target loss) instead of the moves played.  One rank only: the record exchange
-    does not carry visit rows yet."""
+    does not carry visit rows yet.  ``tree_reuse`` (search="puct"): self-play keeps the
+    subtree under each move for the next ply (selfplay_puct_device)."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     rank, ws = gdist.world()
@@ -586,6 +594,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
     if search == "puct" and ws > 1:
         raise NotImplementedError("search='puct' collects on one rank only: RecordExchange does not carry visit rows")
+    if tree_reuse and search != "puct":
+        raise ValueError("tree_reuse needs search='puct'")
     t0 = time.time()
     id_lo = it * ws * games_per_iteration
     replay_base = id_lo + rank * games_per_iteration
@@ -593,7 +603,7 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     if search == "puct":
         d, d_vis, n_rec, st = selfplay_puct_device(games_per_iteration, num_simulations=num_simulations,
                                                    difficulty=difficulty, seed=seed, game_id_base=replay_base,
-                                                   model=model, temp_plies=temp_plies)
+                                                   model=model, temp_plies=temp_plies, tree_reuse=tree_reuse)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order

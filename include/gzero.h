@@ -357,6 +357,37 @@ size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t num_simulations
 int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                          void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
                          uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);
+/* Tree reuse between plies (opt-in; the entry points above are unchanged).  A search
+ * is finished when its root has S+1 visits.  After the move m the subtree of the root's
+ * child at m is the next ply's tree: its nodes keep their creation order and are
+ * renumbered densely, in place; W, visits, prior, value, board and term are carried bit
+ * for bit, the new root has parent -1 and move 255, the header's position advances by
+ * m.  A root that arrives with v visits needs S+1-v more simulations (at least one).
+ * gz_puct_reroot (step API), per game: d_moves[g] = -1 leaves the tree untouched; a
+ * move with a child re-roots (a terminal child: the game is over); a move without one
+ * gives a fresh one-node root that waits for its evaluation, its board in leaf row g
+ * with d_active[g] = 1 (every other case: an empty, inactive row).  d_remaining
+ * (optional) int32 [n]: simulations left to the budget, 0 when the game is over.  On a
+ * game at its budget gz_puct_select gives an inactive row, so games that inherit
+ * different visit counts can share the rounds until the last is done. */
+int gz_puct_reroot(void* d_workspace, int32_t n, int32_t num_simulations, const int32_t* d_moves,
+                   uint32_t* d_leaves, int32_t* d_active, int32_t* d_remaining, void* stream);
+/* Self-play with reuse, every slot on its own clock: n_rounds rounds of (slots at
+ * their budget pick and play their move, every slot re-roots / begins a fresh root as
+ * needed and descends once, one forward over the n_slots leaf rows, backup), with no
+ * host synchronisation and no copy to the host.  Every live slot has one leaf in every
+ * forward; a move takes S+1-v rounds.  Records, visit rows (each sums to S), counters
+ * as gz_selfplay_puct_run; slot statistics (gz_selfplay_draws), added when a move is
+ * played: the rounds in which the slot's leaf was evaluated, main draws, the rounds the
+ * move took (S+1 for a fresh root, S+1-v for an inherited one); a game's moves depend only on
+ * (seed, game id, weights, params), not on the slots or on how rounds are cut into
+ * calls.  Same workspace as gz_selfplay_puct_run.  gz_selfplay_puct_reset marks every
+ * tree invalid: required before the first round and after anything else used the
+ * workspace (a tree is reused only while its root is the slot's game id and position). */
+int gz_selfplay_puct_reset(void* d_workspace, int32_t n_slots, int32_t num_simulations, void* stream);
+int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
+                            void* d_workspace, int32_t n_rounds, gz_record* d_records, int32_t record_cap,
+                            uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);
 
 /* BGPlannerAI.get_move (bg_planner.py:232-269) for each board: d_ai = the
  * planner's colour P, d_keys = RNG stream; d_moves (-1 = None), d_draws.

@@ -11,6 +11,22 @@ build of another commit, e.g. the parent's) if given: (S+1) x that time is what 
 forwards alone cost, the rest of a step is the search kernels and launch gaps.
 
     python tools/puct_bench.py --out profiles/puct/bench.json
+
+--reuse measures tree reuse between plies (SelfPlayEngine(tree_reuse=True)) instead:
+after the burn-in and a warm-up of 4 x (S+1) rounds (the slots' clocks drift apart),
+three windows of 2 x (S+1) rounds are timed with device events: ms per round, the moves
+played in the window, mean rounds per move (the rounds those moves took, from the slot
+statistics; slots that stay in phase play a whole number of moves per window, so slots
+x rounds / moves is quantised) and moves/s = slots / (rounds per move x ms per round).  The
+lock-step step is timed in the same call, alternating with the windows, in a child
+process (its own engine, same slots, simulations, burn-in and weights) that loads
+--lockstep-library (GZ_LIBRARY: a build of the parent commit) if given.  The init
+weights give a nearly flat prior, so runs with the policy FC scaled by
+--policy-scale are added: a synthetic, sharper prior that shows how the reuse depends on
+how peaked the search is -- not a trained network.
+
+    python tools/puct_bench.py --reuse --lockstep-library parent/libgzero.so \\
+        --out profiles/puct/reuse_bench.json
 """
 import argparse
 import json
@@ -31,6 +47,12 @@ ap.add_argument("--temp-plies", type=int, default=12)
 ap.add_argument("--forward-library", default=None, help="libgzero.so the standalone forward is timed on")
 ap.add_argument("--forward-only", action="store_true", help="(child) time gz_pv_forward alone, print JSON")
 ap.add_argument("--note", default=None, help="free text stored in the result's config (e.g. which build --forward-library is)")
+ap.add_argument("--reuse", action="store_true", help="measure tree reuse between plies (see above)")
+ap.add_argument("--policy-scale", default="32,128",
+                help="--reuse: the policy FC's weight and bias times this in the synthetic runs (comma-separated)")
+ap.add_argument("--lockstep-library", default=None, help="--reuse: libgzero.so the lock-step child loads")
+ap.add_argument("--lockstep-child", type=float, default=None, metavar="SCALE",
+                help="(child) time lock-step steps on request, policy FC scaled by SCALE")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 precisions = a.precisions.split(",")
@@ -70,8 +92,145 @@ def forward_only():
     print("FORWARD_JSON " + json.dumps(out))
 
 
+def bench_weights(prec, scale):
+    from gzero import device, weights
+    sd = weights.init_state_dict(0)
+    if scale != 1.0:
+        sd["policy_fc.weight"] = sd["policy_fc.weight"] * scale
+        sd["policy_fc.bias"] = sd["policy_fc.bias"] * scale
+    return device.PVWeights(weights.pack_pv_weights(sd), precision=prec)
+
+
+def lockstep_child():
+    """Per line on stdin: one lock-step step timed with device events, its ms on stdout."""
+    import ctypes
+    import torch
+    from gzero import _lib
+    from gzero.selfplay import SelfPlayEngine
+    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build lacks the newer entry points
+    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    eng = SelfPlayEngine(n_slots=a.slots, num_simulations=a.sims, seed=1,
+                         pv_weights=bench_weights(precisions[0], a.lockstep_child), search="puct",
+                         temp_plies=a.temp_plies)
+    eng.advance(a.burn)
+    eng.step()
+    torch.cuda.synchronize()
+    print("READY", flush=True)
+    for line in sys.stdin:
+        if line.strip() != "step":
+            break
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.step()
+        e1.record()
+        torch.cuda.synchronize()
+        assert eng.counters()["moves"] == a.slots
+        print(f"STEP_MS {e0.elapsed_time(e1)!r}", flush=True)
+
+
+def reuse_run(prec, scale):
+    """One run: the lock-step child (started first; it idles between its steps), then
+    the reuse engine; windows and steps alternate."""
+    env = dict(os.environ)
+    if a.lockstep_library:
+        env["GZ_LIBRARY"] = os.path.abspath(a.lockstep_library)
+    child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--lockstep-child", repr(scale), "--slots",
+                              str(a.slots), "--sims", str(a.sims), "--burn", str(a.burn), "--precisions", prec,
+                              "--temp-plies", str(a.temp_plies)], env=env, stdin=subprocess.PIPE,
+                             stdout=subprocess.PIPE, text=True)
+    try:
+        if child.stdout.readline().strip() != "READY":
+            sys.exit(f"lock-step child failed ({child.poll()})")
+        import torch
+        from gzero.selfplay import SelfPlayEngine
+        S, n = a.sims, a.slots
+        window = 2 * (S + 1)
+        eng = SelfPlayEngine(n_slots=n, num_simulations=S, seed=1, pv_weights=bench_weights(prec, scale), search="puct",
+                             temp_plies=a.temp_plies, tree_reuse=True, rounds_per_step=window)
+        eng.advance(a.burn)
+        eng.step()
+        eng.step()  # warm-up: 4 x (S+1) rounds
+        torch.cuda.synchronize()
+        took0 = int(eng.draws()[:, 2].sum())  # rounds the moves played so far took
+        wins, steps = [], []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng.step()
+            e1.record()
+            torch.cuda.synchronize()
+            c = eng.counters()
+            assert c["records_dropped"] == 0
+            wins.append({"ms": e0.elapsed_time(e1), "moves": int(c["moves"]), "games": int(c["games"])})
+            child.stdin.write("step\n")
+            child.stdin.flush()
+            line = child.stdout.readline().split()
+            if len(line) != 2 or line[0] != "STEP_MS":
+                sys.exit(f"lock-step child failed ({child.poll()}): {line}")
+            steps.append(float(line[1]))
+        took = int(eng.draws()[:, 2].sum()) - took0
+    finally:
+        child.stdin.close()
+        child.wait(timeout=120)
+    round_ms = [w["ms"] / window for w in wins]
+    moves = sum(w["moves"] for w in wins)
+    ms = sum(w["ms"] for w in wins)
+    # the moves played in the windows and the rounds each of them took (S+1 minus the visits
+    # its root inherited), from the slot statistics: slots that stay in phase play a whole
+    # number of moves per window, which would quantise slots x rounds / moves
+    rpm = took / moves
+    rate = n / (rpm * median(round_ms) / 1e3)
+    lock_round = median(steps) / (S + 1)
+    out = {
+        "policy_fc_scale": scale, "rounds_per_window": window, "windows": wins,
+        "round_ms_median": median(round_ms), "round_ms": round_ms,
+        "mean_rounds_per_move": rpm, "mean_rounds_per_move_source": "rounds taken by the moves played in the "
+        "windows (slot statistics) / those moves", "slot_rounds_per_window_move": n * window * len(wins) / moves,
+        "moves_per_s": rate, "moves_per_s_source": "slots / (mean rounds per move x median ms per round)",
+        "moves_per_s_counted_in_windows": moves / (ms / 1e3),
+        "lockstep": {"step_ms": steps, "step_ms_median": median(steps), "round_ms": lock_round,
+                     "rounds_per_move": S + 1, "moves_per_s": n / (median(steps) / 1e3)},
+        "round_ms_over_lockstep_round_ms": median(round_ms) / lock_round,
+        "measured_speedup_rounds": (S + 1) / rpm,
+        "measured_speedup_moves_per_s": rate / (n / (median(steps) / 1e3)),
+    }
+    print(f"{prec} policy x{scale:g}: round {median(round_ms):.3f} ms (lock-step {lock_round:.3f} ms, "
+          f"x{out['round_ms_over_lockstep_round_ms']:.4f}), {rpm:.1f} rounds per move (lock-step {S + 1}), "
+          f"{out['moves_per_s']:.0f} moves/s (lock-step {out['lockstep']['moves_per_s']:.0f})")
+    del eng
+    torch.cuda.empty_cache()
+    return out
+
+
 if a.forward_only:
     forward_only()
+    sys.exit(0)
+if a.lockstep_child is not None:
+    lockstep_child()
+    sys.exit(0)
+if a.reuse:
+    prec = precisions[0]
+    res = {"config": {"slots": a.slots, "simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies,
+                      "precision": prec, "warm_up_rounds": 4 * (a.sims + 1),
+                      "timing": "device events around windows of 2 x (S+1) rounds; lock-step steps of a child "
+                                "process alternate with the windows",
+                      "lockstep_library": "another build (--lockstep-library)" if a.lockstep_library else "this build",
+                      "speedup": "measured (S+1) / mean rounds per move of this run; the scaled-policy run is "
+                                 "synthetic, no figure for a trained network is claimed"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    res["results"]["init_weights"] = reuse_run(prec, 1.0)
+    for scale in (float(x) for x in a.policy_scale.split(",") if x):
+        res["results"][f"policy_fc_x{scale:g}_synthetic"] = reuse_run(prec, scale)
+    import torch
+    res["device"] = torch.cuda.get_device_name(0)
+    print("PUCT_REUSE_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 
 # the child first, while this process has not opened the GPU
