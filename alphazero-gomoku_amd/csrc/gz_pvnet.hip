@@ -462,6 +462,18 @@ __device__ __forceinline__ void conv0_tile(Act& act, const float* __restrict__ W
     store_tiles(act, acc, W + C0_S, W + C0_T, (const f32x4*)nullptr, nt, lane);
 }
 
+// exp(d), d <= 0, of the softmax.  __expf flushes a result below float32's normal range
+// (d < -87.3) to 0, where the reference's np.exp (neural_network.py:248-252) keeps the
+// denormal: a board whose mass sits on an occupied cell 87 to 104 logits above the rest
+// then had an all-zero prior where the reference renormalises the empty cells' tiny
+// values (ai_agent.py:579).  A nonzero __expf is returned as it is, so every result in
+// the normal range is the bit pattern it was; a zero is redone 64 binades up and
+// scaled back down (44.36... = 64 ln 2), which gives the denormal or a true 0.
+__device__ __forceinline__ float softmax_exp(float d) {
+    const float e = __expf(d);
+    return e != 0.f ? e : __expf(d + 44.3614195558365f) * 0x1p-64f;
+}
+
 // heads (neural_network.py:132-159) + softmax (neural_network.py:240-247) for board b;
 // the tower's output map is in act.  Ends with a barrier.
 template <int NTH, class Act>
@@ -528,7 +540,7 @@ __device__ __forceinline__ void heads(const Act& act, const Smem& sm, const floa
     __syncthreads();
     if (wave < 4) {
         const float mx = fmaxf(fmaxf(sm.red[0], sm.red[1]), fmaxf(sm.red[2], sm.red[3]));
-        float e = tid < POS ? __expf(sm.lg[tid] - mx) : 0.f;
+        float e = tid < POS ? softmax_exp(sm.lg[tid] - mx) : 0.f;
         float s = wave_sum(e);
         if (lane == 0) sm.red[8 + wave] = s;
         if (tid < POS) {
@@ -894,7 +906,7 @@ __global__ __launch_bounds__(NTH_H, 2) void pv_heads_kernel(const float* __restr
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int o = lane + 64 * u;
-            e[u] = o < POS ? __expf(x[u] - mx) : 0.f;
+            e[u] = o < POS ? softmax_exp(x[u] - mx) : 0.f;
             sum += e[u];
         }
         sum = wave_sum(sum);

@@ -214,11 +214,14 @@ def pv_forward(weights, leaf_rows, want_prior=False):
     return out
 
 
-def pv_forward_tree(weights, leaf_rows, meta, root_cap=None):
+def pv_forward_tree(weights, leaf_rows, meta, root_cap=None, d_count=None):
     """Host convenience for gz_pv_forward_tree: [n,16] uint32 leaf rows and their
     int32 meta (-1 root, >= 0 the parent's index for a root child or a child of
     one, -2 other) ->
-    (logits [n,225], value [n], probs [n,225], prior [n,225], list sizes)."""
+    (logits [n,225], value [n], probs [n,225], prior [n,225], list sizes).
+    d_count (optional, an int): the count-on-device form -- only the first
+    min(d_count, n) rows are evaluated; the outputs start as NaN, so a row the
+    library did not write stays NaN."""
     lib = require_gpu()
     rows = np.ascontiguousarray(leaf_rows, np.uint32).reshape(-1, 16)
     n = rows.shape[0]
@@ -227,12 +230,16 @@ def pv_forward_tree(weights, leaf_rows, meta, root_cap=None):
         root_cap = int((meta == -1).sum())
     d_b = torch.from_numpy(rows.view(np.int32).copy()).cuda()
     d_m = torch.from_numpy(meta.copy()).cuda()
-    d_lg = torch.empty(n * 225, dtype=torch.float32, device="cuda")
-    d_v = torch.empty(n, dtype=torch.float32, device="cuda")
-    d_p = torch.empty(n * 225, dtype=torch.float32, device="cuda")
-    d_pr = torch.empty(n * 225, dtype=torch.float64, device="cuda")
+    new = torch.empty
+    if d_count is not None:
+        d_count = torch.tensor([int(d_count)], dtype=torch.int32, device="cuda")
+        new = lambda *a, **k: torch.full(*a, float("nan"), **k)  # noqa: E731
+    d_lg = new((n * 225,), dtype=torch.float32, device="cuda")
+    d_v = new((n,), dtype=torch.float32, device="cuda")
+    d_p = new((n * 225,), dtype=torch.float32, device="cuda")
+    d_pr = new((n * 225,), dtype=torch.float64, device="cuda")
     ws = torch.empty(lib.gz_pv_tree_workspace_bytes(n, root_cap), dtype=torch.uint8, device="cuda")
-    _lib.check(lib.gz_pv_forward_tree(ptr(weights.tensor), ptr(d_b), ptr(d_m), n, None, int(root_cap),
+    _lib.check(lib.gz_pv_forward_tree(ptr(weights.tensor), ptr(d_b), ptr(d_m), n, ptr(d_count), int(root_cap),
                                       ptr(d_lg), ptr(d_v), ptr(d_p), ptr(d_pr), ptr(ws), stream()),
                "gz_pv_forward_tree")
     st = torch.zeros(6, dtype=torch.int32, device="cuda")

@@ -92,9 +92,12 @@ typedef struct gz_search_stats {
 
 typedef struct gz_selfplay_counters {
     int32_t records;         /* records written to d_records */
-    int32_t leaves;          /* boards appended to d_leaves */
+    int32_t leaves;          /* boards the searches produced: the first min(leaves, leaf_cap) are
+                                in d_leaves, the counter goes on counting past leaf_cap */
     int32_t records_dropped; /* records lost because d_records was full */
-    int32_t leaves_dropped;
+    int32_t leaves_dropped;  /* never written (stays as the caller set it): a full leaf buffer
+                                shows as leaves > leaf_cap, and the leaves - leaf_cap rows past
+                                the end were dropped.  Do not add this field to that difference. */
     int64_t moves;           /* plies played */
     int64_t games;           /* games finished */
     int64_t mcts_moves;      /* plies decided by MCTS (n_moves >= 6; the opening plies
@@ -128,7 +131,11 @@ int gz_pattern_score(const gz_board_state* d_boards, const int32_t* d_player, in
  * One wavefront per board.  d_trees: n * gz_tree_bytes(num_simulations)
  * scratch holding each search tree (layout in DESIGN.md; readable by tests).
  * d_moves[i] = chosen cell or -1 (None).  Leaves are appended to d_leaves
- * ([leaf_cap][16] uint32: black[8], white[8]) when GZ_FLAG_GATHER_LEAVES. */
+ * ([leaf_cap][16] uint32: black[8], white[8]) when GZ_FLAG_GATHER_LEAVES.
+ * *d_leaf_count (the caller zeroes it) is advanced by every leaf produced, also
+ * past leaf_cap: rows at or past leaf_cap are not written, so a full buffer shows
+ * as *d_leaf_count > leaf_cap and the excess rows were dropped (no separate
+ * dropped-leaves count is kept: gz_selfplay_counters.leaves_dropped is never written). */
 size_t gz_tree_bytes(int32_t num_simulations);
 int gz_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n,
               const gz_search_params* p, void* d_trees, int32_t* d_moves, gz_search_stats* d_stats,

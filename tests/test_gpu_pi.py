@@ -226,9 +226,10 @@ def _check_vs_float64(out, fcs, pin, vin, pi, v, scale):
 
 
 @pytest.mark.parametrize("scale", [1.0, 0.25])
-@pytest.mark.parametrize("B", [1, 7, 17, 128])
+@pytest.mark.parametrize("B", [1, 7, 17, 128, 65, 130])
 def test_soft_loss_vs_float64(B, scale):
-    """17 boards are one more than the gemm's 16-row tile."""
+    """17 boards are one more than the gemm's 16-row tile; 65 and 130 are one and two
+    more than the 64 boards a wave's lanes take at a time, and 130 is above 128."""
     fcs, pin, vin, v = _fc_inputs(B)
     pi = _sparse_pi(B, SEED + 7 * B)
     assert float((pi.sum(1) - 1).abs().max()) < 1e-6
@@ -243,7 +244,7 @@ def test_unnormalised_rows_vs_float64(B):
     _check_vs_float64(_fc_loss(True, fcs, pin, vin, pi, v, 1.0), fcs, pin, vin, pi, v, 1.0)
 
 
-@pytest.mark.parametrize("B,scale", [(7, 0.25), (128, 1.0)])
+@pytest.mark.parametrize("B,scale", [(7, 0.25), (128, 1.0), (65, 1.0)])
 def test_one_hot_rows_equal_the_hard_path_bitwise(B, scale):
     fcs, pin, vin, v = _fc_inputs(B)
     y = torch.randint(0, 225, (B,), generator=torch.Generator().manual_seed(SEED + B))

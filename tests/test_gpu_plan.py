@@ -352,6 +352,7 @@ def test_config4_full_size_step_vs_oracle(oracle, gnw):
     gs = eng.gn_stats()
     c = eng.counters()
     assert c["records_dropped"] == 0 and c["leaves_dropped"] == 0 and c["moves"] == n_slots
+    assert c["leaves"] <= eng.leaf_cap
     assert gs["full"] + gs["incremental"] > n_slots * S  # round 0 alone: one row per rollout ply
     assert gs["checked"] == gs["full"] + gs["incremental"] and gs["mismatched"] == 0, gs
     st1, gid1 = eng.boards()

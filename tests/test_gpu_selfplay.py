@@ -74,7 +74,7 @@ def test_selfplay_leaf_count_equals_reference_predicts(oracle):
         c = eng.counters()
         assert c["moves"] == ref["n"] and c["games"] == 1
         assert c["leaves"] == ref["predicts"]
-        assert c["leaves_dropped"] == 0
+        assert c["leaves_dropped"] == 0 and c["leaves"] <= eng.leaf_cap  # (a full buffer shows as leaves > leaf_cap)
 
 
 def test_sharded_ranks_play_the_single_gpu_games():
@@ -129,6 +129,7 @@ def test_config2_200_sims_vs_oracle(oracle):
         eng.step()
         c = eng.counters()
         assert c["leaves_dropped"] == 0 and c["records_dropped"] == 0 and c["moves"] == n_slots
+        assert c["leaves"] <= eng.leaf_cap
         assert c["games"] == 0  # no game ends in 12 plies: the slots keep their ids
         leaves += int(c["leaves"])
     st, gids = eng.boards()

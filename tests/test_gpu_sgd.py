@@ -156,9 +156,13 @@ def _compare(B, seed, scale=1.0, loss_scale=1.0, gtol=1e-4):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("B", [128, 7, 1])
+@pytest.mark.parametrize("B", [128, 7, 1, 65, 130])
 def test_sgd_tower_vs_float64(B):
-    """Batch 128 (a training step), a 7-board remainder batch and a single board."""
+    """Batch 128 (a training step), a 7-board remainder batch and a single board; 65
+    and 130, a DataLoader's ragged last batch and the first batch above 128: the
+    weight-gradient kernel's min(B, 64) groups of ceil(B / groups) boards are then 32
+    of two boards, one of one board and 31 empty ones (65), and 43 of three boards,
+    one of one board and 20 empty ones (130)."""
     _compare(B, SEED + B)
 
 
@@ -208,7 +212,7 @@ def test_sgd_tower_two_steps_match_torch_trainer():
 
 
 
-@pytest.mark.parametrize("B,scale", [(128, 1.0), (7, 0.25), (1, 1.0)])
+@pytest.mark.parametrize("B,scale", [(128, 1.0), (7, 0.25), (1, 1.0), (65, 1.0), (130, 0.25)])
 def test_sgd_fc_loss_vs_float64(B, scale):
     """gz_sgd_fc_loss (the FC heads, CrossEntropy + MSE and their backward) against
     torch autograd in float64 on the same pin / vin: the loss within 1e-6 relative,
