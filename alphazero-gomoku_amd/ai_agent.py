@@ -20,7 +20,9 @@ the network-guided PUCT search of ``gz_puct_search`` on every ply instead: the
 model's priors steer selection and its value head replaces the rollout.  It has no
 opening book and no exploration move, ignores ``beta`` and ``planner_steps``, samples
 the move from the visit counts below ``temp_plies`` plies (default 0: always the most
-visited cell) and sets ``last_search_visits`` / ``last_root_value``.
+visited cell) and sets ``last_search_visits`` / ``last_root_value``.  Play (here and in
+the arena) is always noise-free: the Dirichlet noise at the search root
+(``SelfPlayEngine(dirichlet_alpha=...)``) is self-play exploration only.
 ``time_limit`` is accepted for compatibility; the GPU completes every
 simulation, so the reference's wall-clock cut-off (ai_agent.py:183-189) never
 applies.

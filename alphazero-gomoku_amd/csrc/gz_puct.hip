@@ -36,8 +36,16 @@
 // All score arithmetic is fp64 in exactly that order (-ffp-contract=off); the
 // network's value enters as (double)float32.
 //
+// Root noise (opt-in, GZ_PUCT_ROOT_NOISE; gz_dirichlet.h, tests/puct_noise_ref.py): the
+// root's stored row becomes (1.0 - eps) * prior + eps * eta at its empty cells, eta ~
+// Dir(alpha) from the (seed, game, ply, GZ_NOISE_SIM) stream, exactly once per root: in
+// puct_backup_kernel when node 0 is the pending one (a fresh root), and after the
+// re-root for an inherited root (puct_reroot_kernel, puct_advance_kernel), on its
+// carried row with the key of its new ply.  No other node's row is touched.
+//
 // Workspace (gz_puct_workspace_bytes(n, S), M = S+1 nodes per game):
-//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S), written by gz_puct_begin
+//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S, noise flag, alpha, eps), written
+//                       by gz_puct_begin
 //   n x game_stride     per game, game_stride = al256(128 + 2334 M):
 //        PuctHdr  128 B   root position, game id, node count, pending node, ...
 //        W        f64 [M]
@@ -86,6 +94,7 @@
 #include <climits>
 #include <string>
 
+#include "gz_dirichlet.h"
 #include "gz_internal.h"
 #include "gz_search.h"
 
@@ -100,7 +109,35 @@ struct PuctCfg {
     uint64_t seed;
     int32_t temp_plies;
     int32_t S;
+    int32_t flags;  // GZ_PUCT_ROOT_NOISE
+    int32_t pad;
+    double noise_alpha;
+    double noise_eps;
 };
+static_assert(sizeof(PuctCfg) <= 256, "the configuration block");
+
+// The root noise of a launch, by value.  on: 0 none, 1 mix with (seed, alpha, eps),
+// -1 as gz_puct_begin stored it in the workspace's PuctCfg (gz_puct_backup and
+// gz_puct_reroot take no params).
+struct PuctNoise {
+    double alpha;
+    double eps;
+    uint64_t seed;
+    int32_t on;
+    int32_t pad;
+};
+
+__device__ inline PuctNoise noise_of(const PuctNoise& nz, const char* ws) {
+    if (nz.on >= 0) return nz;
+    const PuctCfg* cfg = (const PuctCfg*)ws;
+    PuctNoise r;
+    r.alpha = cfg->noise_alpha;
+    r.eps = cfg->noise_eps;
+    r.seed = cfg->seed;
+    r.on = (cfg->flags & GZ_PUCT_ROOT_NOISE) ? 1 : 0;
+    r.pad = 0;
+    return r;
+}
 
 struct PuctHdr {  // 128 bytes
     uint32_t black[8];
@@ -181,6 +218,51 @@ __device__ inline void backup(const PuctTree& t, int i, double v) {
     }
 }
 
+// eta of a root with the empty cells E for this lane's cells (eta[k]: cell lane + 64 k;
+// 0 at stones): every lane samples the Gamma(alpha) of its own cells, then every lane
+// adds all 225 up in ascending cell order (one running fp64 sum, as the reference; a
+// stone's 0.0 changes nothing) and divides.  One wave, no LDS.  false (eta all 0): the
+// total is 0 or not finite.
+__device__ inline bool root_eta(const BB& E, uint64_t seed, int64_t game_id, int ply, double alpha, double eta[4]) {
+    const int lane = lane_id();
+    const uint64_t key = stream_key(seed, game_id, ply, GZ_NOISE_SIM);
+#pragma unroll
+    for (int j = 0; j < 4; j++) eta[j] = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {  // (one copy of the sampler; the result goes to eta[k] by select)
+        const int c = lane + WAVE * k;
+        double x = 0.0;
+        if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) x = noise_gamma(key, c, alpha);
+#pragma unroll
+        for (int j = 0; j < 4; j++) eta[j] = j == k ? x : eta[j];
+    }
+    double total = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        for (int l = 0; l < WAVE && WAVE * k + l < GZ_CELLS; l++) total += __shfl(eta[k], l);
+    const bool ok = noise_total_ok(total);
+#pragma unroll
+    for (int k = 0; k < 4; k++) eta[k] = ok ? eta[k] / total : 0.0;
+    return ok;
+}
+
+// the mix of the root's stored prior row, once per root (one wave)
+__device__ inline void mix_root_row(const PuctTree& t, const PuctNoise& nz) {
+    const PuctHdr* h = t.h;
+    const int lane = lane_id();
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    const BB E = empties(black, white);
+    double eta[4];
+    if (!root_eta(E, nz.seed, h->game_id, h->n_moves, nz.alpha, eta)) return;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int c = lane + WAVE * k;
+        if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) t.prior[c] = noise_mix(t.prior[c], nz.eps, eta[k]);
+    }
+}
+
 // row g of the leaf buffer: the board, or the empty board when the game has no leaf
 __device__ inline void write_leaf(uint32_t* leaves, int32_t* active, int g, const BB& black, const BB& white,
                                   bool live) {
@@ -231,8 +313,8 @@ __device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& 
 
 // ---------------------------------------------------------------- begin
 __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* boards, const int64_t* game_ids, int n,
-                                                          gz_puct_params p, char* ws, uint32_t* leaves,
-                                                          int32_t* active) {
+                                                          gz_puct_params p, PuctNoise nz, char* ws,
+                                                          uint32_t* leaves, int32_t* active) {
     const int g = blockIdx.x;
     if (g >= n) return;
     const int lane = lane_id();
@@ -243,6 +325,10 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
         cfg->seed = p.seed;
         cfg->temp_plies = p.temp_plies;
         cfg->S = S;
+        cfg->flags = nz.on ? GZ_PUCT_ROOT_NOISE : 0;
+        cfg->pad = 0;
+        cfg->noise_alpha = nz.alpha;
+        cfg->noise_eps = nz.eps;
     }
     PuctTree t = tree_of(ws, g, S);
     const gz_board_state& bs = boards[g];
@@ -353,8 +439,13 @@ __global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int 
 }
 
 // ---------------------------------------------------------------- backup
+// The root noise is mixed here, into the row of a root as it is stored (node 0 pending:
+// gz_puct_begin's, puct_round_kernel's and gz_puct_reroot's one-node roots), and not in
+// a kernel of its own: roots appear in any round of gz_selfplay_puct_rounds, so a
+// separate kernel would be one more launch in every round, while here a round without
+// a new root pays one uniform branch.
 __global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int S, const double* prior,
-                                                           const float* value) {
+                                                           const float* value, PuctNoise nz) {
     const int g = blockIdx.x;
     if (g >= n) return;
     const int lane = lane_id();
@@ -362,6 +453,10 @@ __global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int 
     const int j = t.h->pending;
     if (j < 0) return;
     for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[(size_t)g * GZ_CELLS + c];
+    if (j == 0) {
+        const PuctNoise z = noise_of(nz, ws);
+        if (z.on) mix_root_row(t, z);  // (each lane mixes the cells it has just stored)
+    }
     if (lane == 0) {
         const float v = value[g];
         t.value[j] = v;
@@ -617,6 +712,14 @@ __global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n
     __syncthreads();  // (every thread has read the header before any of it changes)
     if (c > 0) reroot(t, c, S, remap, remap + S + 1);
     if (threadIdx.x >= WAVE) return;
+    // an inherited live root: its carried row is mixed once, with the key of its new ply
+    // (a root that still waits for its evaluation is mixed at that backup)
+    if (c > 0 && !h->over && h->pending != 0) {
+        PuctNoise stored = {};
+        stored.on = -1;  // as gz_puct_begin stored it
+        const PuctNoise nz = noise_of(stored, ws);
+        if (nz.on) mix_root_row(t, nz);
+    }
     bool live = false;
     if (play && c <= 0) {
         // no node under the move: a fresh root that waits for its evaluation
@@ -653,8 +756,8 @@ __device__ inline const SlotHeader* slot_of(const char* slots, int s) {
 // unless the move ends the game -- the tree of a move that ends it no longer matches
 // its slot after the commit, and puct_round_kernel begins a fresh one.
 __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* slots, int n, gz_puct_params p,
-                                                                  char* ws, int32_t* moves, gz_search_stats* stats,
-                                                                  uint16_t* pend) {
+                                                                  PuctNoise nz, char* ws, int32_t* moves,
+                                                                  gz_search_stats* stats, uint16_t* pend) {
     extern __shared__ __attribute__((aligned(16))) int16_t remap[];
     __shared__ int next_root;
     const int s = blockIdx.x;
@@ -703,7 +806,11 @@ __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* sl
         }
     }
     __syncthreads();
-    if (next_root > 0) reroot(t, next_root, S, remap, remap + S + 1);
+    if (next_root > 0) {
+        reroot(t, next_root, S, remap, remap + S + 1);
+        // the inherited root (live, evaluated): its carried row, mixed with its new ply's key
+        if (nz.on && threadIdx.x < WAVE) mix_root_row(t, nz);
+    }
 }
 
 // Round step 3: a tree that is not the slot's (a new game, a reset, a move that ended
@@ -780,7 +887,55 @@ __global__ __launch_bounds__(WAVE) void puct_stash_kernel(const gz_board_state* 
     for (int c = lane_id(); c < GZ_CELLS; c += WAVE) row[c] = (uint16_t)visits[(size_t)s * GZ_CELLS + c];
 }
 
+// gz_puct_root_noise: eta of every board's root (ply = n_moves), root_eta as the search runs it
+__global__ __launch_bounds__(WAVE) void puct_root_noise_kernel(const gz_board_state* boards, const int64_t* game_ids,
+                                                               int n, uint64_t seed, double alpha, double* out) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    BB black, white;
+    load_bb(black, boards[g].black);
+    load_bb(white, boards[g].white);
+    double eta[4];
+    root_eta(empties(black, white), seed, game_ids[g], boards[g].n_moves, alpha, eta);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (lane + WAVE * k < GZ_CELLS) out[(size_t)g * GZ_CELLS + lane + WAVE * k] = eta[k];
+}
+
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+int check_alpha(const char* who, double alpha) {
+    if (!(alpha >= 1e-3 && alpha <= 1e3))  // (a NaN fails both)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": noise alpha must be finite and in [1e-3, 1e3]");
+    return GZ_OK;
+}
+
+// The root noise p asks for.  Only with GZ_PUCT_ROOT_NOISE set is p a
+// gz_puct_noise_params; without it nothing past the 32 bytes of gz_puct_params is read.
+int read_noise(const char* who, const gz_puct_params* p, PuctNoise& nz) {
+    nz.alpha = 0.0;
+    nz.eps = 0.0;
+    nz.seed = p->seed;
+    nz.on = 0;
+    nz.pad = 0;
+    if (!(p->flags & GZ_PUCT_ROOT_NOISE)) return GZ_OK;
+    const gz_puct_noise_params* q = (const gz_puct_noise_params*)p;
+    int rc = check_alpha(who, q->noise_alpha);
+    if (rc) return rc;
+    if (!(q->noise_eps >= 0.0 && q->noise_eps <= 1.0))
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": noise eps must be in [0, 1]");
+    nz.alpha = q->noise_alpha;
+    nz.eps = q->noise_eps;
+    nz.on = 1;
+    return GZ_OK;
+}
+
+int backup_impl(void* ws, int32_t n, int32_t S, const double* d_prior, const float* d_value, const PuctNoise& nz,
+                void* stream) {
+    puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_prior, d_value, nz);
+    return gz_check_launch("puct_backup_kernel");
+}
 
 struct RoundBufs {
     uint32_t* leaves;
@@ -832,7 +987,10 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
                 gz_search_stats* d_stats, void* stream) {
     const int S = p->num_simulations;
     const RoundBufs r = carve_rounds(ws, n, S);
-    int rc = gz_puct_begin(d_boards, d_game_ids, n, p, ws, r.leaves, r.active, stream);
+    PuctNoise nz;
+    int rc = read_noise("gz_puct_search", p, nz);
+    if (rc) return rc;
+    rc = gz_puct_begin(d_boards, d_game_ids, n, p, ws, r.leaves, r.active, stream);
     if (rc) return rc;
     for (int round = 0; round <= S; round++) {
         if (round > 0) {
@@ -842,7 +1000,7 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
         rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
                            p->precision, stream);
         if (rc) return rc;
-        rc = gz_puct_backup(ws, n, S, r.prior, r.value, stream);
+        rc = backup_impl(ws, n, S, r.prior, r.value, nz, stream);
         if (rc) return rc;
     }
     return finish_impl(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
@@ -854,7 +1012,8 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     if (rc) return rc;
     if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
-    return GZ_OK;
+    PuctNoise nz;
+    return read_noise(who, p, nz);
 }
 
 struct SelfplayWs {
@@ -910,11 +1069,14 @@ int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int
     if (!p) return gz_fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
     int rc = check_S("gz_puct_begin", n, p->num_simulations);
     if (rc) return rc;
+    PuctNoise nz;
+    rc = read_noise("gz_puct_begin", p, nz);
+    if (rc) return rc;
     if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
         return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
     if (n == 0) return GZ_OK;
-    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, (char*)d_workspace, d_leaves,
-                                                         d_active);
+    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, (char*)d_workspace,
+                                                         d_leaves, d_active);
     return gz_check_launch("puct_begin_kernel");
 }
 
@@ -933,8 +1095,9 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prio
     if (rc) return rc;
     if (n > 0 && (!d_workspace || !d_prior || !d_value)) return gz_fail(GZ_ERR_ARG, "gz_puct_backup: bad arguments");
     if (n == 0) return GZ_OK;
-    puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_prior, d_value);
-    return gz_check_launch("puct_backup_kernel");
+    PuctNoise nz = {};
+    nz.on = -1;  // as gz_puct_begin stored it in the workspace
+    return backup_impl(d_workspace, n, S, d_prior, d_value, nz, stream);
 }
 
 int gz_puct_finish(void* d_workspace, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
@@ -1033,9 +1196,12 @@ int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
     const RoundBufs r = carve_rounds(w.puct, n_slots, S);
     hipStream_t st = as_stream(stream);
+    PuctNoise nz;
+    rc = read_noise("gz_selfplay_puct_rounds", p, nz);
+    if (rc) return rc;
     for (int it = 0; it < n_rounds; it++) {
-        puct_advance_kernel<<<n_slots, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n_slots, *p, (char*)w.puct, w.moves,
-                                                      w.stats, w.pend);
+        puct_advance_kernel<<<n_slots, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n_slots, *p, nz,
+                                                                         (char*)w.puct, w.moves, w.stats, w.pend);
         rc = gz_check_launch("puct_advance_kernel");
         if (rc) return rc;
         rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
@@ -1048,9 +1214,29 @@ int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params
         rc = gz_pv_forward(d_pv_weights, r.leaves, n_slots, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
                            p->precision, stream);
         if (rc) return rc;
-        rc = gz_puct_backup(w.puct, n_slots, S, r.prior, r.value, stream);
+        rc = backup_impl(w.puct, n_slots, S, r.prior, r.value, nz, stream);
         if (rc) return rc;
     }
+    return GZ_OK;
+}
+
+int gz_puct_root_noise(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, uint64_t seed,
+                       double alpha, double* d_eta, void* stream) {
+    int rc = check_alpha("gz_puct_root_noise", alpha);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!d_boards || !d_game_ids || !d_eta)))
+        return gz_fail(GZ_ERR_ARG, "gz_puct_root_noise: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_root_noise_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, seed, alpha, d_eta);
+    return gz_check_launch("puct_root_noise_kernel");
+}
+
+int gz_puct_root_noise_host(uint64_t seed, int64_t game_id, int32_t ply, const uint8_t* empty225, double alpha,
+                            double* eta225) {
+    int rc = check_alpha("gz_puct_root_noise_host", alpha);
+    if (rc) return rc;
+    if (!empty225 || !eta225) return gz_fail(GZ_ERR_ARG, "gz_puct_root_noise_host: bad arguments");
+    noise_eta_row(stream_key(seed, game_id, ply, GZ_NOISE_SIM), empty225, alpha, eta225);
     return GZ_OK;
 }
 

@@ -19,6 +19,7 @@ GZ_MAX_GAME_PLIES = 200
 GZ_PV_FP32 = 0
 GZ_PV_F16X3 = 1
 GZ_AUG_FIX_LABELS = 1
+GZ_PUCT_ROOT_NOISE = 1  # gz_puct_params.flags: the params are a gz_puct_noise_params
 
 
 class GzeroUnavailable(RuntimeError):
@@ -62,6 +63,10 @@ class PuctParams(ctypes.Structure):  # gz_puct_params
                 ("precision", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class PuctNoiseParams(PuctParams):  # gz_puct_noise_params: base, then the noise (48 bytes)
+    _fields_ = [("noise_alpha", ctypes.c_double), ("noise_eps", ctypes.c_double)]
+
+
 class Record(ctypes.Structure):  # gz_record, 80 bytes
     _fields_ = [("black", ctypes.c_uint32 * 8), ("white", ctypes.c_uint32 * 8),
                 ("game_id", ctypes.c_int64), ("ply", ctypes.c_int16), ("move", ctypes.c_int16),
@@ -80,6 +85,7 @@ class SelfplayCounters(ctypes.Structure):
 
 
 assert ctypes.sizeof(BoardState) == 80 and ctypes.sizeof(Record) == 80
+assert ctypes.sizeof(PuctParams) == 32 and ctypes.sizeof(PuctNoiseParams) == 48
 assert ctypes.sizeof(SearchStats) == 24 and ctypes.sizeof(SelfplayCounters) == 40
 
 class SgdNet(ctypes.Structure):  # gz_sgd_net
@@ -176,6 +182,8 @@ SIGNATURES = {
     "gz_selfplay_puct_reset": (ctypes.c_int, [_P, _I32, _I32, _P]),
     "gz_selfplay_puct_rounds": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32, _P,
                                                _P, _P]),
+    "gz_puct_root_noise": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
+    "gz_puct_root_noise_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, ctypes.c_double, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
     "gz_dataset_gather": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P]),

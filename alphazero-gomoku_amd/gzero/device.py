@@ -325,13 +325,51 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 
 
 # ---------------------------------------------------------------- PUCT search
-def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3"):
-    """gz_puct_params; precision ("fp32" / "f16x3") is the forward gz_puct_search runs."""
+def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
+                noise_eps=0.25):
+    """gz_puct_params; precision ("fp32" / "f16x3") is the forward gz_puct_search runs.
+    dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
+    noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
+    the result is then a gz_puct_noise_params with GZ_PUCT_ROOT_NOISE set.  None (the
+    default): no noise, the plain 32-byte struct."""
     if precision not in ("fp32", "f16x3"):
         raise ValueError(f"unknown precision {precision!r}")
     mode = _lib.GZ_PV_FP32 if precision == "fp32" else _lib.GZ_PV_F16X3
-    return _lib.PuctParams(int(num_simulations), int(temp_plies), float(c_puct), int(seed) & ((1 << 64) - 1),
-                           mode, 0)
+    base = (int(num_simulations), int(temp_plies), float(c_puct), int(seed) & ((1 << 64) - 1), mode)
+    if dirichlet_alpha is None:
+        return _lib.PuctParams(*base, 0)
+    alpha, eps = float(dirichlet_alpha), float(noise_eps)
+    if not 1e-3 <= alpha <= 1e3:
+        raise ValueError(f"dirichlet_alpha must be in [1e-3, 1e3], not {dirichlet_alpha!r}")
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"noise_eps must be in [0, 1], not {noise_eps!r}")
+    return _lib.PuctNoiseParams(*base, _lib.GZ_PUCT_ROOT_NOISE, alpha, eps)
+
+
+def puct_root_noise(states, game_ids, seed, alpha):
+    """eta float64 [n,225] of gz_puct_root_noise: the Dirichlet(alpha) sample the search
+    mixes into the root of each state (ply = n_moves), 0 at stones."""
+    lib = require_gpu()
+    states = np.ascontiguousarray(states, dtype=STATE_DTYPE)
+    n = len(states)
+    d_states = to_dev(states)
+    d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
+    d_eta = torch.zeros(n * 225, dtype=torch.float64, device="cuda")
+    _lib.check(lib.gz_puct_root_noise(ptr(d_states), ptr(d_gids), n, int(seed) & ((1 << 64) - 1), float(alpha),
+                                      ptr(d_eta), stream()), "gz_puct_root_noise")
+    return d_eta.cpu().numpy().reshape(n, 225)
+
+
+def puct_root_noise_host(seed, game_id, ply, empty, alpha):
+    """eta float64 [225] of gz_puct_root_noise_host (no GPU): empty = 225 truth values."""
+    lib = _lib.load()
+    e = np.ascontiguousarray(np.asarray(empty).astype(bool), np.uint8)
+    if e.shape != (225,):
+        raise ValueError("empty must have 225 entries")
+    out = np.zeros(225, np.float64)
+    _lib.check(lib.gz_puct_root_noise_host(int(seed) & ((1 << 64) - 1), int(game_id), int(ply), e.ctypes.data,
+                                           float(alpha), out.ctypes.data), "gz_puct_root_noise_host")
+    return out
 
 
 def parse_puct_tree(raw, num_simulations):

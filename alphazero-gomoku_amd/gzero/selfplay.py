@@ -28,7 +28,7 @@ class SelfPlayEngine:
                  seed=0, max_depth=100, pv_weights=None, plies_per_step=1, game_id_base=0,
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
-                 rounds_per_step=None):
+                 rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -45,6 +45,11 @@ class SelfPlayEngine:
         rounds_per_step rounds (default num_simulations + 1, the rounds of one lock-step
         ply), so the moves per step vary; a game's moves and visit rows do not depend on
         the slot count or on rounds_per_step.
+        dirichlet_alpha (search="puct" only; default None = no noise): Dirichlet noise at
+        every search root, prior' = (1 - noise_eps) prior + noise_eps Dir(dirichlet_alpha)
+        over the empty cells, sampled on the device from the (seed, game id, ply) stream
+        (GZ_PUCT_ROOT_NOISE, include/gzero.h), in lock-step and with tree_reuse alike:
+        without it play from temp_plies on is a deterministic function of the position.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -61,6 +66,8 @@ class SelfPlayEngine:
         self.tree_reuse = bool(tree_reuse)
         if self.tree_reuse and search != "puct":
             raise ValueError("tree_reuse needs search='puct'")
+        if dirichlet_alpha is not None and search != "puct":
+            raise ValueError("dirichlet_alpha needs search='puct'")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -105,7 +112,8 @@ class SelfPlayEngine:
         self.d_counters = torch.zeros(COUNTER_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self.puct = self.d_puct_ws = self.d_visits = None
         if search == "puct":
-            self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision)
+            self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision, dirichlet_alpha,
+                                    noise_eps)
             self.d_puct_ws = torch.empty(self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S),
                                          dtype=torch.uint8, device="cuda")
             # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
@@ -226,11 +234,14 @@ class SelfPlayEngine:
         planner plies (the planner pipeline needs the GN forward per ply): the slots
         reach a steady-state mix of positions, and the measured plies are planner plies.
         On a PUCT engine the burn-in plies are PUCT plies at 8 simulations (every ply
-        needs its visit row), in the engine's own workspace; with tree_reuse they are
+        needs its visit row) without root noise, in the engine's own workspace; with tree_reuse they are
         lock-step plies too, and the trees are reset afterwards (the next round begins
         every slot with a fresh root)."""
         if self.search == "puct":
+            # (the 32 bytes of the base struct: the burn-in has no root noise, so the
+            # flag that would make the library read past the copy is cleared)
             p = _lib.PuctParams.from_buffer_copy(self.puct)
+            p.flags &= ~_lib.GZ_PUCT_ROOT_NOISE
             p.num_simulations = min(8, p.num_simulations)
             for _ in range(int(n_plies)):
                 self.d_counters.zero_()

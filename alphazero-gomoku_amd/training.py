@@ -245,7 +245,8 @@ def _check_search(search, model, planner_steps) -> bool:
 
 def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: str = "medium", seed: int = 0,
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
-                         plies_per_step: int = 4, tree_reuse: bool = False):
+                         plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
+                         noise_eps: float = 0.25):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -257,6 +258,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     tree_reuse: the engine keeps the subtree under each move played and runs every slot
     on its own clock (SelfPlayEngine(tree_reuse=True)); a step is then plies_per_step x
     (num_simulations + 1) rounds, in which a slot plays at least plies_per_step moves.
+    dirichlet_alpha / noise_eps: Dirichlet noise at every search root
+    (SelfPlayEngine(dirichlet_alpha=...)); None, the default, plays the noise-free games.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -265,7 +268,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     eng = SelfPlayEngine(n_slots=slots, num_simulations=num_simulations, c_puct=c_puct, seed=seed,
                          pv_weights=model.device_weights(), plies_per_step=plies_per_step,
                          game_id_base=game_id_base, search="puct", temp_plies=temp_plies, tree_reuse=tree_reuse,
-                         rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None)
+                         rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
+                         dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -574,7 +578,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   difficulty: str = "medium", beta: float = 0.2, planner_steps: int = 5, seed: int = 0,
                   train_split: float = 0.9, batch_size: int = 128, epochs: int = 2, augment_ratio: float = 0.35,
                   planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8,
-                  tree_reuse: bool = False) -> dict:
+                  tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
+                  noise_eps: float = 0.25) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -586,7 +591,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     network trains on the root visit distributions (DeviceDataset(..., visits=...), the
     soft-target loss) instead of the moves played.  One rank only: the record exchange
     does not carry visit rows yet.  ``tree_reuse`` (search="puct"): self-play keeps the
-    subtree under each move for the next ply (selfplay_puct_device)."""
+    subtree under each move for the next ply (selfplay_puct_device).  ``dirichlet_alpha``
+    / ``noise_eps`` (search="puct"): Dirichlet noise at the search roots of self-play."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     rank, ws = gdist.world()
@@ -596,6 +602,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise NotImplementedError("search='puct' collects on one rank only: RecordExchange does not carry visit rows")
     if tree_reuse and search != "puct":
         raise ValueError("tree_reuse needs search='puct'")
+    if dirichlet_alpha is not None and search != "puct":
+        raise ValueError("dirichlet_alpha needs search='puct'")
     t0 = time.time()
     id_lo = it * ws * games_per_iteration
     replay_base = id_lo + rank * games_per_iteration
@@ -603,7 +611,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     if search == "puct":
         d, d_vis, n_rec, st = selfplay_puct_device(games_per_iteration, num_simulations=num_simulations,
                                                    difficulty=difficulty, seed=seed, game_id_base=replay_base,
-                                                   model=model, temp_plies=temp_plies, tree_reuse=tree_reuse)
+                                                   model=model, temp_plies=temp_plies, tree_reuse=tree_reuse,
+                                                   dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -677,14 +686,15 @@ def _broadcast_int(x: int) -> int:
 
 def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int] = None, models_dir: str = "models",
          num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
-         temp_plies: int = 8):
+         temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
     games) and the same checkpoint names.  Under torchrun every rank plays its
     own games and trains data-parallel (gzero.train.DeviceTrainer).
     ``search="puct"`` (one rank): self-play by the network-guided search, training on
-    its visit distributions (run_iteration)."""
+    its visit distributions (run_iteration); ``dirichlet_alpha`` / ``noise_eps`` add
+    Dirichlet noise at its search roots."""
     import math
     import os
     from gzero import dist as gdist
@@ -706,7 +716,7 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     for it in range(1, iterations + 1):
         res = run_iteration(model, trainer, it, games_per_iteration, num_simulations=num_simulations,
                             planner_steps=planner_steps, seed=seed, verbose=rank == 0, search=search,
-                            temp_plies=temp_plies)
+                            temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

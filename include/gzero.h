@@ -315,8 +315,8 @@ int gz_selfplay_plan_gn_stats(void* d_workspace, int32_t n_slots, int32_t num_si
  * synchronisation; a game with no leaf in a round has the empty board in its row.
  * Move: with n_moves >= temp_plies the empty cell with the most root-child visits
  * (first maximum); else one draw x of the (seed, game, ply, 0) stream and the first
- * cell whose running visit sum exceeds (x * total) >> 64.  No opening book,
- * exploration or noise.  A board that is over returns move -1 and zero visits.
+ * cell whose running visit sum exceeds (x * total) >> 64.  No opening book or
+ * epsilon-exploration; Dirichlet noise at the root is opt-in (GZ_PUCT_ROOT_NOISE).  A board that is over returns move -1 and zero visits.
  * d_visits (optional) int32 [n][225] root-child visits; d_root_q (optional) the
  * root's mean value for its side to move, -W[0] / visits[0].
  * Workspace layout, node record (~2.3 KB: 1.9 GB at 4096 games x 200 simulations)
@@ -327,8 +327,32 @@ typedef struct gz_puct_params {
     double c_puct;
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
     int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3: gz_puct_search's forward */
-    int32_t flags;           /* reserved, 0 */
+    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE */
 } gz_puct_params;
+/* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).
+ * With GZ_PUCT_ROOT_NOISE in flags the p given to gz_puct_begin, gz_puct_search,
+ * gz_selfplay_puct_run and gz_selfplay_puct_rounds points at a gz_puct_noise_params;
+ * without it nothing past the 32 bytes of gz_puct_params is read.  The root's stored
+ * (and exported) prior row becomes, at its empty cells,
+ *   prior'[c] = (1.0 - noise_eps) * prior[c] + noise_eps * eta[c],  eta ~ Dir(noise_alpha),
+ * eta[c] = g[c] / total, g[c] a Gamma(noise_alpha) sample that cell c draws from the
+ * (seed, game, the root's move count, 0x4E4F4953) stream (draw indices 256 c .. 256 c +
+ * 255; csrc/gz_dirichlet.h), total their running fp64 sum in ascending cell order; a
+ * total of 0 (or not finite) leaves the row alone.  Exactly once per root: a fresh
+ * root (gz_puct_begin's, a move without a child, a new game) when its evaluation is
+ * backed up, an inherited root right after the re-root, on its carried row with the
+ * key of its new ply; gz_puct_reroot's move -1 mixes nothing.  Other nodes, the visit
+ * rows, the move choice and the backup are unchanged, and the sampler is plain fp64
+ * arithmetic that rounds identically on the device, the host and in CPython
+ * (tests/puct_noise_ref.py).  noise_alpha must be finite and in [1e-3, 1e3],
+ * noise_eps in [0, 1] (GZ_ERR_ARG otherwise).  gz_puct_begin keeps the three values in
+ * the workspace for gz_puct_backup and gz_puct_reroot, which take no params. */
+#define GZ_PUCT_ROOT_NOISE 1
+typedef struct gz_puct_noise_params {
+    gz_puct_params base;
+    double noise_alpha;
+    double noise_eps;
+} gz_puct_noise_params;      /* 48 bytes */
 /* includes the forward's workspace and gz_puct_search's leaf / output rows */
 size_t gz_puct_workspace_bytes(int32_t n, int32_t num_simulations);
 /* Step API (the caller supplies the evaluator): begin writes the root boards to
@@ -395,6 +419,16 @@ int gz_selfplay_puct_reset(void* d_workspace, int32_t n_slots, int32_t num_simul
 int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                             void* d_workspace, int32_t n_rounds, gz_record* d_records, int32_t record_cap,
                             uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);
+
+/* The noise sampler on its own (the device and host functions the search runs).
+ * gz_puct_root_noise: d_eta [n][225] = eta at the empty cells of each board (ply =
+ * n_moves) and 0 at stones; an all-zero row when the total is 0 or the board is full.
+ * gz_puct_root_noise_host: the same code on the host, no GPU (empty225: non-zero =
+ * empty cell). */
+int gz_puct_root_noise(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, uint64_t seed,
+                       double alpha, double* d_eta, void* stream);
+int gz_puct_root_noise_host(uint64_t seed, int64_t game_id, int32_t ply, const uint8_t* empty225, double alpha,
+                            double* eta225);
 
 /* BGPlannerAI.get_move (bg_planner.py:232-269) for each board: d_ai = the
  * planner's colour P, d_keys = RNG stream; d_moves (-1 = None), d_draws.

@@ -27,6 +27,19 @@ how peaked the search is -- not a trained network.
 
     python tools/puct_bench.py --reuse --lockstep-library parent/libgzero.so \\
         --out profiles/puct/reuse_bench.json
+
+--noise ALPHA,EPS measures the Dirichlet noise at the search root
+(SelfPlayEngine(dirichlet_alpha=ALPHA, noise_eps=EPS)): three child processes, each with
+its own engine (same slots, simulations, burn-in and weights) -- this build with the
+noise, this build without it, and --lockstep-library (a build of the parent commit)
+without it -- take turns at one timed lock-step step each, --steps times; with --reuse
+the same again with tree-reuse engines and windows of 2 x (S+1) rounds.  Then the effect
+the noise exists for: the distinct positions among the slots after --distinct-plies
+plies from the empty board at temp_plies 0 (play without noise is deterministic there),
+noise on and off.
+
+    python tools/puct_bench.py --noise 0.3,0.25 --reuse --precisions f16x3 --steps 5 \\
+        --lockstep-library parent/libgzero.so --out profiles/puct/noise_bench.json
 """
 import argparse
 import json
@@ -53,6 +66,10 @@ ap.add_argument("--policy-scale", default="32,128",
 ap.add_argument("--lockstep-library", default=None, help="--reuse: libgzero.so the lock-step child loads")
 ap.add_argument("--lockstep-child", type=float, default=None, metavar="SCALE",
                 help="(child) time lock-step steps on request, policy FC scaled by SCALE")
+ap.add_argument("--noise", default=None, metavar="ALPHA,EPS", help="measure the root noise (see above)")
+ap.add_argument("--distinct-plies", type=int, default=8, help="--noise: plies of the distinct-positions count")
+ap.add_argument("--noise-child", default=None, metavar="MODE:NOISE",
+                help="(child) lockstep or reuse, then off or ALPHA,EPS: time steps on request")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 precisions = a.precisions.split(",")
@@ -202,8 +219,147 @@ def reuse_run(prec, scale):
     return out
 
 
+def noise_args(spec):
+    """dirichlet_alpha / noise_eps keywords of SelfPlayEngine from "off" or "ALPHA,EPS"."""
+    if spec in (None, "off"):
+        return {}
+    alpha, eps = (float(x) for x in spec.split(","))
+    return {"dirichlet_alpha": alpha, "noise_eps": eps}
+
+
+def noise_child():
+    """Per line on stdin: one lock-step step (or one window of 2 x (S+1) rounds of a
+    tree-reuse engine) timed with device events; its ms and moves on stdout."""
+    import ctypes
+    import torch
+    from gzero import _lib
+    from gzero.selfplay import SelfPlayEngine
+    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build lacks the newer entry points
+    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    mode, spec = a.noise_child.split(":")
+    reuse = mode == "reuse"
+    eng = SelfPlayEngine(n_slots=a.slots, num_simulations=a.sims, seed=1, pv_weights=bench_weights(precisions[0], 1.0),
+                         search="puct", temp_plies=a.temp_plies, tree_reuse=reuse,
+                         rounds_per_step=2 * (a.sims + 1) if reuse else None, **noise_args(spec))
+    eng.advance(a.burn)
+    for _ in range(2 if reuse else 1):  # warm-up (with reuse 4 x (S+1) rounds: the clocks drift apart)
+        eng.step()
+    torch.cuda.synchronize()
+    print("READY", flush=True)
+    for line in sys.stdin:
+        if line.strip() != "step":
+            break
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.step()
+        e1.record()
+        torch.cuda.synchronize()
+        c = eng.counters()
+        assert c["records_dropped"] == 0
+        print(f"STEP_MS {e0.elapsed_time(e1)!r} {int(c['moves'])}", flush=True)
+
+
+def noise_mode_run(prec, mode):
+    """The three engines of one mode, taking turns: {name: per-step ms, moves, medians}."""
+    S = a.sims
+    rounds = 2 * (S + 1) if mode == "reuse" else S + 1
+    kinds = [("parent", "off", a.lockstep_library), ("noise_off", "off", None), ("noise_on", a.noise, None)]
+    kids = {}
+    try:
+        for name, spec, library in kinds:
+            env = dict(os.environ)
+            if library:
+                env["GZ_LIBRARY"] = os.path.abspath(library)
+            kids[name] = subprocess.Popen(
+                [sys.executable, os.path.abspath(__file__), "--noise-child", f"{mode}:{spec}", "--slots", str(a.slots),
+                 "--sims", str(S), "--burn", str(a.burn), "--precisions", prec, "--temp-plies", str(a.temp_plies)],
+                env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+        for name, kid in kids.items():
+            if kid.stdout.readline().strip() != "READY":
+                sys.exit(f"{mode} child {name} failed ({kid.poll()})")
+        out = {name: {"step_ms": [], "moves": []} for name in kids}
+        for _ in range(a.steps):
+            for name, kid in kids.items():
+                kid.stdin.write("step\n")
+                kid.stdin.flush()
+                line = kid.stdout.readline().split()
+                if len(line) != 3 or line[0] != "STEP_MS":
+                    sys.exit(f"{mode} child {name} failed ({kid.poll()}): {line}")
+                out[name]["step_ms"].append(float(line[1]))
+                out[name]["moves"].append(int(line[2]))
+    finally:
+        for kid in kids.values():
+            kid.stdin.close()
+        for kid in kids.values():
+            kid.wait(timeout=120)
+    for name, r in out.items():
+        r["step_ms_median"] = median(r["step_ms"])
+        r["rounds_per_step"] = rounds
+        r["round_ms_median"] = r["step_ms_median"] / rounds
+    base = out["parent"]["round_ms_median"]
+    for name in ("noise_off", "noise_on"):
+        out[name]["round_ms_over_parent"] = out[name]["round_ms_median"] / base
+    print(f"{prec} {mode}: round ms parent {base:.4f}, noise off {out['noise_off']['round_ms_median']:.4f} "
+          f"(x{out['noise_off']['round_ms_over_parent']:.4f}), noise on {out['noise_on']['round_ms_median']:.4f} "
+          f"(x{out['noise_on']['round_ms_over_parent']:.4f})")
+    return out
+
+
+def distinct_positions(prec, spec):
+    """Distinct positions among the slots after --distinct-plies lock-step plies from the
+    empty board at temp_plies 0."""
+    import numpy as np
+    import torch
+    from gzero.selfplay import SelfPlayEngine
+    eng = SelfPlayEngine(n_slots=a.slots, num_simulations=a.sims, seed=1, pv_weights=bench_weights(prec, 1.0),
+                         search="puct", temp_plies=0, **noise_args(spec))
+    for _ in range(a.distinct_plies):
+        eng.step()
+    st, _ = eng.boards()
+    # (no game ends before its ninth ply; with more plies a slot may already be in its next game)
+    first = st["n_moves"] == a.distinct_plies
+    rows = np.concatenate([st["black"], st["white"]], axis=1)[first]
+    n = len(np.unique(rows, axis=0))
+    del eng
+    torch.cuda.empty_cache()
+    return {"distinct": n, "slots_in_their_first_game": int(first.sum())}
+
+
 if a.forward_only:
     forward_only()
+    sys.exit(0)
+if a.noise_child is not None:
+    noise_child()
+    sys.exit(0)
+if a.noise:
+    prec = precisions[0]
+    res = {"config": {"slots": a.slots, "simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies,
+                      "precision": prec, "noise": noise_args(a.noise), "steps": a.steps,
+                      "timing": "device events around one lock-step step (S+1 rounds) or one window of 2 x (S+1) "
+                                "rounds with tree reuse; three child processes (parent build, this build without "
+                                "and with the noise) take turns",
+                      "parent_library": "another build (--lockstep-library)" if a.lockstep_library else "this build",
+                      "distinct_plies": a.distinct_plies},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    for mode in ("lockstep", "reuse") if a.reuse else ("lockstep",):
+        res["results"][mode] = noise_mode_run(prec, mode)
+    res["results"]["distinct_positions"] = {
+        "what": f"distinct positions among {a.slots} games after {a.distinct_plies} plies from the empty board, "
+                "temp_plies 0, lock-step",
+        "noise_off": distinct_positions(prec, "off"), "noise_on": distinct_positions(prec, a.noise)}
+    print(f"distinct positions after {a.distinct_plies} plies: "
+          f"{res['results']['distinct_positions']['noise_off']['distinct']} without noise, "
+          f"{res['results']['distinct_positions']['noise_on']['distinct']} with")
+    import torch
+    res["device"] = torch.cuda.get_device_name(0)
+    print("PUCT_NOISE_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.lockstep_child is not None:
     lockstep_child()
