@@ -20,7 +20,10 @@ the network-guided PUCT search of ``gz_puct_search`` on every ply instead: the
 model's priors steer selection and its value head replaces the rollout.  It has no
 opening book and no exploration move, ignores ``beta`` and ``planner_steps``, samples
 the move from the visit counts below ``temp_plies`` plies (default 0: always the most
-visited cell) and sets ``last_search_visits`` / ``last_root_value``.  Play (here and in
+visited cell) and sets ``last_search_visits`` / ``last_root_value``.
+``leaves_per_round=K`` (default 1) evaluates K leaves per board per round with virtual
+loss (``device.puct_params``): a move of one board then takes about ``1 + S/K``
+forwards instead of ``S + 1``.  Play (here and in
 the arena) is always noise-free: the Dirichlet noise at the search root
 (``SelfPlayEngine(dirichlet_alpha=...)``) is self-play exploration only.
 ``time_limit`` is accepted for compatibility; the GPU completes every
@@ -45,11 +48,14 @@ class AlphaZeroGomokuAI:
                  device: Optional[str] = None, beta: float = 0.2, planner_steps: int = 5,
                  time_limit: float = 5.0, time_reward_factor: float = 0.1, seed: Optional[int] = None,
                  game_id: int = 0, compute_priors: bool = True, search: str = "reference",
-                 temp_plies: int = 0):
+                 temp_plies: int = 0, leaves_per_round: int = 1):
         if search not in ("reference", "puct"):
             raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
         self.search = search
         self.temp_plies = int(temp_plies)
+        self.leaves_per_round = int(leaves_per_round)
+        if self.leaves_per_round != 1 and search != "puct":
+            raise ValueError("leaves_per_round needs search='puct'")
         self.last_search_visits = None  # puct: int32 [n, 225] root visit counts of the last call
         self.last_root_value = None     # puct: the roots' mean value for the side to move
         self.player = player
@@ -165,7 +171,7 @@ class AlphaZeroGomokuAI:
         if boards:
             w = self.model.device_weights()
             p = device.puct_params(self.params.get("num_simulations", 200), self.params["c_puct"], self.temp_plies,
-                                   self.seed, w.precision)
+                                   self.seed, w.precision, leaves_per_round=self.leaves_per_round)
             states = np.concatenate([b.to_state() for b in boards])
             mv, visits, q, _ = device.puct_search(states, [int(g) for g in game_ids], p, w)
             self.last_search_visits, self.last_root_value = visits, q

@@ -89,10 +89,37 @@
 // Export (gz_puct_trees, gz_puct_tree_bytes(S) = al256(16 + 1884 M) per game):
 //   i32 n_nodes, n_evals, main_draws, move; then W, prior, visits, value, board,
 //   parent, move, term as above (no child table), nodes in creation order.
+//
+// Leaf batching with virtual loss (opt-in, GZ_PUCT_LEAF_BATCH; tests/puct_batch_ref.py
+// restates it).  Game g owns the rows g K .. g K + K - 1 of every round buffer.  Round 0
+// evaluates the root in row g K.  In every later round puct_select_batch_kernel descends
+// up to K times, one descent after the other: vl[x] counts the leaves of this round that
+// wait below node x and enters the score as that many visits, each lost by the selector,
+//   n = visits[j] + vl[j],  q = n ? (W[j] - (double)vl[j]) / (double)n : 0.0,
+//   u = ((c_puct * prior[i][c]) * sqrt((double)(visits[i] + vl[i]))) / (1.0 + (double)n)
+// (W - 0.0 and n + 0: K = 1 is the search above bit for bit).  A descent starts only while
+// visits[0] + vl[0] <= S; one that ends in a terminal node backs up at once and takes no
+// row; one that picks a node created in this round and not yet evaluated (a collision)
+// changes nothing and ends the game's selection for the round; every other one creates a
+// node, puts its board into the game's next row and adds 1 to vl along its path.  The
+// rows left over are empty and inactive.  puct_backup_batch_kernel then stores and backs
+// up the game's active rows in ascending row order (lane 0, so W sums in that order).
+// vl is int16 [S+1] in LDS for the length of the select launch and never reaches global
+// memory: the backup has nothing to undo and the node record keeps its 2,334 bytes.  The
+// select kernel re-reads tree words that lane 0 wrote earlier in the same launch (child,
+// n_nodes, term, visits and W after a terminal backup): between two descents the wave
+// drains its stores and passes a workgroup-scope release / acquire (batch_sync).
+// The first descent of a round never collides, so a move takes between 1 + ceil(S/K) and
+// S+1 rounds; gz_puct_search reads the largest remaining count back (4 bytes) to know.
+// Batched workspace (gz_puct_batch_workspace_bytes(n, S, K)): PuctCfg and the trees as
+// above, then pend i16 [n][K] (the node of every active row), 256 bytes for the
+// remaining count, the round buffers and the forward's workspace for n K rows.
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <mutex>
 #include <string>
+#include <unordered_map>
 
 #include "gz_dirichlet.h"
 #include "gz_internal.h"
@@ -110,7 +137,7 @@ struct PuctCfg {
     int32_t temp_plies;
     int32_t S;
     int32_t flags;  // GZ_PUCT_ROOT_NOISE
-    int32_t pad;
+    int32_t leaves;  // K of a batched search (GZ_PUCT_LEAF_BATCH), 0: one leaf per round
     double noise_alpha;
     double noise_eps;
 };
@@ -313,12 +340,13 @@ __device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& 
 
 // ---------------------------------------------------------------- begin
 __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* boards, const int64_t* game_ids, int n,
-                                                          gz_puct_params p, PuctNoise nz, char* ws,
-                                                          uint32_t* leaves, int32_t* active) {
+                                                          gz_puct_params p, PuctNoise nz, int K, int16_t* pend,
+                                                          char* ws, uint32_t* leaves, int32_t* active) {
     const int g = blockIdx.x;
     if (g >= n) return;
     const int lane = lane_id();
     const int S = p.num_simulations;
+    const int rows = K > 0 ? K : 1;  // (K = 0, pend = nullptr: the unbatched search)
     if (g == 0 && lane == 0) {
         PuctCfg* cfg = (PuctCfg*)ws;
         cfg->c_puct = p.c_puct;
@@ -326,7 +354,7 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
         cfg->temp_plies = p.temp_plies;
         cfg->S = S;
         cfg->flags = nz.on ? GZ_PUCT_ROOT_NOISE : 0;
-        cfg->pad = 0;
+        cfg->leaves = K;
         cfg->noise_alpha = nz.alpha;
         cfg->noise_eps = nz.eps;
     }
@@ -337,7 +365,10 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
     load_bb(white, bs.white);
     const bool over = bs.over != 0 || !bb_any(empties(black, white));
     begin_root(t, black, white, game_ids[g], bs.n_moves, bs.player, over, 0);
-    write_leaf(leaves, active, g, black, white, !over);
+    write_leaf(leaves, active, g * rows, black, white, !over);
+    for (int k = 1; k < rows; k++) write_leaf(leaves, active, g * rows + k, black, white, false);
+    if (pend)
+        for (int k = lane; k < rows; k += WAVE) pend[(size_t)g * rows + k] = -1;
 }
 
 // ---------------------------------------------------------------- select
@@ -465,6 +496,193 @@ __global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int 
         t.h->n_evals += 1;
         t.h->new_evals += 1;
     }
+}
+
+// ---------------------------------------------------------------- leaf batching
+// Between two descents of one launch: every store of the wave (lane 0's tree words, the
+// node rows of all lanes, vl in LDS) has left and is visible to every lane before the
+// next descent's first load.  The wave is alone in its workgroup, so workgroup scope is
+// the whole audience.
+__device__ inline void batch_sync() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+// Up to K descents of game g's tree, one after the other (each sees the virtual losses
+// of those before it); the semantics are in the header comment.  vl: int16 [S+1], LDS.
+__global__ __launch_bounds__(WAVE) void puct_select_batch_kernel(char* ws, int n, int S, int K, int16_t* pend,
+                                                                 uint32_t* leaves, int32_t* active) {
+    extern __shared__ __attribute__((aligned(16))) int16_t vl[];
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    const double c_puct = ((const PuctCfg*)ws)->c_puct;
+    const PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    int16_t* pd = pend + (size_t)g * K;
+    for (int x = lane; x <= S; x += WAVE) vl[x] = 0;
+    BB rblack, rwhite;
+    load_bb(rblack, h->black);
+    load_bb(rwhite, h->white);
+    const int player0 = h->player, cnt0 = h->n_moves;
+    const int first = h->n_nodes;  // nodes from here on are created in this launch
+    // (pending: the root still waits for its backup; keep the tree as it is)
+    bool go = !(h->over || h->pending >= 0);
+    int k = 0;
+    batch_sync();
+    while (go && k < K) {
+        if (t.visits[0] + vl[0] > S) break;  // finished + in-flight simulations fill the budget
+        BB black = rblack, white = rwhite;
+        int mover = player0, cnt = cnt0;
+        int i = 0;
+        while (true) {
+            const int tm = t.term[i];
+            if (tm) {
+                if (lane == 0) backup(t, i, tm == 3 ? 0.0 : -1.0);
+                break;
+            }
+            const BB E = empties(black, white);
+            const double sq = __builtin_sqrt((double)(t.visits[i] + vl[i]));
+            const double* pr = t.prior + (size_t)i * GZ_CELLS;
+            const int16_t* ch = t.child + (size_t)i * GZ_CELLS;
+            double bv = -__builtin_inf();
+            int bi = INT_MAX;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; q4++) {
+                const int c = lane + WAVE * q4;
+                if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) {
+                    const int cj = ch[c];
+                    int nn = 0;
+                    double q = 0.0;
+                    if (cj >= 0) {
+                        const int lost = vl[cj];
+                        nn = t.visits[cj] + lost;
+                        q = nn ? (t.W[cj] - (double)lost) / (double)nn : 0.0;
+                    }
+                    const double u = ((c_puct * pr[c]) * sq) / (1.0 + (double)nn);
+                    const double sc = q + u;
+                    if (sc > bv) {
+                        bv = sc;
+                        bi = c;
+                    }
+                }
+            }
+            wave_argmax(bv, bi);
+            if (bi == INT_MAX) bi = bit_to_cell(lowest_bit(E));  // only if the evaluator gave non-finite priors
+            if (bi < 0 || bi >= GZ_CELLS) {  // (a live node always has an empty cell)
+                go = false;
+                break;
+            }
+            const int bit = cell_to_bit(bi);
+            const int cj = ch[bi];
+            if (cj >= 0) {
+                if (cj >= first && t.term[cj] == 0) {  // a collision: the node has no prior row yet
+                    go = false;
+                    break;
+                }
+                if (mover == 1) bb_set(black, bit);
+                else bb_set(white, bit);
+                mover = 3 - mover;
+                cnt++;
+                i = cj;
+                continue;
+            }
+            const int j = h->n_nodes;
+            if (j > S) {  // (never within the budget: every descent creates at most one node)
+                go = false;
+                break;
+            }
+            // make_move's rules, as descend()
+            const bool win = bb_test(threats(mover == 1 ? black : white).win, bit);
+            const int ne = bb_count(E);
+            if (mover == 1) bb_set(black, bit);
+            else bb_set(white, bit);
+            cnt++;
+            const int term = win ? mover : ((ne == 1 || cnt >= GZ_MAX_GAME_PLIES) ? 3 : 0);
+            new_node(t, j, i, bi, term, black, white);
+            if (lane == 0) {
+                t.child[(size_t)i * GZ_CELLS + bi] = (int16_t)j;
+                h->n_nodes = j + 1;
+                if (term) {
+                    backup(t, j, term == 3 ? 0.0 : -1.0);
+                } else {
+                    pd[k] = (int16_t)j;
+                    vl[j] += 1;
+                    for (int x = i; x >= 0; x = t.parent[x]) vl[x] += 1;
+                }
+            }
+            if (term == 0) {
+                write_leaf(leaves, active, g * K + k, black, white, true);
+                k++;
+            }
+            break;
+        }
+        batch_sync();
+    }
+    for (; k < K; k++) {
+        write_leaf(leaves, active, g * K + k, rblack, rwhite, false);
+        if (lane == 0) pd[k] = -1;
+    }
+}
+
+// The backup step of a batched round: the root of gz_puct_begin (header.pending, row g K,
+// with the root-noise branch of puct_backup_kernel), else the game's active rows in
+// ascending order -- the prior rows by the whole wave, values and backups by lane 0 one
+// row after the other, so every W sums in the reference's order.
+__global__ __launch_bounds__(WAVE) void puct_backup_batch_kernel(char* ws, int n, int S, int K, int16_t* pend,
+                                                                 const double* prior, const float* value,
+                                                                 PuctNoise nz) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    const int j0 = h->pending;
+    if (j0 >= 0) {
+        const size_t row = (size_t)g * K;
+        for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j0 * GZ_CELLS + c] = prior[row * GZ_CELLS + c];
+        if (j0 == 0) {
+            const PuctNoise z = noise_of(nz, ws);
+            if (z.on) mix_root_row(t, z);  // (each lane mixes the cells it has just stored)
+        }
+        if (lane == 0) {
+            const float v = value[row];
+            t.value[j0] = v;
+            backup(t, j0, (double)v);
+            h->pending = -1;
+            h->n_evals += 1;
+            h->new_evals += 1;
+        }
+        return;
+    }
+    int16_t* pd = pend + (size_t)g * K;
+    for (int k = 0; k < K; k++) {
+        const int j = pd[k];
+        if (j < 0 || j > S) continue;
+        const size_t row = (size_t)g * K + k;
+        for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[row * GZ_CELLS + c];
+        if (lane == 0) {
+            const float v = value[row];
+            t.value[j] = v;
+            backup(t, j, (double)v);
+            h->n_evals += 1;
+            h->new_evals += 1;
+        }
+    }
+    // every lane has read the game's pend row before it is cleared
+    batch_sync();
+    for (int k = lane; k < K; k += WAVE) pd[k] = -1;
+}
+
+// simulations left to every game's budget (0: the game is over), and their maximum
+__global__ void puct_remaining_kernel(char* ws, int n, int S, int32_t* remaining, int32_t* largest) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const PuctTree t = tree_of(ws, g, S);
+    int r = t.h->over ? 0 : S + 1 - t.visits[0];
+    if (r < 0) r = 0;
+    if (remaining) remaining[g] = r;
+    if (largest && r > 0) atomicMax(largest, r);
 }
 
 // ---------------------------------------------------------------- finish
@@ -931,6 +1149,44 @@ int read_noise(const char* who, const gz_puct_params* p, PuctNoise& nz) {
     return GZ_OK;
 }
 
+// The leaves per round p asks for: 0 without GZ_PUCT_LEAF_BATCH (nothing past the noise
+// struct is read then), else gz_puct_batch_params.leaves_per_round in 1..GZ_PUCT_MAX_LEAVES.
+int read_leaves(const char* who, const gz_puct_params* p, int& K) {
+    K = 0;
+    if (!(p->flags & GZ_PUCT_LEAF_BATCH)) return GZ_OK;
+    K = ((const gz_puct_batch_params*)p)->leaves_per_round;
+    if (K < 1 || K > GZ_PUCT_MAX_LEAVES)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": leaves_per_round out of range [1, 32]");
+    return GZ_OK;
+}
+
+// the n K rows of a round are indexed with int32
+int check_rows(const char* who, int32_t n, int32_t K) {
+    if (K > 0 && (int64_t)n * K > INT32_MAX) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n x leaves_per_round too large");
+    return GZ_OK;
+}
+
+// Which workspaces hold a batched search.  gz_puct_select, gz_puct_backup and
+// gz_puct_reroot take no params, and the kernel to launch (and its grid of rows) cannot
+// be chosen from the PuctCfg in device memory without reading it back, which would
+// synchronise the unbatched step API too.  So gz_puct_begin notes K on the host as well,
+// by workspace address; a later unbatched begin on the same address removes the note.
+std::mutex g_batch_mutex;
+std::unordered_map<const void*, int> g_batch_leaves;
+
+void note_leaves(const void* ws, int K) {
+    std::lock_guard<std::mutex> lock(g_batch_mutex);
+    if (K > 0) g_batch_leaves[ws] = K;
+    else if (!g_batch_leaves.empty()) g_batch_leaves.erase(ws);
+}
+
+int leaves_of(const void* ws) {
+    std::lock_guard<std::mutex> lock(g_batch_mutex);
+    if (g_batch_leaves.empty()) return 0;
+    const auto it = g_batch_leaves.find(ws);
+    return it == g_batch_leaves.end() ? 0 : it->second;
+}
+
 int backup_impl(void* ws, int32_t n, int32_t S, const double* d_prior, const float* d_value, const PuctNoise& nz,
                 void* stream) {
     puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_prior, d_value, nz);
@@ -950,8 +1206,8 @@ size_t remap_bytes(int32_t S) { return (4 * ((size_t)S + 1) + 15) & ~(size_t)15;
 
 size_t rounds_offset(int32_t n, int32_t S) { return 256 + (size_t)n * game_stride_for(S); }
 
-RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) {
-    char* p = (char*)ws + rounds_offset(n, S);
+// the round buffers of n rows from p on
+RoundBufs carve_rows(char* p, size_t n) {
     RoundBufs r;
     r.leaves = (uint32_t*)p;
     p += al256((size_t)n * 64);
@@ -969,6 +1225,29 @@ RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) {
     return r;
 }
 
+RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) { return carve_rows((char*)ws + rounds_offset(n, S), n); }
+
+// the batched workspace after the trees: pend i16 [n][K], the remaining count, then the
+// round buffers of n K rows
+struct BatchBufs {
+    int16_t* pend;
+    int32_t* left;
+    RoundBufs r;
+};
+
+size_t batch_pend_bytes(int32_t n, int32_t K) { return al256((size_t)n * K * 2); }
+
+BatchBufs carve_batch(void* ws, int32_t n, int32_t S, int32_t K) {
+    char* p = (char*)ws + rounds_offset(n, S);
+    BatchBufs b;
+    b.pend = (int16_t*)p;
+    p += batch_pend_bytes(n, K);
+    b.left = (int32_t*)p;
+    p += 256;
+    b.r = carve_rows(p, (size_t)n * K);
+    return b;
+}
+
 int check_S(const char* who, int32_t n, int32_t S) {
     if (S < 1 || S > GZ_MAX_SIMULATIONS)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": num_simulations out of range [1, 4095]");
@@ -982,9 +1261,75 @@ int finish_impl(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_vis
     return gz_check_launch("puct_finish_kernel");
 }
 
+int select_batch_impl(void* ws, int32_t n, int32_t S, int32_t K, uint32_t* d_leaves, int32_t* d_active, void* stream) {
+    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n, S));
+    puct_select_batch_kernel<<<n, WAVE, 2 * ((size_t)S + 1), as_stream(stream)>>>((char*)ws, n, S, K, pend, d_leaves,
+                                                                                   d_active);
+    return gz_check_launch("puct_select_batch_kernel");
+}
+
+int backup_batch_impl(void* ws, int32_t n, int32_t S, int32_t K, const double* d_prior, const float* d_value,
+                      const PuctNoise& nz, void* stream) {
+    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n, S));
+    puct_backup_batch_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, K, pend, d_prior, d_value, nz);
+    return gz_check_launch("puct_backup_batch_kernel");
+}
+
+// The batched search: the root round, ceil(S/K) rounds of n K rows, then one int32 read
+// back -- the largest remaining count -- and ceil(left/K) more rounds until it is 0.
+// Every unfinished game completes at least one simulation per round, so the count falls.
+int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
+                      int32_t K, const float* d_pv_weights, void* ws, int32_t* d_moves, int32_t* d_visits,
+                      double* d_root_q, gz_search_stats* d_stats, void* stream) {
+    const int S = p->num_simulations;
+    const BatchBufs b = carve_batch(ws, n, S, K);
+    const RoundBufs& r = b.r;
+    hipStream_t st = as_stream(stream);
+    PuctNoise nz;
+    int rc = read_noise("gz_puct_search", p, nz);
+    if (rc) return rc;
+    rc = gz_puct_begin(d_boards, d_game_ids, n, p, ws, r.leaves, r.active, stream);
+    if (rc) return rc;
+    int todo = 1 + (S + K - 1) / K;
+    bool root = true;
+    while (todo > 0) {
+        for (int round = 0; round < todo; round++) {
+            if (!root) {
+                rc = select_batch_impl(ws, n, S, K, r.leaves, r.active, stream);
+                if (rc) return rc;
+            }
+            root = false;
+            rc = gz_pv_forward(d_pv_weights, r.leaves, n * K, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
+                               p->precision, stream);
+            if (rc) return rc;
+            rc = backup_batch_impl(ws, n, S, K, r.prior, r.value, nz, stream);
+            if (rc) return rc;
+        }
+        int32_t left = 0;
+        hipError_t e = hipMemsetAsync(b.left, 0, sizeof(int32_t), st);
+        if (e == hipSuccess) {
+            puct_remaining_kernel<<<(n + 255) / 256, 256, 0, st>>>((char*)ws, n, S, nullptr, b.left);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&left, b.left, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return gz_fail(GZ_ERR_HIP, std::string("gz_puct_search: the remaining count: ") + hipGetErrorString(e));
+        todo = (left + K - 1) / K;
+    }
+    return finish_impl(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
+}
+
 int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
                 const float* d_pv_weights, void* ws, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
                 gz_search_stats* d_stats, void* stream) {
+    int K = 0;
+    if (p->flags & GZ_PUCT_LEAF_BATCH) {
+        int rc = read_leaves("gz_puct_search", p, K);
+        if (rc) return rc;
+        return search_batch_impl(d_boards, d_game_ids, n, p, K, d_pv_weights, ws, d_moves, d_visits, d_root_q, d_stats,
+                                 stream);
+    }
     const int S = p->num_simulations;
     const RoundBufs r = carve_rounds(ws, n, S);
     PuctNoise nz;
@@ -1013,7 +1358,12 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
     PuctNoise nz;
-    return read_noise(who, p, nz);
+    rc = read_noise(who, p, nz);
+    if (rc) return rc;
+    int K;
+    rc = read_leaves(who, p, K);
+    if (rc) return rc;
+    return check_rows(who, n, K);
 }
 
 struct SelfplayWs {
@@ -1072,11 +1422,18 @@ int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int
     PuctNoise nz;
     rc = read_noise("gz_puct_begin", p, nz);
     if (rc) return rc;
+    int K;
+    rc = read_leaves("gz_puct_begin", p, K);
+    if (rc) return rc;
+    rc = check_rows("gz_puct_begin", n, K);
+    if (rc) return rc;
     if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
         return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
     if (n == 0) return GZ_OK;
-    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, (char*)d_workspace,
-                                                         d_leaves, d_active);
+    note_leaves(d_workspace, K);
+    int16_t* pend = K > 0 ? (int16_t*)((char*)d_workspace + rounds_offset(n, p->num_simulations)) : nullptr;
+    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, K, pend,
+                                                         (char*)d_workspace, d_leaves, d_active);
     return gz_check_launch("puct_begin_kernel");
 }
 
@@ -1085,6 +1442,8 @@ int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, 
     if (rc) return rc;
     if (n > 0 && (!d_workspace || !d_leaves || !d_active)) return gz_fail(GZ_ERR_ARG, "gz_puct_select: bad arguments");
     if (n == 0) return GZ_OK;
+    const int K = leaves_of(d_workspace);
+    if (K > 0) return select_batch_impl(d_workspace, n, S, K, d_leaves, d_active, stream);
     puct_select_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
     return gz_check_launch("puct_select_kernel");
 }
@@ -1097,7 +1456,29 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prio
     if (n == 0) return GZ_OK;
     PuctNoise nz = {};
     nz.on = -1;  // as gz_puct_begin stored it in the workspace
+    const int K = leaves_of(d_workspace);
+    if (K > 0) return backup_batch_impl(d_workspace, n, S, K, d_prior, d_value, nz, stream);
     return backup_impl(d_workspace, n, S, d_prior, d_value, nz, stream);
+}
+
+int gz_puct_remaining(void* d_workspace, int32_t n, int32_t S, int32_t* d_remaining, void* stream) {
+    int rc = check_S("gz_puct_remaining", n, S);
+    if (rc) return rc;
+    if (n > 0 && (!d_workspace || !d_remaining)) return gz_fail(GZ_ERR_ARG, "gz_puct_remaining: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_remaining_kernel<<<(n + 255) / 256, 256, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_remaining,
+                                                                         nullptr);
+    return gz_check_launch("puct_remaining_kernel");
+}
+
+size_t gz_puct_batch_workspace_bytes(int32_t n, int32_t S, int32_t K) {
+    if (n < 1) n = 1;
+    if (S < 0) S = 0;
+    if (K < 1) K = 1;
+    if (K > GZ_PUCT_MAX_LEAVES) K = GZ_PUCT_MAX_LEAVES;
+    const size_t m = (size_t)n * K;
+    return rounds_offset(n, S) + batch_pend_bytes(n, K) + 256 + al256(m * 64) + al256(m * 4) + 2 * al256(m * 900) +
+           al256(m * 4) + al256(m * 1800) + gz_pv_workspace_bytes((int32_t)m);
 }
 
 int gz_puct_finish(void* d_workspace, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
@@ -1137,6 +1518,13 @@ size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t S) {
            al256(m * 900) + al256(m * 8) + pend_bytes(n_slots) + gz_puct_workspace_bytes(n_slots, S);
 }
 
+size_t gz_selfplay_puct_batch_workspace_bytes(int32_t n_slots, int32_t S, int32_t K) {
+    if (n_slots < 1) n_slots = 1;
+    const size_t m = (size_t)n_slots;
+    return al256(m * sizeof(gz_board_state)) + al256(m * 8) + al256(m * 4) + al256(m * sizeof(gz_search_stats)) +
+           al256(m * 900) + al256(m * 8) + pend_bytes(n_slots) + gz_puct_batch_workspace_bytes(n_slots, S, K);
+}
+
 int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                          void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
                          uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
@@ -1170,6 +1558,8 @@ int gz_puct_reroot(void* d_workspace, int32_t n, int32_t S, const int32_t* d_mov
     if (n > 0 && (!d_workspace || !d_moves || !d_leaves || !d_active))
         return gz_fail(GZ_ERR_ARG, "gz_puct_reroot: bad arguments");
     if (n == 0) return GZ_OK;
+    if (leaves_of(d_workspace) > 1)
+        return gz_fail(GZ_ERR_ARG, "gz_puct_reroot: tree reuse with leaves_per_round > 1 is not supported");
     puct_reroot_kernel<<<n, RR_THREADS, remap_bytes(S), as_stream(stream)>>>((char*)d_workspace, n, S, d_moves, d_leaves,
                                                                       d_active, d_remaining);
     return gz_check_launch("puct_reroot_kernel");
@@ -1192,6 +1582,11 @@ int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params
     if (!d_slots || n_slots <= 0 || n_rounds < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
         !d_pv_weights || !d_visits)
         return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_rounds: bad arguments");
+    int K;
+    rc = read_leaves("gz_selfplay_puct_rounds", p, K);
+    if (rc) return rc;
+    if (K > 1)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_rounds: tree reuse with leaves_per_round > 1 is not supported");
     const int S = p->num_simulations;
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
     const RoundBufs r = carve_rounds(w.puct, n_slots, S);

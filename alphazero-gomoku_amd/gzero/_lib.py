@@ -20,6 +20,8 @@ GZ_PV_FP32 = 0
 GZ_PV_F16X3 = 1
 GZ_AUG_FIX_LABELS = 1
 GZ_PUCT_ROOT_NOISE = 1  # gz_puct_params.flags: the params are a gz_puct_noise_params
+GZ_PUCT_LEAF_BATCH = 2  # gz_puct_params.flags: the params are a gz_puct_batch_params
+GZ_PUCT_MAX_LEAVES = 32
 
 
 class GzeroUnavailable(RuntimeError):
@@ -67,6 +69,10 @@ class PuctNoiseParams(PuctParams):  # gz_puct_noise_params: base, then the noise
     _fields_ = [("noise_alpha", ctypes.c_double), ("noise_eps", ctypes.c_double)]
 
 
+class PuctBatchParams(PuctNoiseParams):  # gz_puct_batch_params: the noise struct, then K (56 bytes)
+    _fields_ = [("leaves_per_round", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class Record(ctypes.Structure):  # gz_record, 80 bytes
     _fields_ = [("black", ctypes.c_uint32 * 8), ("white", ctypes.c_uint32 * 8),
                 ("game_id", ctypes.c_int64), ("ply", ctypes.c_int16), ("move", ctypes.c_int16),
@@ -86,6 +92,7 @@ class SelfplayCounters(ctypes.Structure):
 
 assert ctypes.sizeof(BoardState) == 80 and ctypes.sizeof(Record) == 80
 assert ctypes.sizeof(PuctParams) == 32 and ctypes.sizeof(PuctNoiseParams) == 48
+assert ctypes.sizeof(PuctBatchParams) == 56
 assert ctypes.sizeof(SearchStats) == 24 and ctypes.sizeof(SelfplayCounters) == 40
 
 class SgdNet(ctypes.Structure):  # gz_sgd_net
@@ -182,6 +189,9 @@ SIGNATURES = {
     "gz_selfplay_puct_reset": (ctypes.c_int, [_P, _I32, _I32, _P]),
     "gz_selfplay_puct_rounds": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32, _P,
                                                _P, _P]),
+    "gz_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "gz_selfplay_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "gz_puct_remaining": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
     "gz_puct_root_noise": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
     "gz_puct_root_noise_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, ctypes.c_double, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),

@@ -326,24 +326,64 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 
 # ---------------------------------------------------------------- PUCT search
 def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
-                noise_eps=0.25):
+                noise_eps=0.25, leaves_per_round=1):
     """gz_puct_params; precision ("fp32" / "f16x3") is the forward gz_puct_search runs.
     dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
     noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
     the result is then a gz_puct_noise_params with GZ_PUCT_ROOT_NOISE set.  None (the
-    default): no noise, the plain 32-byte struct."""
+    default): no noise, the plain 32-byte struct.
+    leaves_per_round K > 1: leaf batching with virtual loss, K leaves per game per round
+    (a gz_puct_batch_params with GZ_PUCT_LEAF_BATCH set); 1 (the default) is the
+    unbatched search with the flag clear."""
     if precision not in ("fp32", "f16x3"):
         raise ValueError(f"unknown precision {precision!r}")
     mode = _lib.GZ_PV_FP32 if precision == "fp32" else _lib.GZ_PV_F16X3
     base = (int(num_simulations), int(temp_plies), float(c_puct), int(seed) & ((1 << 64) - 1), mode)
+    K = int(leaves_per_round)
+    if not 1 <= K <= _lib.GZ_PUCT_MAX_LEAVES:
+        raise ValueError(f"leaves_per_round must be in [1, {_lib.GZ_PUCT_MAX_LEAVES}], not {leaves_per_round!r}")
+    batch = _lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0
     if dirichlet_alpha is None:
-        return _lib.PuctParams(*base, 0)
+        return _lib.PuctBatchParams(*base, batch, 0.0, 0.0, K, 0) if batch else _lib.PuctParams(*base, 0)
     alpha, eps = float(dirichlet_alpha), float(noise_eps)
     if not 1e-3 <= alpha <= 1e3:
         raise ValueError(f"dirichlet_alpha must be in [1e-3, 1e3], not {dirichlet_alpha!r}")
     if not 0.0 <= eps <= 1.0:
         raise ValueError(f"noise_eps must be in [0, 1], not {noise_eps!r}")
+    if batch:
+        return _lib.PuctBatchParams(*base, _lib.GZ_PUCT_ROOT_NOISE | batch, alpha, eps, K, 0)
     return _lib.PuctNoiseParams(*base, _lib.GZ_PUCT_ROOT_NOISE, alpha, eps)
+
+
+def puct_leaves(params):
+    """K of a batched params struct (GZ_PUCT_LEAF_BATCH), 0 for the unbatched search."""
+    return int(params.leaves_per_round) if params.flags & _lib.GZ_PUCT_LEAF_BATCH else 0
+
+
+def with_leaves(params, leaves_per_round):
+    """params with another leaves_per_round (None: params as they are; 1 on unbatched
+    params: as they are too)."""
+    if leaves_per_round is None:
+        return params
+    K = int(leaves_per_round)
+    if not 1 <= K <= _lib.GZ_PUCT_MAX_LEAVES:
+        raise ValueError(f"leaves_per_round must be in [1, {_lib.GZ_PUCT_MAX_LEAVES}], not {leaves_per_round!r}")
+    if K == 1 and not params.flags & _lib.GZ_PUCT_LEAF_BATCH:
+        return params
+    noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
+    flags = noise | (_lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0)
+    base = (params.num_simulations, params.temp_plies, params.c_puct, params.seed, params.precision)
+    alpha, eps = (params.noise_alpha, params.noise_eps) if noise else (0.0, 0.0)
+    if K > 1:
+        return _lib.PuctBatchParams(*base, flags, alpha, eps, K, 0)
+    return _lib.PuctNoiseParams(*base, flags, alpha, eps) if noise else _lib.PuctParams(*base, 0)
+
+
+def _puct_workspace_bytes(lib, n, params):
+    # (an S out of range is the library's error to report: size the workspace for a legal one)
+    S = max(0, min(params.num_simulations, _lib.GZ_MAX_SIMULATIONS))
+    K = puct_leaves(params)
+    return lib.gz_puct_batch_workspace_bytes(n, S, K) if K else lib.gz_puct_workspace_bytes(n, S)
 
 
 def puct_root_noise(states, game_ids, seed, alpha):
@@ -400,11 +440,14 @@ def _puct_trees(lib, ws, n, S):
     return [parse_puct_tree(raw[i], S) for i in range(n)]
 
 
-def puct_search(states, game_ids, params, pv_weights, want_trees=False):
+def puct_search(states, game_ids, params, pv_weights, want_trees=False, leaves_per_round=None):
     """One network-guided PUCT search per state (gz_puct_search) with the forward of
     params.precision.  Returns (moves int32 [n] (-1: the board is over), visits int32
-    [n,225] root-child visits, root_q float64 [n], trees or None)."""
+    [n,225] root-child visits, root_q float64 [n], trees or None).  leaves_per_round:
+    None = as params say (puct_params(leaves_per_round=...)), else that many leaves per
+    game per round."""
     lib = require_gpu()
+    params = with_leaves(params, leaves_per_round)
     states = np.ascontiguousarray(states, dtype=STATE_DTYPE)
     n = len(states)
     S = params.num_simulations
@@ -413,9 +456,7 @@ def puct_search(states, game_ids, params, pv_weights, want_trees=False):
     d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
     d_visits = torch.zeros(n * 225, dtype=torch.int32, device="cuda")
     d_q = torch.zeros(n, dtype=torch.float64, device="cuda")
-    # (an S out of range is the library's error to report: size the workspace for a legal one)
-    ws = torch.empty(lib.gz_puct_workspace_bytes(n, max(0, min(S, _lib.GZ_MAX_SIMULATIONS))), dtype=torch.uint8,
-                     device="cuda")
+    ws = torch.empty(_puct_workspace_bytes(lib, n, params), dtype=torch.uint8, device="cuda")
     _lib.check(lib.gz_puct_search(ptr(d_states), ptr(d_gids), n, ctypes.byref(params), ptr(pv_weights.tensor),
                                   ptr(ws), ptr(d_moves), ptr(d_visits), ptr(d_q), stream()), "gz_puct_search")
     torch.cuda.synchronize()
@@ -434,27 +475,41 @@ class PuctStepper:
         moves, visits, root_q = st.finish()
 
     prior float64 [n,225] and value float32 [n] in gz_pv_forward's layouts (device
-    tensors or arrays); rows of inactive games are ignored."""
+    tensors or arrays); rows of inactive games are ignored.
 
-    def __init__(self, states, game_ids, params):
+    With leaves_per_round K > 1 (here or in params) every buffer has n K rows, game g at
+    rows g K .. g K + K - 1, and a search is no fixed number of rounds: after the root's
+    backup, ``while st.remaining().any(): st.select(); ...; st.backup(prior, value)``."""
+
+    def __init__(self, states, game_ids, params, leaves_per_round=None):
         self.lib = require_gpu()
         states = np.ascontiguousarray(states, dtype=STATE_DTYPE)
+        params = with_leaves(params, leaves_per_round)
         self.n = len(states)
         self.S = params.num_simulations
+        self.K = puct_leaves(params)
+        self.rows = self.n * max(1, self.K)
         self.params = params
         d_states = to_dev(states)
         d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
-        self.d_leaves = torch.zeros(self.n * 16, dtype=torch.int32, device="cuda")
-        self.d_active = torch.zeros(self.n, dtype=torch.int32, device="cuda")
-        nbytes = self.lib.gz_puct_workspace_bytes(self.n, max(0, min(self.S, _lib.GZ_MAX_SIMULATIONS)))
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        self.d_leaves = torch.zeros(self.rows * 16, dtype=torch.int32, device="cuda")
+        self.d_active = torch.zeros(self.rows, dtype=torch.int32, device="cuda")
+        self.ws = torch.empty(_puct_workspace_bytes(self.lib, self.n, params), dtype=torch.uint8, device="cuda")
         _lib.check(self.lib.gz_puct_begin(ptr(d_states), ptr(d_gids), self.n, ctypes.byref(params), ptr(self.ws),
                                           ptr(self.d_leaves), ptr(self.d_active), stream()), "gz_puct_begin")
 
     def leaves(self):
-        """(rows uint32 [n,16], active bool [n]) of the current round (synchronising)."""
-        rows = self.d_leaves.cpu().numpy().view(np.uint32).reshape(self.n, 16)
+        """(rows uint32 [n K,16], active bool [n K]) of the current round (synchronising)."""
+        rows = self.d_leaves.cpu().numpy().view(np.uint32).reshape(self.rows, 16)
         return rows, self.d_active.cpu().numpy() != 0
+
+    def remaining(self):
+        """Simulations left to each game's budget, int32 [n] (0: the game is over or its
+        search is finished); gz_puct_remaining, synchronising."""
+        d_rem = torch.zeros(self.n, dtype=torch.int32, device="cuda")
+        _lib.check(self.lib.gz_puct_remaining(ptr(self.ws), self.n, self.S, ptr(d_rem), stream()),
+                   "gz_puct_remaining")
+        return d_rem.cpu().numpy()
 
     def select(self):
         _lib.check(self.lib.gz_puct_select(ptr(self.ws), self.n, self.S, ptr(self.d_leaves), ptr(self.d_active),
@@ -465,9 +520,9 @@ class PuctStepper:
             prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64).reshape(-1)).cuda()
         if not isinstance(value, torch.Tensor):
             value = torch.from_numpy(np.ascontiguousarray(value, np.float32).reshape(-1)).cuda()
-        if prior.dtype != torch.float64 or prior.numel() != self.n * 225 or value.dtype != torch.float32 \
-                or value.numel() != self.n:
-            raise ValueError("backup() wants prior float64 [n,225] and value float32 [n]")
+        if prior.dtype != torch.float64 or prior.numel() != self.rows * 225 or value.dtype != torch.float32 \
+                or value.numel() != self.rows:
+            raise ValueError("backup() wants prior float64 [n,225] and value float32 [n] (n K rows when batched)")
         _lib.check(self.lib.gz_puct_backup(ptr(self.ws), self.n, self.S, ptr(prior), ptr(value), stream()),
                    "gz_puct_backup")
 

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .boards import RECORD_DTYPE, STATE_DTYPE, words_to_cells
-from .device import GNWeights, PVWeights, ptr, puct_params, require_gpu, search_params, stream
+from .device import GNWeights, PVWeights, ptr, puct_leaves, puct_params, require_gpu, search_params, stream
 
 COUNTER_DTYPE = np.dtype([("records", "<i4"), ("leaves", "<i4"), ("records_dropped", "<i4"),
                           ("leaves_dropped", "<i4"), ("moves", "<i8"), ("games", "<i8"),
@@ -28,7 +28,7 @@ class SelfPlayEngine:
                  seed=0, max_depth=100, pv_weights=None, plies_per_step=1, game_id_base=0,
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
-                 rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25):
+                 rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -50,6 +50,12 @@ class SelfPlayEngine:
         over the empty cells, sampled on the device from the (seed, game id, ply) stream
         (GZ_PUCT_ROOT_NOISE, include/gzero.h), in lock-step and with tree_reuse alike:
         without it play from temp_plies on is a deterministic function of the position.
+        leaves_per_round K (search="puct" only; default 1 = the unbatched search): leaf
+        batching with virtual loss, K leaves per slot per round in one forward of
+        n_slots K rows, about 1 + ceil(num_simulations / K) rounds per move instead of
+        num_simulations + 1 (GZ_PUCT_LEAF_BATCH, include/gzero.h) -- for small n_slots,
+        where a forward of a few boards leaves the chip idle.  The search then
+        synchronises with the host once per block of rounds.  Not with tree_reuse.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -68,6 +74,11 @@ class SelfPlayEngine:
             raise ValueError("tree_reuse needs search='puct'")
         if dirichlet_alpha is not None and search != "puct":
             raise ValueError("dirichlet_alpha needs search='puct'")
+        self.leaves_per_round = int(leaves_per_round)
+        if self.leaves_per_round != 1 and search != "puct":
+            raise ValueError("leaves_per_round needs search='puct'")
+        if self.leaves_per_round > 1 and self.tree_reuse:
+            raise ValueError("leaves_per_round > 1 is not supported with tree_reuse")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -113,9 +124,11 @@ class SelfPlayEngine:
         self.puct = self.d_puct_ws = self.d_visits = None
         if search == "puct":
             self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision, dirichlet_alpha,
-                                    noise_eps)
-            self.d_puct_ws = torch.empty(self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S),
-                                         dtype=torch.uint8, device="cuda")
+                                    noise_eps, self.leaves_per_round)
+            K = puct_leaves(self.puct)
+            nbytes = self.lib.gz_selfplay_puct_batch_workspace_bytes(self.n_slots, S, K) if K else \
+                self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S)
+            self.d_puct_ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
             # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
             # has no uint16 arithmetic; a count is at most GZ_MAX_SIMULATIONS)
             self.d_visits = torch.zeros(self.record_cap * 225, dtype=torch.int16, device="cuda")
@@ -238,10 +251,11 @@ class SelfPlayEngine:
         lock-step plies too, and the trees are reset afterwards (the next round begins
         every slot with a fresh root)."""
         if self.search == "puct":
-            # (the 32 bytes of the base struct: the burn-in has no root noise, so the
-            # flag that would make the library read past the copy is cleared)
+            # (the 32 bytes of the base struct: the burn-in has no root noise and one leaf
+            # per round, so the flags that would make the library read past the copy are
+            # cleared)
             p = _lib.PuctParams.from_buffer_copy(self.puct)
-            p.flags &= ~_lib.GZ_PUCT_ROOT_NOISE
+            p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH)
             p.num_simulations = min(8, p.num_simulations)
             for _ in range(int(n_plies)):
                 self.d_counters.zero_()

@@ -169,13 +169,15 @@ def play_one_game(ai_black, ai_white, step_timeout: float = 10.0,
 def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium", beta: float = 0.2,
              seed: int = 0, n_slots: int = 4096, game_id_base: int = 0, model=None,
              plies_per_step: int = 16, planner_steps: int = 0, planner=None,
-             pv_mode: str = "tree", search: str = "reference", temp_plies: int = 12) -> Tuple[SimpleReplay, dict]:
+             pv_mode: str = "tree", search: str = "reference", temp_plies: int = 12,
+             leaves_per_round: int = 1) -> Tuple[SimpleReplay, dict]:
     """Play game ids [game_id_base, game_id_base + n_games) concurrently on the GPU.
 
     ``search="puct"``: the network-guided search (SelfPlayEngine(search="puct",
     temp_plies=...)); it needs ``model`` and ``planner_steps == 0`` and ignores beta and
     pv_mode.  stats["visits"] is then uint16 [len(replay), 225], the root visit counts
-    behind every replay entry, in replay order (the policy target).
+    behind every replay entry, in replay order (the policy target).  ``leaves_per_round``
+    K > 1: K leaves per game per round with virtual loss (SelfPlayEngine).
 
     With ``model`` (a GomokuModel) the policy-value network is evaluated on every
     node the searches create, as the reference does -- by default incrementally
@@ -201,7 +203,7 @@ def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium
                          plies_per_step=min(plies_per_step, 4) if tree else plies_per_step,
                          game_id_base=game_id_base, planner_steps=planner_steps,
                          planner_difficulty=difficulty, gn_weights=gnw, pv_mode="tree" if tree else "full",
-                         search=search, temp_plies=temp_plies)
+                         search=search, temp_plies=temp_plies, leaves_per_round=leaves_per_round)
     replay = SimpleReplay()
     done, rows = {}, {}
     moves = 0
@@ -246,7 +248,7 @@ def _check_search(search, model, planner_steps) -> bool:
 def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: str = "medium", seed: int = 0,
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
-                         noise_eps: float = 0.25):
+                         noise_eps: float = 0.25, leaves_per_round: int = 1):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -260,6 +262,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     (num_simulations + 1) rounds, in which a slot plays at least plies_per_step moves.
     dirichlet_alpha / noise_eps: Dirichlet noise at every search root
     (SelfPlayEngine(dirichlet_alpha=...)); None, the default, plays the noise-free games.
+    leaves_per_round K > 1: K leaves per game per round with virtual loss (not with
+    tree_reuse) -- a few games no longer run num_simulations + 1 near-empty forwards per ply.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -269,7 +273,7 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          pv_weights=model.device_weights(), plies_per_step=plies_per_step,
                          game_id_base=game_id_base, search="puct", temp_plies=temp_plies, tree_reuse=tree_reuse,
                          rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
-                         dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps)
+                         dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -579,7 +583,7 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   train_split: float = 0.9, batch_size: int = 128, epochs: int = 2, augment_ratio: float = 0.35,
                   planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8,
                   tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
-                  noise_eps: float = 0.25) -> dict:
+                  noise_eps: float = 0.25, leaves_per_round: int = 1) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -592,7 +596,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     soft-target loss) instead of the moves played.  One rank only: the record exchange
     does not carry visit rows yet.  ``tree_reuse`` (search="puct"): self-play keeps the
     subtree under each move for the next ply (selfplay_puct_device).  ``dirichlet_alpha``
-    / ``noise_eps`` (search="puct"): Dirichlet noise at the search roots of self-play."""
+    / ``noise_eps`` (search="puct"): Dirichlet noise at the search roots of self-play.
+    ``leaves_per_round`` (search="puct"): leaves per game per round of self-play's search."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     rank, ws = gdist.world()
@@ -604,6 +609,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError("tree_reuse needs search='puct'")
     if dirichlet_alpha is not None and search != "puct":
         raise ValueError("dirichlet_alpha needs search='puct'")
+    if int(leaves_per_round) != 1 and search != "puct":
+        raise ValueError("leaves_per_round needs search='puct'")
     t0 = time.time()
     id_lo = it * ws * games_per_iteration
     replay_base = id_lo + rank * games_per_iteration
@@ -612,7 +619,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         d, d_vis, n_rec, st = selfplay_puct_device(games_per_iteration, num_simulations=num_simulations,
                                                    difficulty=difficulty, seed=seed, game_id_base=replay_base,
                                                    model=model, temp_plies=temp_plies, tree_reuse=tree_reuse,
-                                                   dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps)
+                                                   dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
+                                                   leaves_per_round=leaves_per_round)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -686,7 +694,8 @@ def _broadcast_int(x: int) -> int:
 
 def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int] = None, models_dir: str = "models",
          num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
-         temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25):
+         temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
+         leaves_per_round: int = 1):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -694,7 +703,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     own games and trains data-parallel (gzero.train.DeviceTrainer).
     ``search="puct"`` (one rank): self-play by the network-guided search, training on
     its visit distributions (run_iteration); ``dirichlet_alpha`` / ``noise_eps`` add
-    Dirichlet noise at its search roots."""
+    Dirichlet noise at its search roots, ``leaves_per_round`` K > 1 evaluates K leaves per
+    game per round (worth it at the default 10 games per iteration)."""
     import math
     import os
     from gzero import dist as gdist
@@ -716,7 +726,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     for it in range(1, iterations + 1):
         res = run_iteration(model, trainer, it, games_per_iteration, num_simulations=num_simulations,
                             planner_steps=planner_steps, seed=seed, verbose=rank == 0, search=search,
-                            temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps)
+                            temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
+                            leaves_per_round=leaves_per_round)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

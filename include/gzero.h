@@ -327,7 +327,7 @@ typedef struct gz_puct_params {
     double c_puct;
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
     int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3: gz_puct_search's forward */
-    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE */
+    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH */
 } gz_puct_params;
 /* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).
  * With GZ_PUCT_ROOT_NOISE in flags the p given to gz_puct_begin, gz_puct_search,
@@ -353,8 +353,52 @@ typedef struct gz_puct_noise_params {
     double noise_alpha;
     double noise_eps;
 } gz_puct_noise_params;      /* 48 bytes */
+/* Leaf batching with virtual loss (opt-in): K leaves per game per round, so a move takes
+ * about 1 + ceil(S/K) rounds of n K rows instead of S+1 rounds of n -- for small n, where
+ * a forward of a few boards leaves the chip idle.  With GZ_PUCT_LEAF_BATCH in flags p
+ * points at a gz_puct_batch_params (its noise fields are read only with
+ * GZ_PUCT_ROOT_NOISE); without it nothing past the 32 (48) bytes is read and every entry
+ * point computes what it did before.  leaves_per_round K in 1..GZ_PUCT_MAX_LEAVES
+ * (GZ_ERR_ARG otherwise, before any GPU call).  Round 0 evaluates the root alone (row
+ * g K; the game's other rows are inactive).  In every later round a game descends up to
+ * K times, one descent after the other, while finished + in-flight simulations
+ * (visits[0] + vl[0]) <= S.  vl[x] counts the round's waiting leaves below node x and
+ * enters the score as that many visits, each lost by the selector (a node's W is from
+ * the selector's view):
+ *   n = visits[j] + vl[j],  q = n ? (W[j] - (double)vl[j]) / (double)n : 0.0,
+ *   score = q + ((c_puct * prior[c]) * sqrt((double)(visits[i] + vl[i]))) / (1.0 + (double)n)
+ * so K = 1 is the unbatched search bit for bit.  A descent that ends in a terminal node
+ * backs up at once and takes no row; one that selects a node created in this round and
+ * not yet evaluated (a collision) changes nothing and ends the game's selection for the
+ * round; any other creates a node, whose board goes to the game's next row.  The backup
+ * step stores and backs up the active rows of a game in ascending row order.  vl lives
+ * for one select launch only and is never stored.  The first descent of a round cannot
+ * collide, so every unfinished game completes at least one simulation per round, a move
+ * takes between 1 + ceil(S/K) and S+1 rounds, the root's visit row still sums to S and a
+ * tree never exceeds S+1 nodes; a game at its budget has only inactive rows.
+ * gz_puct_begin stores K in the workspace (and notes it for that workspace address on the
+ * host): gz_puct_select / gz_puct_backup then treat d_leaves, d_active, d_prior and
+ * d_value as [n K] rows, game g at rows g K .. g K + K - 1; gz_puct_finish and
+ * gz_puct_trees work unchanged.  The workspace is gz_puct_batch_workspace_bytes(n, S, K)
+ * (gz_selfplay_puct_batch_workspace_bytes for gz_selfplay_puct_run).  A round of only
+ * terminal descents has no active row although the search is not over, so a step-API
+ * caller asks gz_puct_remaining: d_remaining [n] = S + 1 - visits[0], 0 when the game is
+ * over.  gz_puct_search and gz_selfplay_puct_run run 1 + ceil(S/K) rounds, read the
+ * largest remaining count back and run ceil(left/K) more until it is 0: unlike the
+ * unbatched search, the batched one synchronises the calling host thread with the stream
+ * (one 4-byte read per block of rounds; it cannot be captured into a graph).  Tree reuse
+ * with K > 1 is not supported: gz_puct_reroot and gz_selfplay_puct_rounds return
+ * GZ_ERR_ARG. */
+#define GZ_PUCT_LEAF_BATCH 2
+#define GZ_PUCT_MAX_LEAVES 32
+typedef struct gz_puct_batch_params {
+    gz_puct_noise_params noise;   /* base and, with GZ_PUCT_ROOT_NOISE, the noise */
+    int32_t leaves_per_round;     /* K */
+    int32_t pad;
+} gz_puct_batch_params;      /* 56 bytes */
 /* includes the forward's workspace and gz_puct_search's leaf / output rows */
 size_t gz_puct_workspace_bytes(int32_t n, int32_t num_simulations);
+size_t gz_puct_batch_workspace_bytes(int32_t n, int32_t num_simulations, int32_t leaves_per_round);
 /* Step API (the caller supplies the evaluator): begin writes the root boards to
  * d_leaves [n][16] and d_active [n] (1 = the row wants an evaluation); after the
  * caller's backup of the roots, S times select (new leaves) and backup; d_prior
@@ -368,6 +412,8 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t num_simulations, const 
                    const float* d_value, void* stream);
 int gz_puct_finish(void* d_workspace, int32_t n, int32_t num_simulations, int32_t* d_moves, int32_t* d_visits,
                    double* d_root_q, void* stream);
+/* simulations left to each game's budget, 0 when the game is over (any search of this mode) */
+int gz_puct_remaining(void* d_workspace, int32_t n, int32_t num_simulations, int32_t* d_remaining, void* stream);
 /* begin, the S+1 rounds with gz_pv_forward(d_pv_weights, p->precision), finish */
 int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
                    const float* d_pv_weights, void* d_workspace, int32_t* d_moves, int32_t* d_visits,
@@ -385,6 +431,7 @@ int gz_puct_trees(const void* d_workspace, int32_t n, int32_t num_simulations, v
  * at the indices of its records (dropped with records that overflow).  Slot
  * statistics (gz_selfplay_draws): nodes evaluated, main draws (0 or 1 per ply), 0. */
 size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t num_simulations);
+size_t gz_selfplay_puct_batch_workspace_bytes(int32_t n_slots, int32_t num_simulations, int32_t leaves_per_round);
 int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                          void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
                          uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);

@@ -40,6 +40,20 @@ noise on and off.
 
     python tools/puct_bench.py --noise 0.3,0.25 --reuse --precisions f16x3 --steps 5 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/noise_bench.json
+
+--leaves K,K,... measures leaf batching with virtual loss (SelfPlayEngine(leaves_per_round=K))
+at small slot counts: for every count of --sweep-slots two child processes -- this build with
+one engine per K, and --lockstep-library (a build of the parent commit, which has no K > 1: the
+K = 1 baseline) -- take turns at one timed lock-step step (one move per slot) each, --steps
+times, with device events.  Before a timed step the child drives the same boards once more
+through the step API, untimed, and counts what the step will run: the rounds (with the block
+rule of gz_puct_search: 1 + ceil(S/K), then ceil(left/K) until nothing is left), the host
+reads and the active rows.  Reported per (slots, K): ms per move (= per step), rounds per
+move, ms per round and the share of forward rows that were empty (collisions, the budget's
+tail, round 0's K - 1 unused rows per game).
+
+    python tools/puct_bench.py --leaves 1,2,4,8,16 --precisions f16x3 --steps 5 \\
+        --lockstep-library parent/libgzero.so --out profiles/puct/batch_bench.json
 """
 import argparse
 import json
@@ -70,6 +84,11 @@ ap.add_argument("--noise", default=None, metavar="ALPHA,EPS", help="measure the 
 ap.add_argument("--distinct-plies", type=int, default=8, help="--noise: plies of the distinct-positions count")
 ap.add_argument("--noise-child", default=None, metavar="MODE:NOISE",
                 help="(child) lockstep or reuse, then off or ALPHA,EPS: time steps on request")
+ap.add_argument("--leaves", default=None, metavar="K,K,...",
+                help="measure leaf batching (SelfPlayEngine(leaves_per_round=K)) over --sweep-slots (see above)")
+ap.add_argument("--sweep-slots", default="1,8,64,256", help="--leaves: the slot counts (comma-separated)")
+ap.add_argument("--leaves-child", default=None, metavar="K,K,...",
+                help="(child) one engine per K at --slots: time steps on request")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 precisions = a.precisions.split(",")
@@ -325,8 +344,175 @@ def distinct_positions(prec, spec):
     return {"distinct": n, "slots_in_their_first_game": int(first.sum())}
 
 
+def count_rounds(eng, K, w):
+    """What the engine's next step will run, from one untimed search of the same boards
+    through the step API: (rounds, host reads, active rows, rows) -- the rounds by the block
+    rule of gz_puct_search (unbatched: S + 1 rounds, no read)."""
+    import torch
+    from gzero import device
+    S = a.sims
+    states, gids = eng.boards()
+    st = device.PuctStepper(states, gids, eng.puct)
+    d_probs = torch.empty(st.rows * 225, device="cuda")
+    d_prior = torch.empty(st.rows * 225, dtype=torch.float64, device="cuda")
+    left, active = [], 0
+    while not left or left[-1] > 0:
+        if left:
+            st.select()
+        active += int(st.d_active.sum().item())
+        _, d_value, _ = device.pv_forward_dev(w, st.d_leaves, st.rows, d_probs=d_probs, d_prior=d_prior)
+        st.backup(d_prior, d_value)
+        left.append(int(st.remaining().max()))
+    if st.K == 0:
+        assert len(left) == S + 1
+        return S + 1, 0, active, (S + 1) * st.rows
+    todo, ran, reads = 1 + -(-S // K), 0, 0
+    while True:
+        ran += todo
+        reads += 1
+        rest = left[min(ran, len(left)) - 1]
+        if rest == 0:
+            break
+        todo = -(-rest // K)
+    return ran, reads, active, ran * st.rows
+
+
+def leaves_child():
+    """One engine per K of --leaves-child at --slots.  Per "step K" on stdin: that engine's
+    next step counted (count_rounds; not on a build without gz_puct_remaining, the parent's,
+    whose K = 1 step is S + 1 rounds) and timed with device events."""
+    import ctypes
+    import torch
+    from gzero import _lib
+    from gzero.selfplay import SelfPlayEngine
+    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build lacks the newer entry points
+    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    can_count = hasattr(have, "gz_puct_remaining")
+    S, n = a.sims, a.slots
+    w = bench_weights(precisions[0], 1.0)
+    engines = {}
+    for K in (int(x) for x in a.leaves_child.split(",")):
+        kw = {"leaves_per_round": K} if K > 1 else {}
+        eng = SelfPlayEngine(n_slots=n, num_simulations=S, seed=1, pv_weights=w, search="puct",
+                             temp_plies=a.temp_plies, **kw)
+        eng.advance(a.burn)
+        eng.step()
+        engines[K] = eng
+    torch.cuda.synchronize()
+    print("READY " + torch.cuda.get_device_name(0), flush=True)
+    for line in sys.stdin:
+        word = line.split()
+        if len(word) != 2 or word[0] != "step":
+            break
+        K = int(word[1])
+        eng = engines[K]
+        rounds, reads, active, rows = count_rounds(eng, K, w) if can_count else (S + 1, 0, -1, (S + 1) * n)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.step()
+        e1.record()
+        torch.cuda.synchronize()
+        c = eng.counters()
+        assert c["records_dropped"] == 0 and c["moves"] == n
+        print(f"STEP_MS {e0.elapsed_time(e1)!r} {rounds} {reads} {active} {rows}", flush=True)
+
+
+device_name = [None]
+
+
+def leaves_run(prec, slots, ks):
+    """This build's engines (one per K) and the parent build's K = 1 engine at `slots`,
+    taking turns at one timed step each."""
+    S = a.sims
+    kids = {}
+    try:
+        for name, spec, library in (("this", ",".join(str(k) for k in ks), None), ("parent", "1", a.lockstep_library)):
+            env = dict(os.environ)
+            if library:
+                env["GZ_LIBRARY"] = os.path.abspath(library)
+            kids[name] = subprocess.Popen(
+                [sys.executable, os.path.abspath(__file__), "--leaves-child", spec, "--slots", str(slots), "--sims",
+                 str(S), "--burn", str(a.burn), "--precisions", prec, "--temp-plies", str(a.temp_plies)],
+                env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+        for name, kid in kids.items():
+            ready = kid.stdout.readline().strip()
+            if not ready.startswith("READY"):
+                sys.exit(f"leaves child {name} at {slots} slots failed ({kid.poll()})")
+            device_name[0] = ready[len("READY "):]
+
+        def step(name, K):
+            kid = kids[name]
+            kid.stdin.write(f"step {K}\n")
+            kid.stdin.flush()
+            line = kid.stdout.readline().split()
+            if len(line) != 6 or line[0] != "STEP_MS":
+                sys.exit(f"leaves child {name} at {slots} slots failed ({kid.poll()}): {line}")
+            return [float(line[1])] + [int(x) for x in line[2:]]
+
+        raw = {"parent": []}
+        raw.update({K: [] for K in ks})
+        for _ in range(a.steps):
+            for K in ks:
+                raw[K].append(step("this", K))
+                raw["parent"].append(step("parent", 1))
+    finally:
+        for kid in kids.values():
+            kid.stdin.close()
+        for kid in kids.values():
+            kid.wait(timeout=120)
+    out = {}
+    for key, rows in raw.items():
+        ms = [r[0] for r in rows]
+        r = {"step_ms": ms, "ms_per_move": median(ms), "rounds_per_move": [x[1] for x in rows],
+             "rounds_per_move_median": median([x[1] for x in rows]),
+             "ms_per_round": median([x[0] / x[1] for x in rows]), "host_reads_per_move": [x[2] for x in rows]}
+        if rows[0][3] >= 0:
+            r["empty_row_share"] = 1.0 - sum(x[3] for x in rows) / sum(x[4] for x in rows)
+            r["forward_rows_per_round"] = rows[0][4] // rows[0][1]
+        out["parent_k1" if key == "parent" else f"k{key}"] = r
+    base = out["parent_k1"]["ms_per_move"]
+    for key, r in out.items():
+        r["ms_per_move_over_parent_k1"] = r["ms_per_move"] / base
+    print(f"{prec} {slots} slots: parent K=1 {base:.2f} ms/move ({out['parent_k1']['ms_per_round']:.4f} ms/round); " +
+          "; ".join(f"K={K} {out[f'k{K}']['ms_per_move']:.2f} ms/move, {out[f'k{K}']['rounds_per_move_median']:g} "
+                    f"rounds, {out[f'k{K}']['ms_per_round']:.4f} ms/round, empty "
+                    f"{out[f'k{K}'].get('empty_row_share', float('nan')):.3f}" for K in ks), flush=True)
+    return out
+
+
 if a.forward_only:
     forward_only()
+    sys.exit(0)
+if a.leaves_child is not None:
+    leaves_child()
+    sys.exit(0)
+if a.leaves:
+    prec = precisions[0]
+    ks = [int(x) for x in a.leaves.split(",")]
+    res = {"config": {"simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies, "precision": prec,
+                      "steps": a.steps, "leaves": ks,
+                      "timing": "device events around one lock-step step (one move per slot); two child processes "
+                                "(this build: one engine per K; the parent build: K = 1) take turns",
+                      "rounds": "counted by an untimed search of the same boards through the step API before "
+                                "each timed step, with gz_puct_search's block rule; empty_row_share = 1 - active "
+                                "rows / (rounds x slots x K), round 0's K - 1 unused rows per game included",
+                      "parent_library": "another build (--lockstep-library)" if a.lockstep_library else "this build",
+                      "unchanged_path": f"{a.slots} slots, K = 1 (the flag clear) against the parent build"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    for slots in (int(x) for x in a.sweep_slots.split(",") if x):
+        res["results"][f"slots_{slots}"] = leaves_run(prec, slots, ks)
+    if a.slots > 0:
+        res["results"][f"unchanged_path_slots_{a.slots}"] = leaves_run(prec, a.slots, [1])
+    res["device"] = device_name[0]
+    print("PUCT_LEAVES_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.noise_child is not None:
     noise_child()
