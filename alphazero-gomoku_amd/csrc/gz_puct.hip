@@ -114,6 +114,33 @@
 // Batched workspace (gz_puct_batch_workspace_bytes(n, S, K)): PuctCfg and the trees as
 // above, then pend i16 [n][K] (the node of every active row), 256 bytes for the
 // remaining count, the round buffers and the forward's workspace for n K rows.
+//
+// Self-play workspace (gz_selfplay_puct_workspace_bytes(n, S); gz_selfplay_puct_layout gives
+// the offsets), every part al256: boards gz_board_state [n], game ids i64 [n], moves i32
+// [n], stats gz_search_stats [n], visits i32 [n][225], root_q f64 [n], then
+//   pend   u16 [n][200][225]   the visit rows of every slot's game in progress
+//   the PUCT block             the workspace above for n games
+// Capacity and active count (gz_selfplay_puct_run_active, gz_selfplay_puct_rounds_active):
+// n is the capacity, which places every part; a run of the first n_active <= n slots
+// launches n_active workgroups, forwards n_active (K) rows and leaves the rest alone --
+// the per-slot indexing (tree_of, pend + s 200 225, leaf row s) is the same either way.
+//
+// Slot compaction (gz_selfplay_puct_compact; in place).  With a active slots among the
+// first n_active, the holes are the idle slots below a and the fillers the active ones at
+// or above a; there are equally many, and the k-th filler goes to the k-th hole (both
+// ascending).  Sources (>= a) and destinations (< a) are disjoint, so all pairs move at
+// once without a second copy of the trees or of pend; the slot order is not preserved.
+//   1. puct_compact_plan_kernel   one workgroup: counts a, ranks holes and fillers, writes
+//                                 the pair lists, d_order and d_n_active;
+//   2. puct_compact_move_kernel   pair x part: the filler's pend rows [0, n_moves) and, for
+//                                 the reuse engine, its PuctHdr and rows [0, n_nodes) of
+//                                 each tree array to the hole's places, byte for byte
+//                                 (16-byte words between the unaligned ends of a span);
+//   3. puct_compact_swap_kernel   the two slot buffers trade places (after 2, which reads
+//                                 n_moves from the filler's slot where it was).
+// The launches are sized for the most pairs there can be, n_active / 2; a workgroup past
+// the device's pair count leaves at once.  What a hole held, and a filler's old place, are
+// dead: an idle slot is never searched, and a later filler overwrites all that is read.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -1121,6 +1148,140 @@ __global__ __launch_bounds__(WAVE) void puct_root_noise_kernel(const gz_board_st
         if (lane + WAVE * k < GZ_CELLS) out[(size_t)g * GZ_CELLS + lane + WAVE * k] = eta[k];
 }
 
+// ---------------------------------------------------------------- slot compaction
+// gz_selfplay_puct_compact (the header comment has the scheme).  The plan in the
+// workspace: int32 n_pairs (16 bytes), holes [cap], fillers [cap].
+constexpr int CP_THREADS = 256;
+constexpr int CP_PARTS = 8;  // workgroups that share the bytes of one pair
+
+// One workgroup scans the first n slots in tiles of 1024 (the ballot and prefix scheme of
+// selfplay_order_kernel): pass 0 counts the active slots, a; pass 1 ranks the holes (idle,
+// index < a) and the fillers (active, index >= a), each ascending; then the k-th filler is
+// paired with the k-th hole.  order[s] = s except at the pairs, which trade places.
+__global__ __launch_bounds__(1024) void puct_compact_plan_kernel(const char* slots, int n, int cap, int32_t* order,
+                                                                 int32_t* n_active, int32_t* plan) {
+    __shared__ int wsum[2][16];
+    __shared__ int carry[2], total;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int32_t* holes = plan + 4;
+    int32_t* fillers = holes + cap;
+    for (int pass = 0; pass < 2; pass++) {
+        if (tid == 0) carry[0] = carry[1] = 0;
+        __syncthreads();
+        for (int t0 = 0; t0 < n; t0 += 1024) {
+            const int s = t0 + tid;
+            const bool in = s < n;
+            bool act = false;
+            if (in) {
+                const SlotHeader* h = slot_of(slots, s);
+                act = h->game_id < h->game_id_end;
+            }
+            // (pass 0: x = active; pass 1: x = hole, y = filler)
+            const bool x = pass == 0 ? act : (in && !act && s < total);
+            const bool y = pass == 1 && act && s >= total;
+            const uint64_t mx = __ballot(x), my = __ballot(y);
+            if (lane == 0) {
+                wsum[0][wave] = __popcll(mx);
+                wsum[1][wave] = __popcll(my);
+            }
+            __syncthreads();
+            int bx = carry[0], by = carry[1];
+            for (int w = 0; w < wave; w++) {
+                bx += wsum[0][w];
+                by += wsum[1][w];
+            }
+            const uint64_t below = (1ull << lane) - 1;
+            if (pass == 1) {
+                if (x) holes[bx + __popcll(mx & below)] = s;
+                if (y) fillers[by + __popcll(my & below)] = s;
+                if (in && !x && !y) order[s] = s;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                for (int w = 0; w < 16; w++) {
+                    carry[0] += wsum[0][w];
+                    carry[1] += wsum[1][w];
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0 && pass == 0) {
+            total = carry[0];
+            *n_active = carry[0];
+        }
+        __syncthreads();
+    }
+    // (as many fillers as holes: a minus the active slots below a, either way)
+    const int pairs = carry[0] < carry[1] ? carry[0] : carry[1];
+    if (tid == 0) plan[0] = pairs;
+    __threadfence_block();  // the lists are written before other threads of the workgroup read them
+    __syncthreads();
+    for (int k = tid; k < pairs; k += 1024) {
+        const int h = holes[k], f = fillers[k];
+        order[h] = f;
+        order[f] = h;
+    }
+}
+
+// nbytes from src to dst, which are congruent mod 16: this workgroup's share (part of
+// CP_PARTS) of the 16-byte words between the unaligned ends, and the ends by part 0
+__device__ inline void copy_span(char* dst, const char* src, size_t nbytes, int part) {
+    size_t head = (16 - ((size_t)src & 15)) & 15;
+    if (head > nbytes) head = nbytes;
+    const size_t words = (nbytes - head) / 16;
+    const uint4* a = (const uint4*)(src + head);
+    uint4* b = (uint4*)(dst + head);
+    for (size_t i = (size_t)part * CP_THREADS + threadIdx.x; i < words; i += (size_t)CP_PARTS * CP_THREADS) b[i] = a[i];
+    if (part == 0 && threadIdx.x < 16) {
+        const size_t t = head + words * 16 + threadIdx.x;
+        if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+        if (t < nbytes) dst[t] = src[t];
+    }
+}
+
+// Pair k (blockIdx.x), part blockIdx.y: the filler's pending visit rows [0, n_moves) and,
+// with trees, its tree (the header and rows [0, n_nodes) of every array) to the hole's
+// places.  The slots are still where they were (puct_compact_swap_kernel runs afterwards).
+__global__ __launch_bounds__(CP_THREADS) void puct_compact_move_kernel(const char* slots, const int32_t* plan, int cap,
+                                                                       int S, int trees, char* ws, uint16_t* pend) {
+    const int k = blockIdx.x, part = blockIdx.y;
+    if (k >= plan[0]) return;
+    const int h = plan[4 + k], f = plan[4 + cap + k];
+    int rows = slot_of(slots, f)->n_moves;
+    rows = rows < 0 ? 0 : (rows > GZ_MAX_GAME_PLIES ? GZ_MAX_GAME_PLIES : rows);
+    const size_t per_slot = (size_t)GZ_MAX_GAME_PLIES * GZ_CELLS * 2;
+    copy_span((char*)pend + h * per_slot, (const char*)pend + f * per_slot, (size_t)rows * GZ_CELLS * 2, part);
+    if (!trees) return;
+    const size_t M = (size_t)S + 1;
+    const char* src = ws + 256 + f * game_stride_for(S);
+    char* dst = ws + 256 + h * game_stride_for(S);
+    int nn = ((const PuctHdr*)src)->n_nodes;
+    nn = nn < 0 ? 0 : (nn > S + 1 ? S + 1 : nn);
+    copy_span(dst, src, sizeof(PuctHdr), part);
+    // W, prior, visits, value, board, child, parent, move, term: bytes per node, as tree_of
+    const int width[9] = {8, 1800, 4, 4, 64, 450, 2, 1, 1};
+    size_t off = sizeof(PuctHdr);
+#pragma unroll
+    for (int a = 0; a < 9; a++) {
+        copy_span(dst + off, src + off, (size_t)width[a] * nn, part);
+        off += width[a] * M;
+    }
+}
+
+// the slot buffers of pair k trade places (16-byte words)
+__global__ __launch_bounds__(CP_THREADS) void puct_compact_swap_kernel(char* slots, const int32_t* plan, int cap) {
+    const int k = blockIdx.x, part = blockIdx.y;
+    if (k >= plan[0]) return;
+    const size_t sb = slot_stride_bytes();
+    uint4* a = (uint4*)(slots + plan[4 + k] * sb);
+    uint4* b = (uint4*)(slots + plan[4 + cap + k] * sb);
+    for (size_t i = (size_t)part * CP_THREADS + threadIdx.x; i < sb / 16; i += (size_t)CP_PARTS * CP_THREADS) {
+        const uint4 x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
 int check_alpha(const char* who, double alpha) {
@@ -1225,6 +1386,8 @@ RoundBufs carve_rows(char* p, size_t n) {
     return r;
 }
 
+// (n: the game count the workspace was sized for -- a search of fewer games on it finds
+// every buffer where the full one does)
 RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) { return carve_rows((char*)ws + rounds_offset(n, S), n); }
 
 // the batched workspace after the trees: pend i16 [n][K], the remaining count, then the
@@ -1261,48 +1424,74 @@ int finish_impl(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_vis
     return gz_check_launch("puct_finish_kernel");
 }
 
-int select_batch_impl(void* ws, int32_t n, int32_t S, int32_t K, uint32_t* d_leaves, int32_t* d_active, void* stream) {
-    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n, S));
+// n_cap: the game count that carved the workspace (the place of pend), n <= n_cap games run
+int select_batch_impl(void* ws, int32_t n_cap, int32_t n, int32_t S, int32_t K, uint32_t* d_leaves, int32_t* d_active,
+                      void* stream) {
+    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n_cap, S));
     puct_select_batch_kernel<<<n, WAVE, 2 * ((size_t)S + 1), as_stream(stream)>>>((char*)ws, n, S, K, pend, d_leaves,
                                                                                    d_active);
     return gz_check_launch("puct_select_batch_kernel");
 }
 
-int backup_batch_impl(void* ws, int32_t n, int32_t S, int32_t K, const double* d_prior, const float* d_value,
-                      const PuctNoise& nz, void* stream) {
-    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n, S));
+int backup_batch_impl(void* ws, int32_t n_cap, int32_t n, int32_t S, int32_t K, const double* d_prior,
+                      const float* d_value, const PuctNoise& nz, void* stream) {
+    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n_cap, S));
     puct_backup_batch_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, K, pend, d_prior, d_value, nz);
     return gz_check_launch("puct_backup_batch_kernel");
+}
+
+// gz_puct_begin on a workspace carved for n_cap games, of which the first n begin
+int begin_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n_cap, int32_t n,
+               const gz_puct_params* p, void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream) {
+    if (!p) return gz_fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
+    int rc = check_S("gz_puct_begin", n, p->num_simulations);
+    if (rc) return rc;
+    PuctNoise nz;
+    rc = read_noise("gz_puct_begin", p, nz);
+    if (rc) return rc;
+    int K;
+    rc = read_leaves("gz_puct_begin", p, K);
+    if (rc) return rc;
+    rc = check_rows("gz_puct_begin", n_cap, K);
+    if (rc) return rc;
+    if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
+        return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
+    if (n == 0) return GZ_OK;
+    note_leaves(d_workspace, K);
+    int16_t* pend = K > 0 ? (int16_t*)((char*)d_workspace + rounds_offset(n_cap, p->num_simulations)) : nullptr;
+    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, K, pend,
+                                                         (char*)d_workspace, d_leaves, d_active);
+    return gz_check_launch("puct_begin_kernel");
 }
 
 // The batched search: the root round, ceil(S/K) rounds of n K rows, then one int32 read
 // back -- the largest remaining count -- and ceil(left/K) more rounds until it is 0.
 // Every unfinished game completes at least one simulation per round, so the count falls.
-int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
-                      int32_t K, const float* d_pv_weights, void* ws, int32_t* d_moves, int32_t* d_visits,
-                      double* d_root_q, gz_search_stats* d_stats, void* stream) {
+int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n_cap, int32_t n,
+                      const gz_puct_params* p, int32_t K, const float* d_pv_weights, void* ws, int32_t* d_moves,
+                      int32_t* d_visits, double* d_root_q, gz_search_stats* d_stats, void* stream) {
     const int S = p->num_simulations;
-    const BatchBufs b = carve_batch(ws, n, S, K);
+    const BatchBufs b = carve_batch(ws, n_cap, S, K);
     const RoundBufs& r = b.r;
     hipStream_t st = as_stream(stream);
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
     if (rc) return rc;
-    rc = gz_puct_begin(d_boards, d_game_ids, n, p, ws, r.leaves, r.active, stream);
+    rc = begin_impl(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
     if (rc) return rc;
     int todo = 1 + (S + K - 1) / K;
     bool root = true;
     while (todo > 0) {
         for (int round = 0; round < todo; round++) {
             if (!root) {
-                rc = select_batch_impl(ws, n, S, K, r.leaves, r.active, stream);
+                rc = select_batch_impl(ws, n_cap, n, S, K, r.leaves, r.active, stream);
                 if (rc) return rc;
             }
             root = false;
             rc = gz_pv_forward(d_pv_weights, r.leaves, n * K, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
                                p->precision, stream);
             if (rc) return rc;
-            rc = backup_batch_impl(ws, n, S, K, r.prior, r.value, nz, stream);
+            rc = backup_batch_impl(ws, n_cap, n, S, K, r.prior, r.value, nz, stream);
             if (rc) return rc;
         }
         int32_t left = 0;
@@ -1320,22 +1509,24 @@ int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids,
     return finish_impl(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
 }
 
-int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
-                const float* d_pv_weights, void* ws, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
-                gz_search_stats* d_stats, void* stream) {
+// The search of the first n games on a workspace sized and carved for n_cap (n <= n_cap):
+// every grid, the forward's rows and the remaining count cover those n games only.
+int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n_cap, int32_t n,
+                const gz_puct_params* p, const float* d_pv_weights, void* ws, int32_t* d_moves, int32_t* d_visits,
+                double* d_root_q, gz_search_stats* d_stats, void* stream) {
     int K = 0;
     if (p->flags & GZ_PUCT_LEAF_BATCH) {
         int rc = read_leaves("gz_puct_search", p, K);
         if (rc) return rc;
-        return search_batch_impl(d_boards, d_game_ids, n, p, K, d_pv_weights, ws, d_moves, d_visits, d_root_q, d_stats,
-                                 stream);
+        return search_batch_impl(d_boards, d_game_ids, n_cap, n, p, K, d_pv_weights, ws, d_moves, d_visits, d_root_q,
+                                 d_stats, stream);
     }
     const int S = p->num_simulations;
-    const RoundBufs r = carve_rounds(ws, n, S);
+    const RoundBufs r = carve_rounds(ws, n_cap, S);
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
     if (rc) return rc;
-    rc = gz_puct_begin(d_boards, d_game_ids, n, p, ws, r.leaves, r.active, stream);
+    rc = begin_impl(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
     if (rc) return rc;
     for (int round = 0; round <= S; round++) {
         if (round > 0) {
@@ -1400,6 +1591,76 @@ SelfplayWs carve_selfplay(void* ws, int32_t n) {
     return w;
 }
 
+// gz_selfplay_puct_run(_active): n_slots sized and carved the workspace, the first n plays
+int run_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, const gz_puct_params* p,
+             const float* d_pv_weights, void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
+             uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
+    int rc = check_search_args(who, p, n_slots);
+    if (rc) return rc;
+    if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
+        !d_pv_weights || !d_visits)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": bad arguments");
+    if (n < 1 || n > n_slots) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n_active out of range [1, n_slots]");
+    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
+    hipStream_t st = as_stream(stream);
+    for (int it = 0; it < n_plies; it++) {
+        rc = gz_selfplay_boards(d_slots, n, p->num_simulations, w.boards, w.gids, stream);
+        if (rc) return rc;
+        rc = search_impl(w.boards, w.gids, n_slots, n, p, d_pv_weights, w.puct, w.moves, w.visits, w.root_q, w.stats,
+                         stream);
+        if (rc) return rc;
+        puct_stash_kernel<<<n, WAVE, 0, st>>>(w.boards, w.moves, w.visits, n, w.pend);
+        rc = gz_check_launch("puct_stash_kernel");
+        if (rc) return rc;
+        rc = gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
+                                         d_visits, stream);
+        if (rc) return rc;
+    }
+    return GZ_OK;
+}
+
+// gz_selfplay_puct_rounds(_active), as run_impl
+int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, const gz_puct_params* p,
+                const float* d_pv_weights, void* d_workspace, int32_t n_rounds, gz_record* d_records,
+                int32_t record_cap, uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
+    int rc = check_search_args(who, p, n_slots);
+    if (rc) return rc;
+    if (!d_slots || n_slots <= 0 || n_rounds < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
+        !d_pv_weights || !d_visits)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": bad arguments");
+    int K;
+    rc = read_leaves(who, p, K);
+    if (rc) return rc;
+    if (K > 1)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": tree reuse with leaves_per_round > 1 is not supported");
+    if (n < 1 || n > n_slots) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n_active out of range [1, n_slots]");
+    const int S = p->num_simulations;
+    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
+    const RoundBufs r = carve_rounds(w.puct, n_slots, S);
+    hipStream_t st = as_stream(stream);
+    PuctNoise nz;
+    rc = read_noise(who, p, nz);
+    if (rc) return rc;
+    for (int it = 0; it < n_rounds; it++) {
+        puct_advance_kernel<<<n, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n, *p, nz, (char*)w.puct,
+                                                                   w.moves, w.stats, w.pend);
+        rc = gz_check_launch("puct_advance_kernel");
+        if (rc) return rc;
+        rc = gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
+                                         d_visits, stream);
+        if (rc) return rc;
+        puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, (char*)w.puct, r.leaves, r.active);
+        rc = gz_check_launch("puct_round_kernel");
+        if (rc) return rc;
+        rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
+                           p->precision, stream);
+        if (rc) return rc;
+        rc = backup_impl(w.puct, n, S, r.prior, r.value, nz, stream);
+        if (rc) return rc;
+    }
+    return GZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1416,25 +1677,7 @@ size_t gz_puct_workspace_bytes(int32_t n, int32_t S) {
 
 int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
                   void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream) {
-    if (!p) return gz_fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
-    int rc = check_S("gz_puct_begin", n, p->num_simulations);
-    if (rc) return rc;
-    PuctNoise nz;
-    rc = read_noise("gz_puct_begin", p, nz);
-    if (rc) return rc;
-    int K;
-    rc = read_leaves("gz_puct_begin", p, K);
-    if (rc) return rc;
-    rc = check_rows("gz_puct_begin", n, K);
-    if (rc) return rc;
-    if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
-        return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
-    if (n == 0) return GZ_OK;
-    note_leaves(d_workspace, K);
-    int16_t* pend = K > 0 ? (int16_t*)((char*)d_workspace + rounds_offset(n, p->num_simulations)) : nullptr;
-    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, K, pend,
-                                                         (char*)d_workspace, d_leaves, d_active);
-    return gz_check_launch("puct_begin_kernel");
+    return begin_impl(d_boards, d_game_ids, n, n, p, d_workspace, d_leaves, d_active, stream);
 }
 
 int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, int32_t* d_active, void* stream) {
@@ -1443,7 +1686,7 @@ int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, 
     if (n > 0 && (!d_workspace || !d_leaves || !d_active)) return gz_fail(GZ_ERR_ARG, "gz_puct_select: bad arguments");
     if (n == 0) return GZ_OK;
     const int K = leaves_of(d_workspace);
-    if (K > 0) return select_batch_impl(d_workspace, n, S, K, d_leaves, d_active, stream);
+    if (K > 0) return select_batch_impl(d_workspace, n, n, S, K, d_leaves, d_active, stream);
     puct_select_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
     return gz_check_launch("puct_select_kernel");
 }
@@ -1457,7 +1700,7 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prio
     PuctNoise nz = {};
     nz.on = -1;  // as gz_puct_begin stored it in the workspace
     const int K = leaves_of(d_workspace);
-    if (K > 0) return backup_batch_impl(d_workspace, n, S, K, d_prior, d_value, nz, stream);
+    if (K > 0) return backup_batch_impl(d_workspace, n, n, S, K, d_prior, d_value, nz, stream);
     return backup_impl(d_workspace, n, S, d_prior, d_value, nz, stream);
 }
 
@@ -1498,7 +1741,7 @@ int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, in
     if (n > 0 && (!d_boards || !d_game_ids || !d_pv_weights || !d_workspace || !d_moves))
         return gz_fail(GZ_ERR_ARG, "gz_puct_search: bad arguments");
     if (n == 0) return GZ_OK;
-    return search_impl(d_boards, d_game_ids, n, p, d_pv_weights, d_workspace, d_moves, d_visits, d_root_q, nullptr,
+    return search_impl(d_boards, d_game_ids, n, n, p, d_pv_weights, d_workspace, d_moves, d_visits, d_root_q, nullptr,
                        stream);
 }
 
@@ -1525,30 +1768,19 @@ size_t gz_selfplay_puct_batch_workspace_bytes(int32_t n_slots, int32_t S, int32_
            al256(m * 900) + al256(m * 8) + pend_bytes(n_slots) + gz_puct_batch_workspace_bytes(n_slots, S, K);
 }
 
+int gz_selfplay_puct_run_active(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_params* p,
+                                const float* d_pv_weights, void* d_workspace, int32_t n_plies, gz_record* d_records,
+                                int32_t record_cap, uint16_t* d_visits, gz_selfplay_counters* d_counters,
+                                void* stream) {
+    return run_impl("gz_selfplay_puct_run_active", d_slots, n_slots, n_active, p, d_pv_weights, d_workspace, n_plies,
+                    d_records, record_cap, d_visits, d_counters, stream);
+}
+
 int gz_selfplay_puct_run(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                          void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
                          uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
-    int rc = check_search_args("gz_selfplay_puct_run", p, n_slots);
-    if (rc) return rc;
-    if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
-        !d_pv_weights || !d_visits)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_run: bad arguments");
-    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
-    hipStream_t st = as_stream(stream);
-    for (int it = 0; it < n_plies; it++) {
-        rc = gz_selfplay_boards(d_slots, n_slots, p->num_simulations, w.boards, w.gids, stream);
-        if (rc) return rc;
-        rc = search_impl(w.boards, w.gids, n_slots, p, d_pv_weights, w.puct, w.moves, w.visits, w.root_q, w.stats,
-                         stream);
-        if (rc) return rc;
-        puct_stash_kernel<<<n_slots, WAVE, 0, st>>>(w.boards, w.moves, w.visits, n_slots, w.pend);
-        rc = gz_check_launch("puct_stash_kernel");
-        if (rc) return rc;
-        rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
-                                         d_visits, stream);
-        if (rc) return rc;
-    }
-    return GZ_OK;
+    return run_impl("gz_selfplay_puct_run", d_slots, n_slots, n_slots, p, d_pv_weights, d_workspace, n_plies, d_records,
+                    record_cap, d_visits, d_counters, stream);
 }
 
 int gz_puct_reroot(void* d_workspace, int32_t n, int32_t S, const int32_t* d_moves, uint32_t* d_leaves,
@@ -1574,45 +1806,66 @@ int gz_selfplay_puct_reset(void* d_workspace, int32_t n_slots, int32_t S, void* 
     return gz_check_launch("puct_reset_kernel");
 }
 
+int gz_selfplay_puct_rounds_active(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_params* p,
+                                   const float* d_pv_weights, void* d_workspace, int32_t n_rounds,
+                                   gz_record* d_records, int32_t record_cap, uint16_t* d_visits,
+                                   gz_selfplay_counters* d_counters, void* stream) {
+    return rounds_impl("gz_selfplay_puct_rounds_active", d_slots, n_slots, n_active, p, d_pv_weights, d_workspace,
+                       n_rounds, d_records, record_cap, d_visits, d_counters, stream);
+}
+
 int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                             void* d_workspace, int32_t n_rounds, gz_record* d_records, int32_t record_cap,
                             uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
-    int rc = check_search_args("gz_selfplay_puct_rounds", p, n_slots);
+    return rounds_impl("gz_selfplay_puct_rounds", d_slots, n_slots, n_slots, p, d_pv_weights, d_workspace, n_rounds,
+                       d_records, record_cap, d_visits, d_counters, stream);
+}
+
+int gz_selfplay_puct_layout(int32_t n_slots, int32_t S, int32_t K, size_t out[4]) {
+    int rc = check_S("gz_selfplay_puct_layout", n_slots, S);
     if (rc) return rc;
-    if (!d_slots || n_slots <= 0 || n_rounds < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
-        !d_pv_weights || !d_visits)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_rounds: bad arguments");
-    int K;
-    rc = read_leaves("gz_selfplay_puct_rounds", p, K);
-    if (rc) return rc;
-    if (K > 1)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_rounds: tree reuse with leaves_per_round > 1 is not supported");
-    const int S = p->num_simulations;
-    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
-    const RoundBufs r = carve_rounds(w.puct, n_slots, S);
-    hipStream_t st = as_stream(stream);
-    PuctNoise nz;
-    rc = read_noise("gz_selfplay_puct_rounds", p, nz);
-    if (rc) return rc;
-    for (int it = 0; it < n_rounds; it++) {
-        puct_advance_kernel<<<n_slots, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n_slots, *p, nz,
-                                                                         (char*)w.puct, w.moves, w.stats, w.pend);
-        rc = gz_check_launch("puct_advance_kernel");
-        if (rc) return rc;
-        rc = gz_internal_selfplay_commit(d_slots, n_slots, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
-                                         d_visits, stream);
-        if (rc) return rc;
-        puct_round_kernel<<<n_slots, WAVE, 0, st>>>((const char*)d_slots, n_slots, *p, (char*)w.puct,
-                                                                r.leaves, r.active);
-        rc = gz_check_launch("puct_round_kernel");
-        if (rc) return rc;
-        rc = gz_pv_forward(d_pv_weights, r.leaves, n_slots, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
-                           p->precision, stream);
-        if (rc) return rc;
-        rc = backup_impl(w.puct, n_slots, S, r.prior, r.value, nz, stream);
-        if (rc) return rc;
-    }
+    if (n_slots < 1 || K < 0 || K > GZ_PUCT_MAX_LEAVES || !out)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_layout: bad arguments");
+    const uintptr_t base = 4096;  // (any address: only the differences are used)
+    const SelfplayWs w = carve_selfplay((void*)base, n_slots);
+    out[0] = (size_t)((uintptr_t)w.pend - base);
+    out[1] = (size_t)((uintptr_t)w.puct - base);
+    out[2] = out[1] + 256;
+    out[3] = game_stride_for(S);
     return GZ_OK;
+}
+
+size_t gz_selfplay_puct_compact_workspace_bytes(int32_t n_slots) {
+    return al256(16 + 2 * (size_t)(n_slots > 0 ? n_slots : 0) * 4);
+}
+
+int gz_selfplay_puct_compact(void* d_slots, int32_t n_slots, int32_t n_active, int32_t S, int32_t K,
+                             int32_t move_trees, void* d_puct_workspace, int32_t* d_order, int32_t* d_n_active,
+                             void* d_workspace, void* stream) {
+    int rc = check_S("gz_selfplay_puct_compact", n_slots, S);
+    if (rc) return rc;
+    if (!d_slots || n_slots < 1 || !d_puct_workspace || !d_order || !d_n_active || !d_workspace)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: bad arguments");
+    if (n_active < 1 || n_active > n_slots)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: n_active out of range [1, n_slots]");
+    if (K < 0 || K > GZ_PUCT_MAX_LEAVES)  // (0: the unbatched search, as PuctCfg.leaves)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: leaves_per_round out of range [0, 32]");
+    if (K > 1 && move_trees)
+        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: tree reuse with leaves_per_round > 1 is not supported");
+    const SelfplayWs w = carve_selfplay(d_puct_workspace, n_slots);
+    int32_t* plan = (int32_t*)d_workspace;
+    hipStream_t st = as_stream(stream);
+    puct_compact_plan_kernel<<<1, 1024, 0, st>>>((const char*)d_slots, n_active, n_slots, d_order, d_n_active, plan);
+    rc = gz_check_launch("puct_compact_plan_kernel");
+    if (rc) return rc;
+    const int pairs = n_active / 2;  // at most: the count itself stays on the device
+    if (pairs == 0) return GZ_OK;
+    puct_compact_move_kernel<<<dim3(pairs, CP_PARTS), CP_THREADS, 0, st>>>((const char*)d_slots, plan, n_slots, S,
+                                                                          move_trees ? 1 : 0, (char*)w.puct, w.pend);
+    rc = gz_check_launch("puct_compact_move_kernel");
+    if (rc) return rc;
+    puct_compact_swap_kernel<<<dim3(pairs, CP_PARTS), CP_THREADS, 0, st>>>((char*)d_slots, plan, n_slots);
+    return gz_check_launch("puct_compact_swap_kernel");
 }
 
 int gz_puct_root_noise(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, uint64_t seed,

@@ -189,6 +189,13 @@ SIGNATURES = {
     "gz_selfplay_puct_reset": (ctypes.c_int, [_P, _I32, _I32, _P]),
     "gz_selfplay_puct_rounds": (ctypes.c_int, [_P, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32, _P,
                                                _P, _P]),
+    "gz_selfplay_puct_run_active": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P, _I32,
+                                                   _P, _P, _P]),
+    "gz_selfplay_puct_rounds_active": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(PuctParams), _P, _P, _I32, _P,
+                                                      _I32, _P, _P, _P]),
+    "gz_selfplay_puct_layout": (ctypes.c_int, [_I32, _I32, _I32, _P]),
+    "gz_selfplay_puct_compact_workspace_bytes": (_SZ, [_I32]),
+    "gz_selfplay_puct_compact": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "gz_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "gz_selfplay_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "gz_puct_remaining": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),

@@ -28,7 +28,8 @@ class SelfPlayEngine:
                  seed=0, max_depth=100, pv_weights=None, plies_per_step=1, game_id_base=0,
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
-                 rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1):
+                 rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1,
+                 compact_slots=False):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -59,6 +60,13 @@ class SelfPlayEngine:
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
+        compact_slots (search="puct" with a game_id_end only): :meth:`compact` works on this
+        PUCT engine (gz_selfplay_puct_compact, in place): active slots from the tail fill the
+        idle places in front, their pending visit rows and, with tree_reuse, their trees
+        moving with them.  The slot order is not preserved: after a compaction
+        :meth:`draws`, :meth:`boards` and every other per-slot view are permuted
+        (:attr:`d_order` holds the last permutation); a game's moves, visit rows and z are
+        the same with and without it.
         planner_steps > 0: BG-planner rollout plies (config 4); gn_weights = the
         planner's GraphNet/DQN blob (gzero.planner_nets) or a GNWeights.
         pv_mode: "full" = one full forward per node (gz_pv_forward); "tree" = the
@@ -84,6 +92,9 @@ class SelfPlayEngine:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
             if int(planner_steps) != 0:
                 raise ValueError("search='puct' has no rollouts: planner_steps must be 0")
+        self.compact_slots = bool(compact_slots)
+        if self.compact_slots and (search != "puct" or game_id_end is None):
+            raise ValueError("compact_slots needs search='puct' and a game_id_end")
         self.lib = require_gpu()
         self.n_slots = int(n_slots)
         self.n_active = self.n_slots  # the slots the launches run (the first n_active)
@@ -158,18 +169,35 @@ class SelfPlayEngine:
         if game_id_end is not None:
             _lib.check(self.lib.gz_selfplay_set_game_end(ptr(self.d_slots), self.n_slots, int(game_id_end), stream()),
                        "gz_selfplay_set_game_end")
+            self.d_n_active = torch.zeros(1, dtype=torch.int32, device="cuda")
+        self.d_order = None
+        if self.compact_slots:  # in place: no second slot buffer
+            self.d_compact_ws = torch.empty(self.lib.gz_selfplay_puct_compact_workspace_bytes(self.n_slots),
+                                            dtype=torch.uint8, device="cuda")
+            self.d_order = torch.zeros(self.n_slots, dtype=torch.int32, device="cuda")
+        elif game_id_end is not None:
             self.d_slots_alt = torch.empty_like(self.d_slots)
             self.d_compact_ws = torch.empty(self.lib.gz_selfplay_compact_workspace_bytes(self.n_slots),
                                             dtype=torch.uint8, device="cuda")
-            self.d_n_active = torch.zeros(1, dtype=torch.int32, device="cuda")
 
     def compact(self):
         """Launch gz_selfplay_compact: the active slots to the front of the slot buffer
         (the two buffers swap).  Returns the device int32 [1] active count; the caller
-        sets :attr:`n_active` from it once read (the next launches run that many)."""
+        sets :attr:`n_active` from it once read (the next launches run that many).
+        On a PUCT engine built with compact_slots: gz_selfplay_puct_compact among the first
+        :attr:`n_active` slots, in place -- the slots, their pending visit rows and (with
+        tree_reuse) their trees; the slot order, and with it :meth:`draws` and
+        :meth:`boards`, is permuted (d_order[:n_active]: the new index of each old slot)."""
+        if self.compact_slots:
+            if self.n_active > 0:
+                _lib.check(self.lib.gz_selfplay_puct_compact(
+                    ptr(self.d_slots), self.n_slots, self.n_active, self.puct.num_simulations, self.leaves_per_round,
+                    1 if self.tree_reuse else 0, ptr(self.d_puct_ws), ptr(self.d_order), ptr(self.d_n_active),
+                    ptr(self.d_compact_ws), stream()), "gz_selfplay_puct_compact")
+            return self.d_n_active
         if self.search == "puct":
-            # the pending visit rows live per slot in the workspace and would have to move too
-            raise ValueError("compact() is not available on a PUCT engine")
+            # the pending visit rows live per slot in the workspace and have to move too
+            raise ValueError("compact() on a PUCT engine needs compact_slots=True")
         if self.d_slots_alt is None:
             raise ValueError("compact() needs an engine built with game_id_end")
         _lib.check(self.lib.gz_selfplay_compact(ptr(self.d_slots), self.n_slots, ptr(self.d_slots_alt),
@@ -206,16 +234,19 @@ class SelfPlayEngine:
                    "gz_selfplay_run")
 
     def _puct_run(self, p, n_plies):
-        _lib.check(self.lib.gz_selfplay_puct_run(ptr(self.d_slots), self.n_slots, ctypes.byref(p),
-                                                 ptr(self.pv_weights.tensor), ptr(self.d_puct_ws), int(n_plies),
-                                                 ptr(self.d_records), self.record_cap, ptr(self.d_visits),
-                                                 ptr(self.d_counters), stream()), "gz_selfplay_puct_run")
+        # (n_slots carved the workspace; the first n_active slots run)
+        _lib.check(self.lib.gz_selfplay_puct_run_active(ptr(self.d_slots), self.n_slots, self.n_active,
+                                                        ctypes.byref(p), ptr(self.pv_weights.tensor),
+                                                        ptr(self.d_puct_ws), int(n_plies), ptr(self.d_records),
+                                                        self.record_cap, ptr(self.d_visits), ptr(self.d_counters),
+                                                        stream()), "gz_selfplay_puct_run_active")
 
     def _puct_rounds(self, n_rounds):
-        _lib.check(self.lib.gz_selfplay_puct_rounds(ptr(self.d_slots), self.n_slots, ctypes.byref(self.puct),
-                                                    ptr(self.pv_weights.tensor), ptr(self.d_puct_ws), int(n_rounds),
-                                                    ptr(self.d_records), self.record_cap, ptr(self.d_visits),
-                                                    ptr(self.d_counters), stream()), "gz_selfplay_puct_rounds")
+        _lib.check(self.lib.gz_selfplay_puct_rounds_active(ptr(self.d_slots), self.n_slots, self.n_active,
+                                                           ctypes.byref(self.puct), ptr(self.pv_weights.tensor),
+                                                           ptr(self.d_puct_ws), int(n_rounds), ptr(self.d_records),
+                                                           self.record_cap, ptr(self.d_visits), ptr(self.d_counters),
+                                                           stream()), "gz_selfplay_puct_rounds_active")
 
     def _puct_reset(self):
         _lib.check(self.lib.gz_selfplay_puct_reset(ptr(self.d_puct_ws), self.n_slots, self.puct.num_simulations,
@@ -257,7 +288,7 @@ class SelfPlayEngine:
             p = _lib.PuctParams.from_buffer_copy(self.puct)
             p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH)
             p.num_simulations = min(8, p.num_simulations)
-            for _ in range(int(n_plies)):
+            for _ in range(int(n_plies) if self.n_active > 0 else 0):
                 self.d_counters.zero_()
                 self._puct_run(p, 1)
             if self.tree_reuse:
@@ -343,6 +374,7 @@ class SelfPlayEngine:
         return d.cpu().numpy().view(np.uint16)
 
     def boards(self):
+        """(states, game ids) of every slot, in slot order (permuted by a compaction)."""
         out = torch.zeros(self.n_slots * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         gids = torch.zeros(self.n_slots, dtype=torch.int64, device="cuda")
         _lib.check(self.lib.gz_selfplay_boards(ptr(self.d_slots), self.n_slots, self.params.num_simulations,
@@ -353,7 +385,8 @@ class SelfPlayEngine:
     def draws(self):
         """int64 [n_slots, 3]: (predict calls, main-stream RNG draws, simulation-stream
         RNG draws) summed over every search each slot ran since the engine was created
-        (gz_selfplay_draws)."""
+        (gz_selfplay_draws).  The totals travel with the slot buffers: after a compaction
+        the rows are permuted (and, in the default mode, the active slots' come first)."""
         out = torch.zeros(self.n_slots * 3, dtype=torch.int64, device="cuda")
         _lib.check(self.lib.gz_selfplay_draws(ptr(self.d_slots), self.n_slots, ptr(out), stream()),
                    "gz_selfplay_draws")

@@ -248,7 +248,7 @@ def _check_search(search, model, planner_steps) -> bool:
 def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: str = "medium", seed: int = 0,
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
-                         noise_eps: float = 0.25, leaves_per_round: int = 1):
+                         noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -264,6 +264,12 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     (SelfPlayEngine(dirichlet_alpha=...)); None, the default, plays the noise-free games.
     leaves_per_round K > 1: K leaves per game per round with virtual loss (not with
     tree_reuse) -- a few games no longer run num_simulations + 1 near-empty forwards per ply.
+    compact=True (as selfplay_device): a slot whose wanted games are over goes idle instead
+    of refilling (game_id_end) and after every step the active slots fill the idle places
+    in front (SelfPlayEngine(compact_slots=True)), so the next step's forwards have only
+    the live games' rows; the active count rides in the step's one host read.  The rows,
+    visit rows and n are the same bytes either way; stats["moves_played"] no longer
+    counts the unwanted refill games' moves.  compact=False: continuous refill.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -273,7 +279,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          pv_weights=model.device_weights(), plies_per_step=plies_per_step,
                          game_id_base=game_id_base, search="puct", temp_plies=temp_plies, tree_reuse=tree_reuse,
                          rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
-                         dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round)
+                         dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round,
+                         game_id_end=game_id_base + n_games if compact else None, compact_slots=bool(compact))
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -299,7 +306,13 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
         gid, ply = rec64[:, 8], rec16[:, 36].to(torch.int64)
         first = ((slot_idx < cnt) & (gid >= lo) & (gid < hi) & (ply == 0)).sum().reshape(1)
         # the step's one host synchronisation: records, drops, moves, wanted games finished
-        c = torch.cat([eng.d_counters.view(torch.int64), first]).cpu().numpy()
+        # (and, compacting, the slots still active)
+        parts = [eng.d_counters.view(torch.int64), first]
+        if compact:
+            parts.append(eng.compact().to(torch.int64))
+        c = torch.cat(parts).cpu().numpy()
+        if compact:
+            eng.n_active = int(c[6])
         head = c[:2].view(np.int32)  # records, leaves, records_dropped, leaves_dropped
         if head[2]:
             raise RuntimeError(f"selfplay_puct_device: {int(head[2])} records dropped by the engine buffer")

@@ -466,6 +466,54 @@ int gz_selfplay_puct_reset(void* d_workspace, int32_t n_slots, int32_t num_simul
 int gz_selfplay_puct_rounds(void* d_slots, int32_t n_slots, const gz_puct_params* p, const float* d_pv_weights,
                             void* d_workspace, int32_t n_rounds, gz_record* d_records, int32_t record_cap,
                             uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);
+/* A workspace carved for its capacity and run for its active count.  The two entry
+ * points above with one more argument: n_slots is the capacity that sized and carved
+ * d_workspace (gz_selfplay_puct_workspace_bytes / gz_selfplay_puct_batch_workspace_bytes
+ * of n_slots), so the pending visit rows, the trees and the round buffers keep their
+ * places; every kernel grid, the forward's rows (n_active, or n_active K when batched)
+ * and the remaining count cover the first n_active slots only, 1 <= n_active <= n_slots.
+ * A game's moves and rows do not depend on n_active.  gz_selfplay_puct_run and
+ * gz_selfplay_puct_rounds are these with n_active = n_slots. */
+int gz_selfplay_puct_run_active(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_params* p,
+                                const float* d_pv_weights, void* d_workspace, int32_t n_plies, gz_record* d_records,
+                                int32_t record_cap, uint16_t* d_visits, gz_selfplay_counters* d_counters,
+                                void* stream);
+int gz_selfplay_puct_rounds_active(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_params* p,
+                                   const float* d_pv_weights, void* d_workspace, int32_t n_rounds,
+                                   gz_record* d_records, int32_t record_cap, uint16_t* d_visits,
+                                   gz_selfplay_counters* d_counters, void* stream);
+/* Byte offsets in the self-play workspace of n_slots slots (the same with and without
+ * leaf batching; leaves_per_round 0 or 1 = unbatched): out[0] the pending visit rows
+ * (uint16 [n_slots][200][225]), out[1] the PUCT block (the d_workspace of gz_puct_trees),
+ * out[2] the first tree (out[1] + 256), out[3] the per-game tree stride; the round
+ * buffers begin at out[2] + n_slots out[3]. */
+int gz_selfplay_puct_layout(int32_t n_slots, int32_t num_simulations, int32_t leaves_per_round, size_t out[4]);
+/* Slot compaction of a PUCT engine with a bounded game range (gz_selfplay_set_game_end),
+ * in place: among the first n_active slots a are active (game_id < game_id_end); the
+ * holes are the idle slots below a, the fillers the active slots at or above a -- equally
+ * many -- and the k-th filler goes to the k-th hole, both ascending.  Sources and
+ * destinations are disjoint, so the moves run in parallel and nothing needs a second copy
+ * of the trees or the pending rows; the order of the slots is NOT preserved (per-slot
+ * views such as gz_selfplay_draws and gz_selfplay_boards are permuted with them).
+ *   slot buffers      the pair trades places: d_slots stays a permutation of what it was;
+ *   pending rows      rows [0, n_moves) of the filler move to the hole's place;
+ *   trees             only with move_trees (the tree-reuse engine): the tree header and
+ *                     rows [0, n_nodes) of every array, byte for byte, reuse mark included
+ *                     (a tree belongs to its slot at the new index exactly when it did at
+ *                     the old one).  Lock-step and batched searches rebuild every tree
+ *                     each ply and pass move_trees = 0.
+ * What the hole held (its old tree and rows) is dead and stays as it is, as does the
+ * filler's old place.  d_order [n_active]: the new index of each old slot (the identity
+ * except at the pairs); *d_n_active = a; the caller then runs the first a slots
+ * (gz_selfplay_puct_run_active / _rounds_active).  No active slot below a, or no idle
+ * one: only d_order and d_n_active are written.  d_puct_workspace: the self-play
+ * workspace of n_slots slots; d_workspace: gz_selfplay_puct_compact_workspace_bytes(n_slots).
+ * GZ_ERR_ARG: n_active outside [1, n_slots], leaves_per_round outside [0, 32], or
+ * leaves_per_round > 1 with move_trees; nothing is launched then. */
+size_t gz_selfplay_puct_compact_workspace_bytes(int32_t n_slots);
+int gz_selfplay_puct_compact(void* d_slots, int32_t n_slots, int32_t n_active, int32_t num_simulations,
+                             int32_t leaves_per_round, int32_t move_trees, void* d_puct_workspace,
+                             int32_t* d_order, int32_t* d_n_active, void* d_workspace, void* stream);
 
 /* The noise sampler on its own (the device and host functions the search runs).
  * gz_puct_root_noise: d_eta [n][225] = eta at the empty cells of each board (ply =

@@ -54,6 +54,20 @@ tail, round 0's K - 1 unused rows per game).
 
     python tools/puct_bench.py --leaves 1,2,4,8,16 --precisions f16x3 --steps 5 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/batch_bench.json
+
+--compact measures slot compaction (training.selfplay_puct_device(compact=True)): one
+self-play iteration of G games on G slots, for every G of --compact-games, without root
+noise and with --compact-noise.  Three child processes -- this build compacting, this build
+with continuous refill (compact=False) and --lockstep-library (a build of the parent commit)
+with continuous refill -- take turns at one whole iteration each, --steps times; reported per
+child: seconds per iteration (wall clock around the call, median of the turns), steps, moves
+played, the mean and longest game and the device time of the compaction launches themselves.
+mean / longest game is the ratio the forward's row count alone predicts for seconds with
+compaction / without.  Then the path with compaction off: one lock-step step at --slots
+against the parent build, as --leaves 1 measures it.
+
+    python tools/puct_bench.py --compact --precisions f16x3 --steps 3 \\
+        --lockstep-library parent/libgzero.so --out profiles/puct/compact_bench.json
 """
 import argparse
 import json
@@ -89,6 +103,11 @@ ap.add_argument("--leaves", default=None, metavar="K,K,...",
 ap.add_argument("--sweep-slots", default="1,8,64,256", help="--leaves: the slot counts (comma-separated)")
 ap.add_argument("--leaves-child", default=None, metavar="K,K,...",
                 help="(child) one engine per K at --slots: time steps on request")
+ap.add_argument("--compact", action="store_true", help="measure slot compaction over --compact-games (see above)")
+ap.add_argument("--compact-games", default="512,4096", help="--compact: games = slots per iteration (comma-separated)")
+ap.add_argument("--compact-noise", default="0.3,0.25", metavar="ALPHA,EPS", help="--compact: the root noise of the noisy runs")
+ap.add_argument("--compact-child", default=None, metavar="on|off:NOISE",
+                help="(child) compaction on or off, then off or ALPHA,EPS: one iteration of --slots games on request")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 precisions = a.precisions.split(",")
@@ -97,6 +116,32 @@ precisions = a.precisions.split(",")
 def median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
+
+
+def bind_older_build():
+    """(child) Bind what the loaded library has.  A build from before the capacity / active
+    count entry points runs every slot anyway: its engines call the older ones."""
+    import ctypes
+    from gzero import _lib
+    from gzero.device import ptr, stream
+    from gzero.selfplay import SelfPlayEngine
+    have = ctypes.CDLL(_lib.LIB_PATH)
+    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    if hasattr(have, "gz_selfplay_puct_run_active"):
+        return have
+
+    def call(name):
+        def run(self, p, n):
+            assert self.n_active == self.n_slots
+            _lib.check(getattr(self.lib, name)(ptr(self.d_slots), self.n_slots, ctypes.byref(p),
+                                               ptr(self.pv_weights.tensor), ptr(self.d_puct_ws), int(n),
+                                               ptr(self.d_records), self.record_cap, ptr(self.d_visits),
+                                               ptr(self.d_counters), stream()), name)
+        return run
+    SelfPlayEngine._puct_run = call("gz_selfplay_puct_run")
+    rounds = call("gz_selfplay_puct_rounds")
+    SelfPlayEngine._puct_rounds = lambda self, n_rounds: rounds(self, self.puct, n_rounds)
+    return have
 
 
 def forward_only():
@@ -143,8 +188,7 @@ def lockstep_child():
     import torch
     from gzero import _lib
     from gzero.selfplay import SelfPlayEngine
-    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build lacks the newer entry points
-    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    have = bind_older_build()
     eng = SelfPlayEngine(n_slots=a.slots, num_simulations=a.sims, seed=1,
                          pv_weights=bench_weights(precisions[0], a.lockstep_child), search="puct",
                          temp_plies=a.temp_plies)
@@ -253,8 +297,7 @@ def noise_child():
     import torch
     from gzero import _lib
     from gzero.selfplay import SelfPlayEngine
-    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build lacks the newer entry points
-    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    have = bind_older_build()
     mode, spec = a.noise_child.split(":")
     reuse = mode == "reuse"
     eng = SelfPlayEngine(n_slots=a.slots, num_simulations=a.sims, seed=1, pv_weights=bench_weights(precisions[0], 1.0),
@@ -385,8 +428,7 @@ def leaves_child():
     import torch
     from gzero import _lib
     from gzero.selfplay import SelfPlayEngine
-    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build lacks the newer entry points
-    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(have, k)}
+    have = bind_older_build()
     can_count = hasattr(have, "gz_puct_remaining")
     S, n = a.sims, a.slots
     w = bench_weights(precisions[0], 1.0)
@@ -416,6 +458,104 @@ def leaves_child():
         c = eng.counters()
         assert c["records_dropped"] == 0 and c["moves"] == n
         print(f"STEP_MS {e0.elapsed_time(e1)!r} {rounds} {reads} {active} {rows}", flush=True)
+
+
+def compact_child():
+    """Per "iter" on stdin: one selfplay_puct_device iteration of --slots games on --slots
+    slots; a JSON line with its seconds, steps, moves, game lengths and the device time of
+    the compaction launches (events around every SelfPlayEngine.compact call)."""
+    import time
+    import numpy as np
+    import torch
+    bind_older_build()
+    import training
+    from gzero import weights
+    from gzero.boards import RECORD_DTYPE
+    from gzero.selfplay import SelfPlayEngine
+    from neural_network import GomokuModel
+    mode, spec = a.compact_child.split(":")
+    model = GomokuModel(device="cpu", precision=precisions[0])
+    model.model.load_state_dict(weights.init_state_dict(0))
+    model.device_weights()
+    events = []
+    launch = SelfPlayEngine.compact
+
+    def timed_compact(self):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = launch(self)
+        e1.record()
+        events.append((e0, e1))
+        return out
+    SelfPlayEngine.compact = timed_compact
+    noise = noise_args(spec)
+    torch.cuda.synchronize()
+    print("READY " + torch.cuda.get_device_name(0), flush=True)
+    for line in sys.stdin:
+        if line.strip() != "iter":
+            break
+        del events[:]
+        t0 = time.perf_counter()
+        d, _, n, st = training.selfplay_puct_device(a.slots, num_simulations=a.sims, seed=1, n_slots=a.slots,
+                                                    model=model, temp_plies=a.temp_plies, compact=mode == "on",
+                                                    **noise)
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        recs = np.frombuffer(d.cpu().numpy().tobytes(), RECORD_DTYPE)
+        length = np.bincount((recs["game_id"] - recs["game_id"].min()).astype(np.int64), minlength=a.slots)
+        print("ITER " + json.dumps({"seconds": sec, "steps": st["steps"], "moves_played": st["moves_played"],
+                                    "rows": n, "mean_game": float(length.mean()), "longest_game": int(length.max()),
+                                    "compaction_launches": len(events),
+                                    "compaction_ms": sum(e0.elapsed_time(e1) for e0, e1 in events)}), flush=True)
+
+
+def compact_run(prec, games, spec):
+    """The three engines of one (G, noise) cell, taking turns at one iteration each."""
+    kinds = [("parent_refill", "off", a.lockstep_library), ("refill", "off", None), ("compact", "on", None)]
+    kids = {}
+    try:
+        for name, mode, library in kinds:
+            env = dict(os.environ)
+            if library:
+                env["GZ_LIBRARY"] = os.path.abspath(library)
+            kids[name] = subprocess.Popen(
+                [sys.executable, os.path.abspath(__file__), "--compact-child", f"{mode}:{spec}", "--slots", str(games),
+                 "--sims", str(a.sims), "--precisions", prec, "--temp-plies", str(a.temp_plies)],
+                env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+        for name, kid in kids.items():
+            ready = kid.stdout.readline().strip()
+            if not ready.startswith("READY"):
+                sys.exit(f"compact child {name} at {games} games failed ({kid.poll()})")
+            device_name[0] = ready[len("READY "):]
+        out = {name: {"turns": []} for name in kids}
+        for _ in range(a.steps):
+            for name, kid in kids.items():
+                kid.stdin.write("iter\n")
+                kid.stdin.flush()
+                line = kid.stdout.readline()
+                if not line.startswith("ITER "):
+                    sys.exit(f"compact child {name} at {games} games failed ({kid.poll()}): {line}")
+                out[name]["turns"].append(json.loads(line[len("ITER "):]))
+                print(f"  {games} games, noise {spec}, {name}: {line.strip()}", flush=True)
+    finally:
+        for kid in kids.values():
+            kid.stdin.close()
+        for kid in kids.values():
+            kid.wait(timeout=120)
+    for r in out.values():
+        r["seconds_median"] = median([t["seconds"] for t in r["turns"]])
+    on, off = out["compact"], out["refill"]
+    t = on["turns"][0]
+    out["seconds_compact_over_refill"] = on["seconds_median"] / off["seconds_median"]
+    out["seconds_compact_over_parent_refill"] = on["seconds_median"] / out["parent_refill"]["seconds_median"]
+    out["seconds_refill_over_parent_refill"] = off["seconds_median"] / out["parent_refill"]["seconds_median"]
+    out["mean_over_longest_game"] = t["mean_game"] / t["longest_game"]
+    out["compaction_ms_share_of_iteration"] = median([x["compaction_ms"] / 1e3 / x["seconds"] for x in on["turns"]])
+    print(f"{prec} {games} games, noise {spec}: {on['seconds_median']:.2f} s compacting, {off['seconds_median']:.2f} s "
+          f"refilling (x{out['seconds_compact_over_refill']:.3f}; parent {out['parent_refill']['seconds_median']:.2f} s); "
+          f"mean / longest game {t['mean_game']:.1f} / {t['longest_game']} = {out['mean_over_longest_game']:.3f}",
+          flush=True)
+    return out
 
 
 device_name = [None]
@@ -486,6 +626,35 @@ if a.forward_only:
     sys.exit(0)
 if a.leaves_child is not None:
     leaves_child()
+    sys.exit(0)
+if a.compact_child is not None:
+    compact_child()
+    sys.exit(0)
+if a.compact:
+    prec = precisions[0]
+    res = {"config": {"simulations": a.sims, "temp_plies": a.temp_plies, "precision": prec, "turns": a.steps,
+                      "weights": "init_state_dict(0)", "noise": noise_args(a.compact_noise),
+                      "what": "one training.selfplay_puct_device iteration of G games on G slots (plies_per_step 4, "
+                              "lock-step), wall clock around the call; three child processes (the parent build and "
+                              "this build with continuous refill, this build compacting) take turns",
+                      "prediction": "mean / longest game: the share of the refill run's forward rows that belong "
+                                    "to wanted games",
+                      "parent_library": "another build (--lockstep-library)" if a.lockstep_library else "this build"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    for games in (int(x) for x in a.compact_games.split(",") if x):
+        for spec in ("off", a.compact_noise):
+            res["results"][f"games_{games}_noise_{'off' if spec == 'off' else 'on'}"] = compact_run(prec, games, spec)
+    if a.slots > 0:
+        res["results"][f"compaction_off_step_slots_{a.slots}"] = leaves_run(prec, a.slots, [1])
+    res["device"] = device_name[0]
+    print("PUCT_COMPACT_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.leaves:
     prec = precisions[0]
