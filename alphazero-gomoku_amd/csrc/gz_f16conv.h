@@ -6,6 +6,9 @@
 // a_hi*w_lo + a_lo*w_hi on v_mfma_f32_16x16x32_f16, every product exact in the f32
 // accumulator (~22-bit operands).  The MFMAs compute C^T[ch][pos] (A = weight
 // fragment, B = activation fragment).
+//
+// One term (GZ_PV_F16, gz_pvnet.hip): the hi halves alone -- maps stored as fp16(x) in
+// ActF16, a*w ~ a_hi*w_hi, one MFMA per product (f16_conv with TERMS = 1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +60,17 @@ struct ActF16x3 {
     }
 };
 
+// The one-term f16 map (GZ_PV_F16): the hi plane alone, x stored as fp16(x).  Same
+// addressing, so the conv reads either with the same ds_read_b128.
+struct ActF16 {
+    _Float16* hi;
+    __device__ static int off(int ch, int pos) { return ActF16x3::off(ch, pos); }
+    __device__ void zero_slots(int tid, int nth, int channels) {
+        constexpr int PAD = (ROWS16 - BPOS) * 8;
+        for (int i = tid; i < (channels / 8) * PAD; i += nth) hi[(i / PAD) * ROWS16 * 8 + BPOS * 8 + i % PAD] = (_Float16)0.f;
+    }
+};
+
 // lane (li, g) of a C^T tile holds channels 4g..4g+3 of its N tile for position
 // 16*tile + li: 4 consecutive channels = 8 bytes of the hi plane and 8 of the lo.
 __device__ __forceinline__ void f16_get4(const ActF16x3& act, int ch0, int pos, f32x4& out) {
@@ -86,6 +100,28 @@ __device__ __forceinline__ void f16_put4(ActF16x3& act, const f32x4& acc, const 
     *(h4*)(act.lo + o) = lo;
 }
 
+// hi-only siblings: the value as stored
+__device__ __forceinline__ void f16_get4(const ActF16& act, int ch0, int pos, f32x4& out) {
+    const h4 xh = *(const h4*)(act.hi + ActF16::off(ch0, pos));
+#pragma unroll
+    for (int r = 0; r < 4; r++) out[r] = (float)xh[r];
+}
+
+// y = fma(acc, S, T) (+ skip), ReLU, stored as fp16(y): one 8-byte write
+template <bool SKIP>
+__device__ __forceinline__ void f16_put4(ActF16& act, const f32x4& acc, const f32x4& s, const f32x4& t,
+                                         const f32x4& skip, int ch0, int pos) {
+    h4 hi;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        float y = __builtin_fmaf(acc[r], s[r], t[r]);
+        if (SKIP) y += skip[r];
+        y = y > 0.f ? y : 0.f;
+        hi[r] = (_Float16)y;
+    }
+    *(h4*)(act.hi + ActF16::off(ch0, pos)) = hi;
+}
+
 // Implicit-GEMM conv (3x3 with TAPS = 9, 1x1 with TAPS = 1) over CQ 32-channel
 // input groups, for the wave's n-tiles {2np, 2np+1} of NTT and M tiles
 // [m0, m0 + NM).  Weights: f16 hi then lo, each in A-fragment order
@@ -98,10 +134,16 @@ __device__ __forceinline__ void f16_put4(ActF16x3& act, const f32x4& acc, const 
 // (the default scheduler sinks every read to its use).  Branch-free: the last
 // k-step prefetches k-step 0 / the tap after the last (valid addresses, unused),
 // so each tap is one basic block.
-template <int NM, int CQ, int NTT, int TAPS>
-__device__ __forceinline__ void f16_conv(const ActF16x3& act, const _Float16* __restrict__ Wf, int np, int m0,
+//
+// TERMS = 3: the f16x3 split above.  TERMS = 1 (Act = ActF16): a_hi*w_hi alone -- no
+// lo plane is read, no lo weight fragment loaded, one MFMA per (n, m); per tile that
+// is 1 DS read and 2 MFMAs, per k-step 2 VMEM reads.
+template <int NM, int CQ, int NTT, int TAPS, int TERMS = 3, class Act = ActF16x3>
+__device__ __forceinline__ void f16_conv(const Act& act, const _Float16* __restrict__ Wf, int np, int m0,
                                          int lane, f32x4 (&acc)[2][NM]) {
+    static_assert(TERMS == 1 || TERMS == 3, "one term or the 3-term split");
     constexpr int HA = (NM + 1) / 2, HB = NM - HA;
+    constexpr int RD = TERMS == 3 ? 2 : 1;  // DS reads per tile, and weight loads per n-tile
     constexpr int KS = TAPS * CQ;
     constexpr int KS_HALVES = NTT * 64 * 8;  // fragments of one k-step, all n-tiles
     constexpr int KS_BYTES = KS_HALVES * 2, LO_BYTES = KS * KS_BYTES;
@@ -117,7 +159,7 @@ __device__ __forceinline__ void f16_conv(const ActF16x3& act, const _Float16* __
 #pragma unroll
     for (int n = 0; n < 2; n++) {
         b[n][0] = wload(0, n, 0);
-        b[n][1] = wload(0, n, 1);
+        if constexpr (TERMS == 3) b[n][1] = wload(0, n, 1);
     }
 
     h8 ah[NM], al[NM];
@@ -130,7 +172,7 @@ __device__ __forceinline__ void f16_conv(const ActF16x3& act, const _Float16* __
 #pragma unroll
     for (int m = 0; m < HA; m++) {
         ah[m] = *(const h8*)(act.hi + nb[m]);
-        al[m] = *(const h8*)(act.lo + nb[m]);
+        if constexpr (TERMS == 3) al[m] = *(const h8*)(act.lo + nb[m]);
     }
     for (int tap = 0; tap < TAPS; tap++) {
 #pragma unroll
@@ -140,7 +182,7 @@ __device__ __forceinline__ void f16_conv(const ActF16x3& act, const _Float16* __
 #pragma unroll
             for (int m = HA; m < NM; m++) {
                 ah[m] = *(const h8*)(act.hi + ao + nb[m]);
-                al[m] = *(const h8*)(act.lo + ao + nb[m]);
+                if constexpr (TERMS == 3) al[m] = *(const h8*)(act.lo + ao + nb[m]);
             }
             h8 bn[2][2];
             {
@@ -148,17 +190,19 @@ __device__ __forceinline__ void f16_conv(const ActF16x3& act, const _Float16* __
 #pragma unroll
                 for (int n = 0; n < 2; n++) {
                     bn[n][0] = wload(ks1, n, 0);
-                    bn[n][1] = wload(ks1, n, 1);
+                    if constexpr (TERMS == 3) bn[n][1] = wload(ks1, n, 1);
                 }
             }
 #pragma unroll
             for (int m = 0; m < HA; m++) {
 #pragma unroll
                 for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][0], ah[m], acc[n][m], 0, 0, 0);
+                if constexpr (TERMS == 3) {
 #pragma unroll
-                for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][1], ah[m], acc[n][m], 0, 0, 0);
+                    for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][1], ah[m], acc[n][m], 0, 0, 0);
 #pragma unroll
-                for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][0], al[m], acc[n][m], 0, 0, 0);
+                    for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][0], al[m], acc[n][m], 0, 0, 0);
+                }
             }
             if (TAPS == 9 && cq == CQ - 1) {  // next tap: new neighbour offsets (tap 9 after the last: unused)
                 const int t2 = tap + 1, dr = t2 / 3 - 1, dc = t2 % 3 - 1;
@@ -172,37 +216,41 @@ __device__ __forceinline__ void f16_conv(const ActF16x3& act, const _Float16* __
 #pragma unroll
                 for (int m = 0; m < HA; m++) {
                     ah[m] = *(const h8*)(act.hi + ao2 + nb[m]);
-                    al[m] = *(const h8*)(act.lo + ao2 + nb[m]);
+                    if constexpr (TERMS == 3) al[m] = *(const h8*)(act.lo + ao2 + nb[m]);
                 }
             }
 #pragma unroll
             for (int m = HA; m < NM; m++) {
 #pragma unroll
                 for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][0], ah[m], acc[n][m], 0, 0, 0);
+                if constexpr (TERMS == 3) {
 #pragma unroll
-                for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][1], ah[m], acc[n][m], 0, 0, 0);
+                    for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][1], ah[m], acc[n][m], 0, 0, 0);
 #pragma unroll
-                for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][0], al[m], acc[n][m], 0, 0, 0);
+                    for (int n = 0; n < 2; n++) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[n][0], al[m], acc[n][m], 0, 0, 0);
+                }
             }
 #pragma unroll
             for (int n = 0; n < 2; n++) {
                 b[n][0] = bn[n][0];
-                b[n][1] = bn[n][1];
+                if constexpr (TERMS == 3) b[n][1] = bn[n][1];
             }
             // pin the interleave: weight prefetch first, then 2 activation reads per 6 MFMAs
-            __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);  // VMEM read
+            // (one term: 1 read per 2 MFMAs)
+            constexpr int MF = 2 * TERMS;
+            __builtin_amdgcn_sched_group_barrier(0x020, 2 * RD, 0);  // VMEM read
 #pragma unroll
             for (int m = 0; m < HA; m++) {
-                if (m < HB) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read
-                __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);              // MFMA
+                if (m < HB) __builtin_amdgcn_sched_group_barrier(0x100, RD, 0);  // DS read
+                __builtin_amdgcn_sched_group_barrier(0x008, MF, 0);              // MFMA
             }
 #pragma unroll
             for (int m = 0; m + 1 < HB; m++) {
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, RD, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, MF, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 + 2 * (HA - HB), 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, RD * (1 + HA - HB), 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, MF, 0);
         }
     }
 }

@@ -1546,7 +1546,7 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     if (!p) return gz_fail(GZ_ERR_ARG, std::string(who) + ": params is NULL");
     int rc = check_S(who, n, p->num_simulations);
     if (rc) return rc;
-    if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3)
+    if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3 && p->precision != GZ_PV_F16)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
     PuctNoise nz;
     rc = read_noise(who, p, nz);

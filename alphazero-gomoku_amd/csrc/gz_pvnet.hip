@@ -6,7 +6,7 @@
 // tower; every 3x3 conv is an implicit GEMM
 //   C[pos][ch] = sum_k A[pos][k] * W[k][ch],  A[pos][tap*128+cin] = act[cin][pos+tap]
 // with M = 225 positions (15 tiles of 16), N = 128 channels (8 tiles of 16).
-// Off-board neighbours read a zero slot instead of predicating.  Two precisions:
+// Off-board neighbours read a zero slot instead of predicating.  Three precisions:
 //
 //  * GZ_PV_FP32: v_mfma_f32_16x16x4_f32 -- exact f32 products, f32 accumulate.
 //    Wave w owns N tile w for all 15 M tiles (each weight fragment read once per
@@ -20,6 +20,10 @@
 //    per MFMA; activations as hi/lo fp16 planes [16 ch-groups][240][8]
 //    (conflict-free ds_read_b128); weights pre-arranged in B-fragment order.
 //    The skip input of a residual block stays in registers.
+//  * GZ_PV_F16: the f16x3 kernel with the lo terms of the residual tower dropped --
+//    maps stored as fp16(y) in one plane, weights fp16(w), one MFMA per product,
+//    the same fp32 BN / skip / ReLU epilogues, conv0 and heads (pv_kernel_f16).
+//    Opt-in, for the PUCT search; not within 1e-4 of the fp32 forward.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -303,6 +307,81 @@ __device__ __forceinline__ void f16_tower(ActF16x3& act, const float* __restrict
     }
 }
 
+// ============================================================ one-term f16 policy (GZ_PV_F16)
+// The f16x3 tower with the lo terms dropped: maps stored as fp16(y) in the hi plane
+// alone, one MFMA per product (f16_conv TERMS = 1), the same fp32 epilogues.  Siblings
+// of the f16x3 helpers above, not shared with them: the f16x3 instantiations (and the
+// tree forward's, which stay f16x3) compile as they did.
+template <int NM>
+__device__ __forceinline__ void f16_load(const ActF16& act, f32x4 (&out)[2][NM], int np, int m0, int lane) {
+    asm volatile("" : "+v"(lane));  // addresses are recomputed per layer, not hoisted (and spilled)
+    lane &= 63;
+#pragma unroll
+    for (int n = 0; n < 2; n++) {
+        const int ch0 = (2 * np + n) * 16 + 4 * (lane >> 4);
+#pragma unroll
+        for (int m = 0; m < NM; m++) {
+            const int pos = (m0 + m) * 16 + (lane & 15);
+            if (pos < POS) f16_get4(act, ch0, pos, out[n][m]);
+            else out[n][m] = zero4();
+        }
+    }
+}
+
+template <int NM, bool SKIP>
+__device__ __forceinline__ void f16_store(ActF16& act, const f32x4 (&acc)[2][NM], const float* __restrict__ S,
+                                          const float* __restrict__ T, const f32x4 (&skip)[2][NM], int np, int m0,
+                                          int lane) {
+    asm volatile("" : "+v"(lane));
+    lane &= 63;
+#pragma unroll
+    for (int n = 0; n < 2; n++) {
+        const int ch0 = (2 * np + n) * 16 + 4 * (lane >> 4);
+        const f32x4 s = *(const f32x4*)(S + ch0), t = *(const f32x4*)(T + ch0);
+#pragma unroll
+        for (int m = 0; m < NM; m++) {
+            const int pos = (m0 + m) * 16 + (lane & 15);
+            if (pos < POS) f16_put4<SKIP>(act, acc[n][m], s, t, skip[n][m], ch0, pos);
+        }
+    }
+}
+
+// the skip input is the block input as stored (fp16); the last epilogue is the f16x3
+// one: the 1x1 head convs read its fp32 y, x2 is never rounded
+template <int NM, int m0>
+__device__ __forceinline__ void f16_tower(ActF16& act, const float* __restrict__ W, int wave, int lane,
+                                          float* __restrict__ hpart) {
+    const int np = wave & 3;
+    for (int blk = 0; blk < 2; blk++) {
+        f32x4 skip[2][NM];
+        for (int half = 0; half < 2; half++) {
+            const int layer = 2 * blk + half;
+            const float* R = W + RES0 + layer * RES_STRIDE;
+            f32x4 acc[2][NM];
+#pragma unroll
+            for (int n = 0; n < 2; n++)
+#pragma unroll
+                for (int m = 0; m < NM; m++) acc[n][m] = zero4();
+            PV_WAVE_T0();
+            f16_conv<NM, 4, 8, 9, 1>(act, (const _Float16*)(W + F16_RES0 + layer * F16_STRIDE), np, m0, lane, acc);
+            PV_STAMP(2);
+            PV_WAVE_STAMP(8);
+            if (half == 0) f16_load<NM>(act, skip, np, m0, lane);
+            __syncthreads();
+            PV_WAVE_STAMP(16);
+            PV_STAMP(3);
+            if (half == 0)
+                f16_store<NM, false>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane);
+            else if (blk == 0)
+                f16_store<NM, true>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane);
+            else
+                f16_store_heads<NM>(acc, W, R + RES_S, R + RES_T, skip, np, m0, lane, hpart, nullptr);
+            __syncthreads();
+            PV_STAMP(4);
+        }
+    }
+}
+
 // conv0 3->128 + BN + ReLU in f16 (C^T form): the input planes are 0/1, exact in
 // fp16, so a*w = a*w_hi + a*w_lo (2 MFMAs, no a_lo term); K = 27 (k = tap*3 + cin)
 // padded to one 32-deep k-step.  Wave w: N tile w, all 15 M tiles.
@@ -349,6 +428,28 @@ __device__ __forceinline__ void conv0_f16(ActF16x3& act, const float* __restrict
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, a[m], acc, 0, 0, 0);
         const int pos = m * 16 + li;
         if (pos < POS) pv_put4<false>(act, acc, s, t, none, ch0, pos, g, nullptr);
+    }
+}
+
+// GZ_PV_F16: the same two MFMAs (w_hi + w_lo on the 0/1 input), x0 stored as fp16(x0)
+__device__ __forceinline__ void conv0_f16(ActF16& act, const float* __restrict__ W, const _Float16* col, int nt,
+                                          int lane) {
+    const int li = lane & 15, q = lane >> 4;
+    const _Float16* wf = (const _Float16*)(W + F16_C0) + ((size_t)nt * 64 + lane) * 8;
+    const h8 bh = *(const h8*)wf, bl = *(const h8*)(wf + 8 * 64 * 8);
+    const int ch0 = nt * 16 + 4 * q;
+    const f32x4 s = *(const f32x4*)(W + C0_S + ch0), t = *(const f32x4*)(W + C0_T + ch0);
+    const f32x4 none = zero4();
+    h8 a[MT];
+#pragma unroll
+    for (int m = 0; m < MT; m++) a[m] = *(const h8*)(col + (m * 16 + li) * 32 + 8 * q);
+#pragma unroll
+    for (int m = 0; m < MT; m++) {
+        f32x4 acc = zero4();
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, a[m], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, a[m], acc, 0, 0, 0);
+        const int pos = m * 16 + li;
+        if (pos < POS) f16_put4<false>(act, acc, s, t, none, ch0, pos);
     }
 }
 
@@ -410,9 +511,9 @@ static_assert((2 * POS + POS + 32 + 256 + 512 + 192 + 4 * 3 * 256) * 4 >= 256 * 
 constexpr int SMALL_F = 3 * ROWS + 2 * POS + POS + 32 + 256 + 512 + 192 + 4 * 3 * 256;
 constexpr int LDS_BYTES = ACT_BYTES + SMALL_F * 4;
 
-__device__ inline Smem smem_layout(char* lds) {
+__device__ inline Smem smem_layout(char* lds, int act_bytes = ACT_BYTES) {
     Smem m;
-    m.planes = (float*)(lds + ACT_BYTES);
+    m.planes = (float*)(lds + act_bytes);
     m.hp = m.planes + 3 * ROWS;
     m.hv = m.hp + 2 * POS;
     m.red = m.hv + POS;
@@ -687,6 +788,66 @@ __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restri
             }
             float* h = hbuf + (size_t)b * HSTRIDE;
             h[tid_h] = p0;  // flatten order: channel-major (policy.view(B, -1))
+            h[POS + tid_h] = p1;
+            h[HV_OFF + tid_h] = v;
+        } else if (tid_h < POS + (HV_OFF - 2 * POS)) {
+            hbuf[(size_t)b * HSTRIDE + 2 * POS + (tid_h - POS)] = 0.f;  // hp k-padding
+        } else if (tid_h < POS + (HV_OFF - 2 * POS) + (HSTRIDE - HV_OFF - POS)) {
+            hbuf[(size_t)b * HSTRIDE + HV_OFF + POS + (tid_h - POS - (HV_OFF - 2 * POS))] = 0.f;  // hv padding
+        }
+    }
+}
+
+// ============================================================ one-term f16 kernel (GZ_PV_F16)
+// pv_kernel_f16x3 with the hi plane alone: the same 8 waves, 8/7 M-tile split and
+// n-tile pairs, a third of the MFMAs and half the LDS (no lo plane is allocated or
+// zeroed).  It writes the same tower -> heads records; no LIST / DUMP (the tree
+// forward stays f16x3).
+constexpr int ACT_BYTES_F16H = CH * 256 * 2;  // 65536: the hi plane of 256 rows
+constexpr int LDS_BYTES_F16H = ACT_BYTES_F16H + SMALL_F * 4;
+__global__ __launch_bounds__(NT16, 1) void pv_kernel_f16(const float* __restrict__ W,
+                                                       const uint32_t* __restrict__ boards, int n,
+                                                       const int32_t* d_count, float* __restrict__ hbuf) {
+    __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES_F16H];
+    const Smem sm = smem_layout(lds, ACT_BYTES_F16H);
+    ActF16 act;
+    act.hi = (_Float16*)lds;
+    const int count = board_count(n, d_count);
+    act.zero_slots(threadIdx.x, NT16, CH);
+    for (int i = threadIdx.x; i < 3 * (ROWS - POS); i += NT16)
+        sm.planes[(i / (ROWS - POS)) * ROWS + POS + i % (ROWS - POS)] = 0.f;
+
+    PV_STAMP(30);
+    for (int b = blockIdx.x; b < count; b += gridDim.x) {
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        load_planes<NT16>(sm.planes, boards + (size_t)b * 16, tid);
+        __syncthreads();
+        PV_STAMP(0);
+        _Float16* col = (_Float16*)sm.hp;  // im2col in the heads' scratch area, as in pv_kernel_f16x3
+        build_im2col<NT16>(col, sm.planes, tid);
+        __syncthreads();
+        conv0_f16(act, W, col, wave, lane);
+        __syncthreads();
+        PV_STAMP(1);
+        if (wave >> 2)
+            f16_tower<PV_YOUNG_TILES, PV_SPLIT>(act, W, wave, lane, sm.hpart);
+        else
+            f16_tower<PV_SPLIT, 0>(act, W, wave, lane, sm.hpart);
+        int tid_h = threadIdx.x;
+        asm volatile("" : "+v"(tid_h));
+        // the record of pv_kernel_f16x3, same order of the sums
+        if (tid_h < POS) {
+            float p0 = W[P_B], p1 = W[P_B + 1], v = W[V_B];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                p0 += sm.hpart[(q * 3 + 0) * 256 + tid_h];
+                p1 += sm.hpart[(q * 3 + 1) * 256 + tid_h];
+                v += sm.hpart[(q * 3 + 2) * 256 + tid_h];
+            }
+            float* h = hbuf + (size_t)b * HSTRIDE;
+            h[tid_h] = p0;
             h[POS + tid_h] = p1;
             h[HV_OFF + tid_h] = v;
         } else if (tid_h < POS + (HV_OFF - 2 * POS)) {
@@ -1058,7 +1219,7 @@ extern "C" int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, i
                              int32_t precision, void* stream) {
     if (n < 0 || (n > 0 && (!d_weights || !d_boards || !d_logits || !d_value)))
         return gz_fail(GZ_ERR_ARG, "gz_pv_forward: bad arguments");
-    if (precision != GZ_PV_FP32 && precision != GZ_PV_F16X3)
+    if (precision != GZ_PV_FP32 && precision != GZ_PV_F16X3 && precision != GZ_PV_F16)
         return gz_fail(GZ_ERR_ARG, "gz_pv_forward: unknown precision");
     if (!d_workspace) return gz_fail(GZ_ERR_ARG, "gz_pv_forward: d_workspace is required");
     if (d_prior && !d_probs)
@@ -1071,8 +1232,11 @@ extern "C" int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, i
                                             (float*)d_workspace);
     else
     {
-        pv_kernel_f16x3<false, false><<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, (float*)d_workspace, nullptr,
-                                                     nullptr, nullptr, nullptr, 0);
+        if (precision == GZ_PV_F16)
+            pv_kernel_f16<<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, (float*)d_workspace);
+        else
+            pv_kernel_f16x3<false, false><<<grid, NT16, 0, s>>>(d_weights, d_boards, n, d_count, (float*)d_workspace,
+                                                                nullptr, nullptr, nullptr, nullptr, 0);
         pv_heads_launch(d_weights, (const float*)d_workspace, n, d_count, d_logits, d_value, d_probs,
                         (_Float16*)((char*)d_workspace + pv_hf_offset(n)), s);
     }

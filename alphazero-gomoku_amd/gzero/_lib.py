@@ -18,6 +18,7 @@ GZ_MAX_SIMULATIONS = 4095
 GZ_MAX_GAME_PLIES = 200
 GZ_PV_FP32 = 0
 GZ_PV_F16X3 = 1
+GZ_PV_F16 = 2  # one-term fp16 tower (include/gzero.h); opt-in
 GZ_AUG_FIX_LABELS = 1
 GZ_PUCT_ROOT_NOISE = 1  # gz_puct_params.flags: the params are a gz_puct_noise_params
 GZ_PUCT_LEAF_BATCH = 2  # gz_puct_params.flags: the params are a gz_puct_batch_params

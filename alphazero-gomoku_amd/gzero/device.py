@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from .boards import RECORD_DTYPE, STATE_DTYPE
+from .weights import PRECISIONS
 
 
 def require_gpu():
@@ -156,15 +157,16 @@ def search(states, game_ids, params, want_trees=False, leaf_cap=0):
 class PVWeights:
     """Packed weight blob resident on the device (+ the fp32 kernel's scratch slab).
 
-    precision: "fp32" (exact f32 MFMA) or "f16x3" (3-term fp16 split on the
-    fp16 MFMA, f32 accumulation)."""
+    precision: "fp32" (exact f32 MFMA), "f16x3" (3-term fp16 split on the
+    fp16 MFMA, f32 accumulation) or "f16" (GZ_PV_F16: one fp16 MFMA per product,
+    maps stored as fp16; opt-in, not within 1e-4 of the fp32 forward)."""
 
     def __init__(self, blob, precision="f16x3"):
-        lib = require_gpu()
-        if precision not in ("fp32", "f16x3"):
+        if precision not in PRECISIONS:
             raise ValueError(f"unknown precision {precision!r}")
+        lib = require_gpu()
         self.precision = precision
-        self.mode = _lib.GZ_PV_FP32 if precision == "fp32" else _lib.GZ_PV_F16X3
+        self.mode = PRECISIONS[precision]
         if isinstance(blob, torch.Tensor):  # (weights.pack_pv_weights_torch: packed on the device)
             blob = blob.detach().to(device="cuda", dtype=torch.float32).contiguous().reshape(-1)
         else:
@@ -327,7 +329,7 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 # ---------------------------------------------------------------- PUCT search
 def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
                 noise_eps=0.25, leaves_per_round=1):
-    """gz_puct_params; precision ("fp32" / "f16x3") is the forward gz_puct_search runs.
+    """gz_puct_params; precision ("fp32" / "f16x3" / "f16") is the forward gz_puct_search runs.
     dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
     noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
     the result is then a gz_puct_noise_params with GZ_PUCT_ROOT_NOISE set.  None (the
@@ -335,9 +337,9 @@ def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision
     leaves_per_round K > 1: leaf batching with virtual loss, K leaves per game per round
     (a gz_puct_batch_params with GZ_PUCT_LEAF_BATCH set); 1 (the default) is the
     unbatched search with the flag clear."""
-    if precision not in ("fp32", "f16x3"):
+    if precision not in PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}")
-    mode = _lib.GZ_PV_FP32 if precision == "fp32" else _lib.GZ_PV_F16X3
+    mode = PRECISIONS[precision]
     base = (int(num_simulations), int(temp_plies), float(c_puct), int(seed) & ((1 << 64) - 1), mode)
     K = int(leaves_per_round)
     if not 1 <= K <= _lib.GZ_PUCT_MAX_LEAVES:

@@ -149,7 +149,7 @@ V1_P = PF_P + PF_KB * PF_NT * 256
 V1_KB, V1_NT = 15, 4
 TOTAL = V1_P + V1_KB * V1_NT * 256
 
-PRECISIONS = {"fp32": 0, "f16x3": 1}  # GZ_PV_FP32, GZ_PV_F16X3
+PRECISIONS = {"fp32": 0, "f16x3": 1, "f16": 2}  # GZ_PV_FP32, GZ_PV_F16X3, GZ_PV_F16
 
 PV_MACS = 133_690_114  # conv0 777,600 + 4 x 33,177,600 + heads 202,114
 PV_FLOPS = 2 * PV_MACS

@@ -28,6 +28,8 @@ class GomokuModel:
         self.board_size = board_size
         self.model_path = model_path
         self.device = torch.device(device)
+        if precision not in _w.PRECISIONS:  # "fp32", "f16x3" or "f16" (gzero.device.PVWeights)
+            raise ValueError(f"unknown precision {precision!r}")
         self.precision = precision
         self.logger = logging.getLogger(__name__)
         self.model = AlphaZeroGomokuNet(board_size)
@@ -35,6 +37,7 @@ class GomokuModel:
         self.model.eval()
         self._packed = None
         self._packed_key = None
+        self._packed_other = {}  # precision -> (key, PVWeights): device_weights(precision=...)
         # auto-load order of the reference (neural_network.py:189-212): path, best, newest
         if model_path and os.path.exists(model_path):
             self.load_model(model_path)
@@ -49,10 +52,20 @@ class GomokuModel:
     def _param_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.model.state_dict().values())
 
-    def device_weights(self):
-        """Packed weights on the GPU, repacked after any parameter change."""
+    def device_weights(self, precision: Optional[str] = None):
+        """Packed weights on the GPU, repacked after any parameter change.  ``precision``
+        (None: the model's own): a second pack of the same parameters at another
+        precision, cached by the same key (training's ``selfplay_precision``)."""
         from gzero.device import PVWeights
         key = self._param_key()
+        if precision is not None and precision != self.precision:
+            if precision not in _w.PRECISIONS:
+                raise ValueError(f"unknown precision {precision!r}")
+            hit = self._packed_other.get(precision)
+            if hit is None or hit[0] != key:
+                hit = (key, PVWeights(_w.pack_pv_weights_torch(self.model.state_dict(), "cuda"), precision=precision))
+                self._packed_other[precision] = hit
+            return hit[1]
         if self._packed is None or key != self._packed_key:
             # packed on the device (the host packer's numpy took ~0.5 s per repack)
             self._packed = PVWeights(_w.pack_pv_weights_torch(self.model.state_dict(), "cuda"),

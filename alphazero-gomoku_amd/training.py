@@ -183,7 +183,8 @@ def selfplay(n_games: int, num_simulations: int = 200, difficulty: str = "medium
     node the searches create, as the reference does -- by default incrementally
     (``pv_mode="tree"``: each root's children and grandchildren recompute only the
     windows their stone changes, outputs bit-identical; f16x3 models only, at most
-    4 plies per step to bound its workspace).  ``planner_steps > 0`` adds
+    4 plies per step to bound its workspace; an "f16" or "fp32" model runs the full
+    forward of every node at its own precision).  ``planner_steps > 0`` adds
     BG-planner plies to every rollout (the reference's default AI, planner_steps=5);
     ``planner`` is the BGPlannerAI whose nets they use (a fresh one if None)."""
     from gzero.selfplay import SelfPlayEngine
@@ -248,7 +249,8 @@ def _check_search(search, model, planner_steps) -> bool:
 def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: str = "medium", seed: int = 0,
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
-                         noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True):
+                         noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True,
+                         pv_weights=None):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -270,13 +272,16 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     the live games' rows; the active count rides in the step's one host read.  The rows,
     visit rows and n are the same bytes either way; stats["moves_played"] no longer
     counts the unwanted refill games' moves.  compact=False: continuous refill.
+    pv_weights: the PVWeights the leaves are evaluated with (None: model.device_weights());
+    its precision is the search's -- "f16" runs GZ_PV_F16, a third of the tower's MFMAs.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
     c_puct = {"easy": 1.4, "medium": 1.6, "hard": 1.8}[difficulty]
     slots = min(n_slots, n_games)
     eng = SelfPlayEngine(n_slots=slots, num_simulations=num_simulations, c_puct=c_puct, seed=seed,
-                         pv_weights=model.device_weights(), plies_per_step=plies_per_step,
+                         pv_weights=pv_weights if pv_weights is not None else model.device_weights(),
+                         plies_per_step=plies_per_step,
                          game_id_base=game_id_base, search="puct", temp_plies=temp_plies, tree_reuse=tree_reuse,
                          rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
                          dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round,
@@ -356,7 +361,8 @@ def selfplay_device(n_games: int, id_lo: int, id_hi: int, num_simulations: int =
     raises at once).  The loop
     ends when every one of those games has arrived (the count every rank computes
     from the same chunks, so the ranks stop together), or raises after a bound on
-    the steps the games can take.
+    the steps the games can take.  The incremental tree forward is f16x3 only: an "f16" or
+    "fp32" model runs the full forward of every node at its own precision.
     Returns (device uint8 rows [n, 80], n, stats)."""
     from gzero import dist as gdist
     from gzero.selfplay import SelfPlayEngine
@@ -596,7 +602,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   train_split: float = 0.9, batch_size: int = 128, epochs: int = 2, augment_ratio: float = 0.35,
                   planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8,
                   tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
-                  noise_eps: float = 0.25, leaves_per_round: int = 1) -> dict:
+                  noise_eps: float = 0.25, leaves_per_round: int = 1,
+                  selfplay_precision: Optional[str] = None) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -610,9 +617,14 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     does not carry visit rows yet.  ``tree_reuse`` (search="puct"): self-play keeps the
     subtree under each move for the next ply (selfplay_puct_device).  ``dirichlet_alpha``
     / ``noise_eps`` (search="puct"): Dirichlet noise at the search roots of self-play.
-    ``leaves_per_round`` (search="puct"): leaves per game per round of self-play's search."""
+    ``leaves_per_round`` (search="puct"): leaves per game per round of self-play's search.
+    ``selfplay_precision`` (search="puct"; "fp32" / "f16x3" / "f16"): self-play evaluates
+    its leaves on a second pack of the current parameters at that precision
+    (model.device_weights(precision=...)); predict, validation and the arena keep the
+    model's own."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
+    from gzero.weights import PRECISIONS
     rank, ws = gdist.world()
     if search not in ("reference", "puct"):
         raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
@@ -624,6 +636,11 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError("dirichlet_alpha needs search='puct'")
     if int(leaves_per_round) != 1 and search != "puct":
         raise ValueError("leaves_per_round needs search='puct'")
+    if selfplay_precision is not None:
+        if search != "puct":
+            raise ValueError("selfplay_precision needs search='puct'")
+        if selfplay_precision not in PRECISIONS:
+            raise ValueError(f"unknown precision {selfplay_precision!r}")
     t0 = time.time()
     id_lo = it * ws * games_per_iteration
     replay_base = id_lo + rank * games_per_iteration
@@ -633,7 +650,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                                                    difficulty=difficulty, seed=seed, game_id_base=replay_base,
                                                    model=model, temp_plies=temp_plies, tree_reuse=tree_reuse,
                                                    dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
-                                                   leaves_per_round=leaves_per_round)
+                                                   leaves_per_round=leaves_per_round,
+                                                   pv_weights=model.device_weights(selfplay_precision))
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -708,7 +726,7 @@ def _broadcast_int(x: int) -> int:
 def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int] = None, models_dir: str = "models",
          num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
          temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
-         leaves_per_round: int = 1):
+         leaves_per_round: int = 1, selfplay_precision: Optional[str] = None):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -717,12 +735,16 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     ``search="puct"`` (one rank): self-play by the network-guided search, training on
     its visit distributions (run_iteration); ``dirichlet_alpha`` / ``noise_eps`` add
     Dirichlet noise at its search roots, ``leaves_per_round`` K > 1 evaluates K leaves per
-    game per round (worth it at the default 10 games per iteration)."""
+    game per round (worth it at the default 10 games per iteration),
+    ``selfplay_precision="f16"`` runs self-play's leaf evaluations in GZ_PV_F16 while the
+    model itself stays f16x3."""
     import math
     import os
     from gzero import dist as gdist
     from gzero.train import DeviceTrainer
     from neural_network import GomokuModel
+    if selfplay_precision is not None and search != "puct":
+        raise ValueError("selfplay_precision needs search='puct'")
     rank, ws = gdist.init_from_env()
     seed = int(seed if seed is not None else 20240101)
     random.seed(seed)  # every rank draws the same dataset / split / shuffles
@@ -740,7 +762,7 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
         res = run_iteration(model, trainer, it, games_per_iteration, num_simulations=num_simulations,
                             planner_steps=planner_steps, seed=seed, verbose=rank == 0, search=search,
                             temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
-                            leaves_per_round=leaves_per_round)
+                            leaves_per_round=leaves_per_round, selfplay_precision=selfplay_precision)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

@@ -196,11 +196,23 @@ int gz_selfplay_boards(const void* d_slots, int32_t n_slots, int32_t num_simulat
  * the reference's compact vector is prior[i][empty cells, row-major].
  * precision: GZ_PV_FP32 (exact f32 MFMA) or
  * GZ_PV_F16X3 (3-term fp16 split on the fp16 MFMA, ~22-bit operands, f32
- * accumulation).  d_workspace: gz_pv_workspace_bytes(n) bytes, required (fp32:
- * per-wave slabs; f16x3: the 1x1 head convs' outputs of every board, 2,816 B
- * each, passed from the tower kernel to the batched FC-heads kernel). */
+ * accumulation) or GZ_PV_F16 (below).  d_workspace: gz_pv_workspace_bytes(n)
+ * bytes, required (fp32: per-wave slabs; f16x3 and f16: the 1x1 head convs' outputs
+ * of every board, 2,816 B each, passed from the tower kernel to the batched FC-heads
+ * kernel). */
 #define GZ_PV_FP32 0
 #define GZ_PV_F16X3 1
+/* GZ_PV_F16: the f16x3 forward with the lo terms of the residual tower dropped, one
+ * fp16 MFMA per product where f16x3 issues three.  conv0 as in f16x3 (0/1 inputs,
+ * w_hi + w_lo, fp32 BN, ReLU), its output stored as fp16(x0).  Each residual conv:
+ * acc = sum fp16(w) * a in an f32 accumulator (k order: tap, then 4 x 32 channels), a
+ * the stored fp16 activation; y = relu(fma(acc, S, T) (+ skip)) in fp32, S / T the
+ * blob's fp32 BN affine, skip the block input as stored; y1, x1, y2 stored as
+ * fp16(y).  The last epilogue feeds the 1x1 head convs from its fp32 y (x2 is never
+ * rounded); heads, softmax, value and prior are f16x3's kernels.  Batch-invariant like
+ * f16x3; same workspace.  Opt-in (the PUCT search): its logits differ from the fp32
+ * forward's by ~1e-4 at init weights, more at trained magnitudes. */
+#define GZ_PV_F16 2
 size_t gz_pv_weight_floats(void);
 size_t gz_pv_workspace_bytes(int32_t n);
 int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, int32_t n, const int32_t* d_count,
@@ -222,7 +234,8 @@ int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, int32_t n, c
  * board does not differ from its parent's by exactly one cell is ignored (full
  * forward), so the tags only decide speed.  d_workspace:
  * gz_pv_tree_workspace_bytes(n, root_cap) bytes (~2.4 MB per root: maps 512 KB,
- * pre-BN accumulators 512 KB, 16 patches of 84 KB). */
+ * pre-BN accumulators 512 KB, 16 patches of 84 KB).  It has no precision argument:
+ * the tree forward is f16x3 only (there is no GZ_PV_F16 tree forward). */
 size_t gz_pv_tree_workspace_bytes(int32_t n, int32_t root_cap);
 int gz_pv_forward_tree(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta, int32_t n,
                        const int32_t* d_count, int32_t root_cap, float* d_logits, float* d_value, float* d_probs,
@@ -326,7 +339,7 @@ typedef struct gz_puct_params {
     int32_t temp_plies;      /* plies (move counts below this) that sample the move from the visits */
     double c_puct;
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
-    int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3: gz_puct_search's forward */
+    int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3 / GZ_PV_F16: the forward of every search and self-play entry */
     int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH */
 } gz_puct_params;
 /* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).

@@ -68,6 +68,15 @@ against the parent build, as --leaves 1 measures it.
 
     python tools/puct_bench.py --compact --precisions f16x3 --steps 3 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/compact_bench.json
+
+--precision f16x3|f16|fp32 runs the lock-step, --reuse or --leaves measurement at that one
+precision (it replaces --precisions).  "f16" is the one-term fp16 tower (GZ_PV_F16); a child
+that loads another build (--forward-library, --lockstep-library: the parent commit, which
+has no f16) runs f16x3 instead, so every f16 figure stands beside the parent's f16x3 of the
+same call.
+
+    python tools/puct_bench.py --precision f16 --forward-library parent/libgzero.so
+    python tools/puct_bench.py --reuse --precision f16 --lockstep-library parent/libgzero.so
 """
 import argparse
 import json
@@ -84,6 +93,8 @@ ap.add_argument("--sims", type=int, default=200)
 ap.add_argument("--burn", type=int, default=24, help="burn-in plies (8 simulations each)")
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--precisions", default="f16x3,fp32")
+ap.add_argument("--precision", default=None, choices=["f16x3", "f16", "fp32"],
+                help="the one precision of the lock-step, --reuse or --leaves measurement (replaces --precisions)")
 ap.add_argument("--temp-plies", type=int, default=12)
 ap.add_argument("--forward-library", default=None, help="libgzero.so the standalone forward is timed on")
 ap.add_argument("--forward-only", action="store_true", help="(child) time gz_pv_forward alone, print JSON")
@@ -110,7 +121,12 @@ ap.add_argument("--compact-child", default=None, metavar="on|off:NOISE",
                 help="(child) compaction on or off, then off or ALPHA,EPS: one iteration of --slots games on request")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
-precisions = a.precisions.split(",")
+precisions = [a.precision] if a.precision else a.precisions.split(",")
+
+
+def other_build(prec, library):
+    """The precision a child runs that loads `library`: another build has no "f16"."""
+    return "f16x3" if library and prec == "f16" else prec
 
 
 def median(xs):
@@ -215,8 +231,9 @@ def reuse_run(prec, scale):
     if a.lockstep_library:
         env["GZ_LIBRARY"] = os.path.abspath(a.lockstep_library)
     child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--lockstep-child", repr(scale), "--slots",
-                              str(a.slots), "--sims", str(a.sims), "--burn", str(a.burn), "--precisions", prec,
-                              "--temp-plies", str(a.temp_plies)], env=env, stdin=subprocess.PIPE,
+                              str(a.slots), "--sims", str(a.sims), "--burn", str(a.burn), "--precisions",
+                              other_build(prec, a.lockstep_library), "--temp-plies", str(a.temp_plies)], env=env,
+                             stdin=subprocess.PIPE,
                              stdout=subprocess.PIPE, text=True)
     try:
         if child.stdout.readline().strip() != "READY":
@@ -268,7 +285,8 @@ def reuse_run(prec, scale):
         "windows (slot statistics) / those moves", "slot_rounds_per_window_move": n * window * len(wins) / moves,
         "moves_per_s": rate, "moves_per_s_source": "slots / (mean rounds per move x median ms per round)",
         "moves_per_s_counted_in_windows": moves / (ms / 1e3),
-        "lockstep": {"step_ms": steps, "step_ms_median": median(steps), "round_ms": lock_round,
+        "lockstep": {"precision": other_build(prec, a.lockstep_library), "step_ms": steps,
+                     "step_ms_median": median(steps), "round_ms": lock_round,
                      "rounds_per_move": S + 1, "moves_per_s": n / (median(steps) / 1e3)},
         "round_ms_over_lockstep_round_ms": median(round_ms) / lock_round,
         "measured_speedup_rounds": (S + 1) / rpm,
@@ -573,7 +591,8 @@ def leaves_run(prec, slots, ks):
                 env["GZ_LIBRARY"] = os.path.abspath(library)
             kids[name] = subprocess.Popen(
                 [sys.executable, os.path.abspath(__file__), "--leaves-child", spec, "--slots", str(slots), "--sims",
-                 str(S), "--burn", str(a.burn), "--precisions", prec, "--temp-plies", str(a.temp_plies)],
+                 str(S), "--burn", str(a.burn), "--precisions", other_build(prec, library), "--temp-plies",
+                 str(a.temp_plies)],
                 env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
         for name, kid in kids.items():
             ready = kid.stdout.readline().strip()
@@ -660,7 +679,7 @@ if a.leaves:
     prec = precisions[0]
     ks = [int(x) for x in a.leaves.split(",")]
     res = {"config": {"simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies, "precision": prec,
-                      "steps": a.steps, "leaves": ks,
+                      "parent_precision": other_build(prec, a.lockstep_library), "steps": a.steps, "leaves": ks,
                       "timing": "device events around one lock-step step (one move per slot); two child processes "
                                 "(this build: one engine per K; the parent build: K = 1) take turns",
                       "rounds": "counted by an untimed search of the same boards through the step API before "
@@ -748,11 +767,25 @@ if a.reuse:
 env = dict(os.environ)
 if a.forward_library:
     env["GZ_LIBRARY"] = os.path.abspath(a.forward_library)
-child = subprocess.run([sys.executable, os.path.abspath(__file__), "--forward-only", "--slots", str(a.slots),
-                        "--precisions", a.precisions], env=env, capture_output=True, text=True, timeout=300)
-if child.returncode != 0:
-    sys.exit(f"forward-only child failed ({child.returncode}):\n{child.stdout}\n{child.stderr}")
-fwd = json.loads([ln for ln in child.stdout.splitlines() if ln.startswith("FORWARD_JSON ")][-1][len("FORWARD_JSON "):])
+
+
+def forward_child(env, precs):
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--forward-only", "--slots", str(a.slots),
+                            "--precisions", ",".join(precs)], env=env, capture_output=True, text=True, timeout=300)
+    if child.returncode != 0:
+        sys.exit(f"forward-only child failed ({child.returncode}):\n{child.stdout}\n{child.stderr}")
+    return json.loads([ln for ln in child.stdout.splitlines() if ln.startswith("FORWARD_JSON ")][-1][len("FORWARD_JSON "):])
+
+
+# (another build has no f16: it times its f16x3 instead, and this build times the f16)
+fwd = forward_child(env, list(dict.fromkeys(other_build(p, a.forward_library) for p in precisions)))
+fwd_other_f16x3 = None
+if a.forward_library and "f16" in precisions:
+    fwd_other_f16x3 = fwd["f16x3"]
+    mine = forward_child(dict(os.environ), ["f16"] + (["f16x3"] if "f16x3" not in precisions else []))
+    fwd["f16"] = mine["f16"]
+    if "f16x3" not in precisions:
+        fwd["f16x3_this_build"] = mine["f16x3"]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -810,6 +843,10 @@ for prec in precisions:
         "forward_standalone_ms": fwd[prec], "forwards_alone_ms": alone,
         "search_and_gaps_share_of_step": 1.0 - alone / t,
     }
+    if prec == "f16" and fwd_other_f16x3:
+        res["results"][prec]["forward_standalone_ms_f16x3_other_build"] = fwd_other_f16x3
+        if "f16x3_this_build" in fwd:
+            res["results"][prec]["forward_standalone_ms_f16x3_this_build"] = fwd["f16x3_this_build"]
     print(f"{prec}: {n / (t / 1e3):.0f} moves/s, step {t:.1f} ms; per round select "
           f"{median(stage['select']):.3f} / forward {median(stage['forward']):.3f} / backup "
           f"{median(stage['backup']):.3f} ms; {S + 1} standalone forwards {alone:.1f} ms")
