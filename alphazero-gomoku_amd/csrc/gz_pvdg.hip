@@ -22,9 +22,10 @@
 // Gather with tap skipping: a pass's output rows (every on-board position of each
 // node's radius-(L+2) square) are MFMA M rows; row p needs tap t only if p + t lies in
 // the D square (and on the board) -- a set TY x TX.  The rows are counting-sorted by
-// that class, so a 16-row tile's tap set (the union of its rows') is small, and a
-// tile runs only its taps: 102 tile-taps per node on real searches (92 for the
-// unclipped ideal), against 124 for the exact recomputation of the squares -- the delta
+// that class in an order that puts each tap set next to its supersets (gz_dgclass.h),
+// so a 16-row tile's tap set (the union of its rows') is small, and a tile runs only
+// its taps: 95 tile-taps per node on real searches (92 for the unclipped
+// ideal), against 124 for the exact recomputation of the squares -- the delta
 // form's saving without pv_delta_kernel's scatter (an LDS read-add-write of the
 // accumulators per tap).  Accumulators stay in registers for the whole pass; the D
 // squares of the pass's nodes sit in LDS ([plane][16 cg][position][8], a node's square
@@ -37,10 +38,14 @@
 // first nodes (y1 -> x1 of nodes 0-2, y2 -> x2 of node 2k): those squares go from the
 // epilogue straight into the next pass's LDS image.  A node with grandchildren also
 // writes its CHILD values into its patch slot for pv_sib_kernel (gz_pvinc.hip).
+// A lane owns the 8 channels of one 16-byte slot of those layouts (dg_ch0 below), so
+// per row and plane each of these is ONE 16-byte access: the D store, the patch store,
+// the LDS hand-off write, the skip load and conv0's root-x0 load.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
+#include "gz_dgclass.h"
 #include "gz_internal.h"
 #include "gz_pvtree.h"
 
@@ -188,14 +193,29 @@ __device__ __forceinline__ void gst(void* p, const T& v) {
     *(GZ_GLB T*)DG_CHK(p, 1) = v;
 }
 
+// ------------------------------------------------------------------ lanes and channels
+// Wave np's two n-tiles cover channels [32 np, 32 np + 32).  Of n-tile n, lane (q = lane
+// >> 4) holds the accumulators of channels 32 np + 8 q + 4 n + r, r = 0..3: with both
+// n-tiles the 8 channels of ONE 16-byte slot of the [plane][16 cg][position][8] layouts
+// (channel group 4 np + q), so every D / patch / image store and every skip / x0 load of a
+// row is one 16-byte access per plane.  (In channel order, (2 np + n) * 16 + 4 q + r, a
+// lane held half of two slots: twice the instructions, 8 bytes each.)
+// MFMA output row i = 4 q + r of n-tile n is then channel 32 np + 8 (i >> 2) + 4 n + (i & 3),
+// so A-operand lane l (i = l & 15) holds that channel's weights -- in the fragment arrays
+// (F16_RES0, F16_C0: [k-step][n-tile][lane][8] halves, channel order) n-tile 2 np + (i >> 3),
+// lane (l & 48) | (8 ((i >> 2) & 1) + 4 n + (i & 3)): a wave still reads its 2 KB per k-step.
+__device__ __forceinline__ int dg_ch0(int np, int q, int n) { return 32 * np + 8 * q + 4 * n; }
+// the lane's fragment ([n-tile][lane] index) of n-tile 0; n-tile 1's is DG_WFRAG_N further
+__device__ __forceinline__ int dg_wfrag(int np, int lane) {
+    const int i = lane & 15;
+    return (2 * np + (i >> 3)) * 64 + ((lane & 48) | (8 * ((i >> 2) & 1) + (i & 3)));
+}
+constexpr int DG_WFRAG_N = 4;
+
 // ------------------------------------------------------------------ rows of a pass
 // row entry: node (4 bits) | dy + RO (4) << 4 | dx + RO (4) << 8 | tap mask (9) << 12 |
 // valid << 21; tap bit (ty + 1) * 3 + (tx + 1)
-// class rank of a tap set (bit 0: -1, bit 1: 0, bit 2: +1) in the order {-1,0,1},
-// {-1,0}, {-1}, {0,1}, {0}, {1}: neighbouring classes share taps
-__device__ __forceinline__ int set_rank(int b) {
-    return b == 7 ? 0 : (b == 3 ? 1 : (b == 1 ? 2 : (b == 6 ? 3 : (b == 2 ? 4 : 5))));
-}
+// class rank of the row's tap sets: dg_class_rank (gz_dgclass.h)
 
 // The row tables of every pass of the chunk (nodes U[0, ng)), counting-sorted by class,
 // then per pass and tap the tiles that need it.  Ends with the tables written but NOT
@@ -239,7 +259,7 @@ __device__ __forceinline__ void dg_rows_all(char* lds, const DgUnit* U, int ng, 
             if ((ty >> a) & 1) m |= (uint32_t)tx << (3 * a);
         const int gl = L == 0 ? 0 : (L == 1 ? 3 : (L == 2 ? 2 : 1));  // nodes per pass of layer L (g(L))
         const int p = K::pass_of(L, gi), u0 = L == 0 ? 0 : (gi / gl) * gl;
-        kk[i] = p * K::NKEY + set_rank(ty) * 6 + set_rank(tx);
+        kk[i] = p * K::NKEY + dg_class_rank(ty, tx);
         ent[i] = (uint32_t)(gi - u0) | ((uint32_t)(dy + RO) << 4) | ((uint32_t)(dx + RO) << 8) | (m << 12) | (1u << 21);
         rank[i] = (int)atomicAdd(&hist[kk[i]], 1u);
     }
@@ -289,7 +309,8 @@ __device__ __forceinline__ void dg_rows_all(char* lds, const DgUnit* U, int ng, 
 }
 
 // ------------------------------------------------------------------ the k-loop
-// The pass's residual conv for the wave's n-tiles {nt0, nt0+1} over NT output tiles:
+// The pass's residual conv for the wave's two n-tiles (wave nt0 / 2's 32 channels in the
+// lane order of dg_ch0, the weight fragments picked by dg_wfrag) over NT output tiles:
 // per tap, per 32-channel k-step (the full kernel's k order and its 3 products:
 // w_hi a_hi, w_lo a_hi, w_hi a_lo), the tiles that need the tap.  ri[m]: the lane's row
 // of tile m: (D-square index of its position + 32) | tap mask << 16.  Activation
@@ -305,9 +326,9 @@ __device__ __forceinline__ void dg_kloop(const char* lds, const uint32_t (&ri)[K
     constexpr int KS_BYTES = 8 * 64 * 8 * 2, LO_BYTES = KS * KS_BYTES, RING = 4;
     const int lb = K::IN + (lane >> 4) * NPOS * 16;
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)Wf, 0, 0x7fffffff, 0x00020000);
-    const int wo = (nt0 * 64 + lane) * 16;
+    const int wo = dg_wfrag(nt0 >> 1, lane) * 16;
     auto wload = [&](int ks, int n, int lo) -> h8 {
-        return __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wo, ks * KS_BYTES + n * 1024 + lo * LO_BYTES, 0));
+        return __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wo, ks * KS_BYTES + n * DG_WFRAG_N * 16 + lo * LO_BYTES, 0));
     };
     auto addr = [&](int tap, uint32_t r) -> int {
         const int toff = (tap / 3 - 1) * S + (tap - (tap / 3) * 3 - 1);
@@ -397,33 +418,33 @@ __device__ __forceinline__ void dg_kloop(const char* lds, const uint32_t (&ri)[K
 }
 
 // ------------------------------------------------------------------ epilogue
-struct H4x2 {
-    h4 h, l;
+// a 16-byte slot (the lane's 8 channels: n-tile 0's four, then n-tile 1's), hi and lo planes
+struct H8x2 {
+    h8 h, l;
 };
-__device__ __forceinline__ float h2f(const H4x2& x, int r) { return (float)x.h[r] + (float)x.l[r]; }
-// v split into hi / lo halves at p (global memory) and p + plane_halves
-__device__ __forceinline__ void put_hl(_Float16* p, int plane_halves, const f32x4& v) {
-    h4 hi, lo;
+__device__ __forceinline__ float h2f(const H8x2& x, int r) { return (float)x.h[r] + (float)x.l[r]; }
+// the lane's values of both n-tiles split into hi / lo halves
+__device__ __forceinline__ H8x2 split_hl(const f32x4 (&v)[2]) {
+    H8x2 o;
 #pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const _Float16 h = (_Float16)v[r];
-        hi[r] = h;
-        lo[r] = (_Float16)(v[r] - (float)h);
-    }
-    gst<h4>(p, hi);
-    gst<h4>(p + plane_halves, lo);
+    for (int n = 0; n < 2; n++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const _Float16 h = (_Float16)v[n][r];
+            o.h[4 * n + r] = h;
+            o.l[4 * n + r] = (_Float16)(v[n][r] - (float)h);
+        }
+    return o;
+}
+// a slot at p (global memory), its lo plane at p + plane_halves
+__device__ __forceinline__ void put_hl(_Float16* p, int plane_halves, const H8x2& x) {
+    gst<h8>(p, x.h);
+    gst<h8>(p + plane_halves, x.l);
 }
 // the same into LDS
-__device__ __forceinline__ void put_hl_lds(_Float16* p, int plane_halves, const f32x4& v) {
-    h4 hi, lo;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const _Float16 h = (_Float16)v[r];
-        hi[r] = h;
-        lo[r] = (_Float16)(v[r] - (float)h);
-    }
-    *(h4*)p = hi;
-    *(h4*)(p + plane_halves) = lo;
+__device__ __forceinline__ void put_hl_lds(_Float16* p, int plane_halves, const H8x2& x) {
+    *(h8*)p = x.h;
+    *(h8*)(p + plane_halves) = x.l;
 }
 
 // The epilogue of a pass (layer L, nodes U[0, g), row table rt): per row,
@@ -439,12 +460,12 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
     constexpr int RS = L == 1 ? 1 : 3, SK = 2 * RS + 1, SSK = SK * SK;
     constexpr int GB = K::GB, NGRP = (K::NMAX + GB - 1) / GB, ST = 2;
     float* hpart = (float*)(lds + K::HP);
-    const int q = lane >> 4, li = lane & 15;
+    const int q = lane >> 4, li = lane & 15, cg = 4 * np + q;  // cg: the lane's channel group (dg_ch0 >> 3)
     const float* cst = (const float*)(lds + K::CST);  // staged at kernel start
     f32x4 es[2], e0[2], e1[2], ev[2];
 #pragma unroll
     for (int n = 0; n < 2; n++) {
-        const int ch0 = (2 * np + n) * 16 + 4 * q;
+        const int ch0 = dg_ch0(np, q, n);
         es[n] = *(const f32x4*)(cst + L * 128 + ch0);
         if (L == 3) {
             e0[n] = *(const f32x4*)(cst + 512 + ch0);
@@ -453,7 +474,7 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
         }
     }
     f32x4 z[ST][GB][2];
-    H4x2 dk[ST][GB][2];
+    H8x2 dk[ST][GB];
     uint32_t ent[ST][GB];
     auto loads = [&](int grp, int st) {
 #pragma unroll
@@ -470,13 +491,11 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
             const bool near = SKIP && v && iabs(dy) <= RS && iabs(dx) <= RS;
             const int sidx = near ? (dy + RS) * SK + (dx + RS) : 0;
 #pragma unroll
-            for (int n = 0; n < 2; n++) {
-                const int ch0 = (2 * np + n) * 16 + 4 * q;
-                z[st][j][n] = gld<f32x4>(u.pre + L * PV_PRE_FLOATS + pos * CH + ch0);
-                if (SKIP) {
-                    const _Float16* p = u.own + u.sq[L - 1] + ((ch0 >> 3) * SSK + sidx) * 8 + (ch0 & 7);
-                    dk[st][j][n] = H4x2{gld<h4>(p), gld<h4>(p + 16 * SSK * 8)};
-                }
+            for (int n = 0; n < 2; n++)
+                z[st][j][n] = gld<f32x4>(u.pre + L * PV_PRE_FLOATS + pos * CH + dg_ch0(np, q, n));
+            if (SKIP) {
+                const _Float16* p = u.own + u.sq[L - 1] + (cg * SSK + sidx) * 8;
+                dk[st][j] = H8x2{gld<h8>(p), gld<h8>(p + 16 * SSK * 8)};
             }
         }
     };
@@ -498,37 +517,35 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
             const bool near = SKIP && iabs(dy) <= RS && iabs(dx) <= RS;
             const int oidx = (dy + RO) * SO + (dx + RO);
             float s0 = 0.f, s1 = 0.f, sv = 0.f;
+            f32x4 y[2], d[2];
 #pragma unroll
             for (int n = 0; n < 2; n++) {
-                const int ch0 = (2 * np + n) * 16 + 4 * q;
-                f32x4 y, d;
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const float zr = z[st][j][n][r];
                     float tc = __builtin_fmaf(acc[n][m][r], es[n][r], zr);
-                    if (SKIP) tc += near ? h2f(dk[st][j][n], r) : 0.f;
+                    if (SKIP) tc += near ? h2f(dk[st][j], 4 * n + r) : 0.f;
                     tc = tc > 0.f ? tc : 0.f;
                     if (L == 3) {
                         s0 = __builtin_fmaf(e0[n][r], tc, s0);
                         s1 = __builtin_fmaf(e1[n][r], tc, s1);
                         sv = __builtin_fmaf(ev[n][r], tc, sv);
                     } else {
-                        y[r] = tc;
-                        d[r] = tc - (zr > 0.f ? zr : 0.f);
+                        y[n][r] = tc;
+                        d[n][r] = tc - (zr > 0.f ? zr : 0.f);
                     }
                 }
-                if (L < 3 && v) {
-                    const DgUnit& u = U[gi];
-                    const int o = PATCH_OFF[L + 1] + ((ch0 >> 3) * SSO + oidx) * 8 + (ch0 & 7);
-                    if (gi < ldsg) {  // the next pass's image (dg_fill<L + 1>'s layout)
-                        constexpr int NPN = K::npos(L + 1 < 4 ? L + 1 : 3), SSN = SSO;
-                        put_hl_lds((_Float16*)(lds + K::IN) + ((ch0 >> 3) * NPN + gi * SSN + oidx) * 8 + (ch0 & 7),
-                                   16 * NPN * 8, d);
-                    } else {
-                        put_hl(u.own + u.sq[L + 1] + ((ch0 >> 3) * SSO + oidx) * 8 + (ch0 & 7), 16 * SSO * 8, d);
-                    }
-                    if (u.patch) put_hl(u.patch + o, 16 * SSO * 8, y);
+            }
+            if (L < 3 && v) {  // the lane's slot (channel group cg) of the row's position
+                const DgUnit& u = U[gi];
+                const H8x2 dd = split_hl(d);
+                if (gi < ldsg) {  // the next pass's image (dg_fill<L + 1>'s layout)
+                    constexpr int NPN = K::npos(L + 1 < 4 ? L + 1 : 3), SSN = SSO;
+                    put_hl_lds((_Float16*)(lds + K::IN) + (cg * NPN + gi * SSN + oidx) * 8, 16 * NPN * 8, dd);
+                } else {
+                    put_hl(u.own + u.sq[L + 1] + (cg * SSO + oidx) * 8, 16 * SSO * 8, dd);
                 }
+                if (u.patch) put_hl(u.patch + PATCH_OFF[L + 1] + (cg * SSO + oidx) * 8, 16 * SSO * 8, split_hl(y));
             }
             if (L == 3) {
                 s0 += __shfl_xor(s0, 16);
@@ -618,7 +635,9 @@ __device__ __forceinline__ void dg_fill(char* lds, const DgUnit* U, int g, int t
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const int pc = wave * 8 + k;
-                __builtin_amdgcn_global_load_lds((glb_void_t*)DG_CHK(src + pc * stride, 2), (lds_void_t*)(dst + pc * NPOS * 16),
+                // (the zero source is a device global, not part of the workspace the check knows)
+                const _Float16* sp = src + pc * stride;
+                __builtin_amdgcn_global_load_lds((glb_void_t*)(stride ? DG_CHK(sp, 2) : sp), (lds_void_t*)(dst + pc * NPOS * 16),
                                                  16, 0, 0);
             }
         }
@@ -654,13 +673,13 @@ __device__ __forceinline__ void dg_col(_Float16* col, const DgUnit* U, int ng, i
 __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const DgUnit* U, int ng,
                                          const float* __restrict__ W, int np, int lane) {
     constexpr int NPOS = K::npos(0);
-    const int li = lane & 15, q = lane >> 4;
+    const int li = lane & 15, q = lane >> 4, cg = 4 * np + q;
     h8 wh[2], wl[2];
     f32x4 ws[2], wt[2];
 #pragma unroll
     for (int n = 0; n < 2; n++) {
-        const int nt = 2 * np + n, ch0 = nt * 16 + 4 * q;
-        const _Float16* wf = (const _Float16*)(W + F16_C0) + ((size_t)nt * 64 + lane) * 8;
+        const int ch0 = dg_ch0(np, q, n);
+        const _Float16* wf = (const _Float16*)(W + F16_C0) + (size_t)(dg_wfrag(np, lane) + n * DG_WFRAG_N) * 8;
         wh[n] = *(const h8*)wf;
         wl[n] = *(const h8*)(wf + 8 * 64 * 8);
         ws[n] = *(const f32x4*)(W + C0_S + ch0);
@@ -668,7 +687,7 @@ __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const D
     }
     _Float16* in = (_Float16*)(lds + K::IN);
     // every node's root x0 values first (one round of latency for the chunk), then the MFMAs
-    h4 rxh[K::C][2], rxl[K::C][2];
+    h8 rxh[K::C], rxl[K::C];
 #pragma unroll
     for (int g = 0; g < K::C; g++) {
         const DgUnit& u = U[g < ng ? g : 0];
@@ -677,13 +696,9 @@ __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const D
         const int c0 = cc > 0 ? cc - 1 : 0, c1 = cc < BN - 1 ? cc + 1 : BN - 1, wr = c1 - c0 + 1;
         const bool rowok = li < (r1 - r0 + 1) * wr;
         const int pr = rowok ? r0 + li / wr : cr, pc = rowok ? c0 + li % wr : cc, pos = pr * BN + pc;
-#pragma unroll
-        for (int n = 0; n < 2; n++) {
-            const int ch0 = (2 * np + n) * 16 + 4 * q;
-            const _Float16* rp = u.gm + ((ch0 >> 3) * 256 + pos) * 8 + (ch0 & 7);
-            rxh[g][n] = gld<h4>(rp);
-            rxl[g][n] = gld<h4>(rp + PV_MAP_PLANE);
-        }
+        const _Float16* rp = u.gm + (cg * 256 + pos) * 8;
+        rxh[g] = gld<h8>(rp);
+        rxl[g] = gld<h8>(rp + PV_MAP_PLANE);
     }
 #pragma unroll
     for (int g = 0; g < K::C; g++) {
@@ -696,27 +711,26 @@ __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const D
         const bool rowok = li < (r1 - r0 + 1) * wr;
         const int pr = rowok ? r0 + li / wr : cr, pc = rowok ? c0 + li % wr : cc;
         const int idx = (pr - cr + 1) * 3 + (pc - cc + 1);
+        f32x4 y[2], d[2];
 #pragma unroll
         for (int n = 0; n < 2; n++) {
-            const int ch0 = (2 * np + n) * 16 + 4 * q;
             f32x4 acc = zero4();
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[n], a, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[n], a, acc, 0, 0, 0);
-            if (rowok) {
-                const h4 rh = rxh[g][n], rl = rxl[g][n];  // the root's x0
-                f32x4 y, d;
 #pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    float t = __builtin_fmaf(acc[r], ws[n][r], wt[n][r]);
-                    t = t > 0.f ? t : 0.f;
-                    y[r] = t;
-                    d[r] = t - ((float)rh[r] + (float)rl[r]);
-                }
-                put_hl_lds(in + ((ch0 >> 3) * NPOS + g * 9 + idx) * 8 + (ch0 & 7), 16 * NPOS * 8, d);
-                const int o = PATCH_OFF[0] + ((ch0 >> 3) * 9 + idx) * 8 + (ch0 & 7);
-                put_hl(u.own + u.sq[0] + o, 16 * 9 * 8, d);
-                if (u.patch) put_hl(u.patch + o, 16 * 9 * 8, y);
+            for (int r = 0; r < 4; r++) {
+                float t = __builtin_fmaf(acc[r], ws[n][r], wt[n][r]);
+                t = t > 0.f ? t : 0.f;
+                y[n][r] = t;
+                d[n][r] = t - ((float)rxh[g][4 * n + r] + (float)rxl[g][4 * n + r]);  // the root's x0
             }
+        }
+        if (rowok) {
+            const H8x2 dd = split_hl(d);
+            put_hl_lds(in + (cg * NPOS + g * 9 + idx) * 8, 16 * NPOS * 8, dd);
+            const int o = PATCH_OFF[0] + (cg * 9 + idx) * 8;
+            put_hl(u.own + u.sq[0] + o, 16 * 9 * 8, dd);
+            if (u.patch) put_hl(u.patch + o, 16 * 9 * 8, split_hl(y));
         }
     }
 }
@@ -941,7 +955,7 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
             // y2(2k, 2k+1) -> x2(2k)), those nodes' D squares go straight into the next
             // pass's LDS image (dg_fill's layout) instead of the scratch: no store, no fill,
             // no drain; the pass's other nodes go through the scratch as before.  (The
-            // epilogue's scattered 8-B stores of the D squares are 15 % of the kernel.)
+            // epilogue's scattered stores of the D squares are 15 % of the kernel.)
             const int ldsg = more && L2 == L + 1 && v0 == u0 && (L == 0 || L == 2) ? g2 : 0;
             const bool to_lds = ldsg > 0;
             if (L == 0) dg_epilogue<0>(lds, U + u0, rt, np, t & 63, acc, nt, ldsg);
