@@ -91,7 +91,18 @@ class SelfplayCounters(ctypes.Structure):
                 ("moves", ctypes.c_int64), ("games", ctypes.c_int64), ("mcts_moves", ctypes.c_int64)]
 
 
+class PuctMatchParams(ctypes.Structure):  # gz_puct_match_params, 40 bytes
+    _fields_ = [("search", ctypes.c_void_p), ("d_weights", ctypes.c_void_p * 2),
+                ("precision", ctypes.c_int32 * 2), ("a_black_parity", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class PuctMatchTally(ctypes.Structure):  # gz_puct_match_tally, 72 bytes
+    _fields_ = [(k, ctypes.c_int64) for k in ("games", "a_wins", "b_wins", "draws", "a_wins_black", "a_wins_white",
+                                              "b_wins_black", "b_wins_white", "plies")]
+
+
 assert ctypes.sizeof(BoardState) == 80 and ctypes.sizeof(Record) == 80
+assert ctypes.sizeof(PuctMatchParams) == 40 and ctypes.sizeof(PuctMatchTally) == 72
 assert ctypes.sizeof(PuctParams) == 32 and ctypes.sizeof(PuctNoiseParams) == 48
 assert ctypes.sizeof(PuctBatchParams) == 56
 assert ctypes.sizeof(SearchStats) == 24 and ctypes.sizeof(SelfplayCounters) == 40
@@ -200,6 +211,10 @@ SIGNATURES = {
     "gz_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "gz_selfplay_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "gz_puct_remaining": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
+    "gz_puct_match_workspace_bytes": (_SZ, [_I32, _I32]),
+    "gz_puct_match_run": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(PuctMatchParams), _P, _I32, _P, _I32, _P, _P,
+                                         _P]),
+    "gz_puct_match_results": (ctypes.c_int, [_P, _I32, _I32, _I64, _I32, _P, _P, _P]),
     "gz_puct_root_noise": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
     "gz_puct_root_noise_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, ctypes.c_double, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),

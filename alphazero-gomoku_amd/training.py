@@ -474,7 +474,7 @@ class RandomAgent:
 def evaluate_model(current, baseline, device=None, games: int = 8, eval_difficulty: str = "easy",
                    eval_num_sim: int = 60, eval_plans: int = 2, seed: Optional[int] = None,
                    return_games: bool = False, alternate: bool = True, seeds: Optional[Tuple[int, int]] = None,
-                   game_id_base: int = 0):
+                   game_id_base: int = 0, search: str = "reference", puct: Optional[dict] = None):
     """training.py:221-270 with all ``games`` played at once: every ply, the games
     whose side to move belongs to the same agent are searched in ONE batched GPU
     call (AlphaZeroGomokuAI.get_moves).  As in the reference the evaluated model
@@ -488,7 +488,15 @@ def evaluate_model(current, baseline, device=None, games: int = 8, eval_difficul
     ``evaluate_model(..., games=1)`` calls amount to (training.py:484-492).
     ``seeds`` = (seed_a, seed_b) overrides the pair derived from ``seed``; game g
     uses game id ``game_id_base + g`` (tests/golden arena fixture: one seed for
-    both sides, as the reference's single global stream)."""
+    both sides, as the reference's single global stream).
+    ``search="puct"``: the two networks play a device-side match of the network-guided
+    search instead (gzero.arena.play_match: ``eval_num_sim`` simulations, the difficulty's
+    c_puct, colours alternating, ``current`` black in the first game); it needs a baseline
+    -- a random opponent is not a network -- and ``puct`` holds further play_match
+    keywords (temp_plies, precision_a, precision_b, dirichlet_alpha, noise_eps)."""
+    if search != "reference":
+        return _evaluate_puct(current, baseline, search, games, eval_difficulty, eval_num_sim, seed, return_games,
+                              alternate, game_id_base, puct)
     from ai_agent import AlphaZeroGomokuAI
     seed = random.getrandbits(64) if seed is None else int(seed)
     seed_a, seed_b = seed, (seed * 0x9E3779B97F4A7C15 + 1) & ((1 << 64) - 1)
@@ -545,6 +553,23 @@ def evaluate_model(current, baseline, device=None, games: int = 8, eval_difficul
                         for g in range(games)]
         out["seeds"] = (seed_a, seed_b)
     return out
+
+
+def _evaluate_puct(current, baseline, search, games, eval_difficulty, eval_num_sim, seed, return_games, alternate,
+                   game_id_base, puct):
+    """evaluate_model(search="puct"): the arguments checked, then gzero.arena.play_match."""
+    if search != "puct":
+        raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
+    if baseline is None:
+        raise ValueError("search='puct' needs a baseline: a random opponent is not a network")
+    if not alternate:
+        raise ValueError("search='puct' alternates colours by game (alternate=False is not supported)")
+    from gzero.arena import play_match
+    kw = dict(puct or {})
+    kw.setdefault("c_puct", {"easy": 1.4, "medium": 1.6, "hard": 1.8}[eval_difficulty])
+    seed = random.getrandbits(64) if seed is None else int(seed)
+    return play_match(current, baseline, games=games, num_simulations=eval_num_sim, seed=seed,
+                      game_id_base=game_id_base, return_games=return_games, **kw)
 
 
 # ---------------------------------------------------------------- SGD (training.py:277-337)
@@ -726,7 +751,7 @@ def _broadcast_int(x: int) -> int:
 def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int] = None, models_dir: str = "models",
          num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
          temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
-         leaves_per_round: int = 1, selfplay_precision: Optional[str] = None):
+         leaves_per_round: int = 1, selfplay_precision: Optional[str] = None, arena_search: str = "reference"):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -737,7 +762,11 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     Dirichlet noise at its search roots, ``leaves_per_round`` K > 1 evaluates K leaves per
     game per round (worth it at the default 10 games per iteration),
     ``selfplay_precision="f16"`` runs self-play's leaf evaluations in GZ_PV_F16 while the
-    model itself stays f16x3."""
+    model itself stays f16x3.
+    ``arena_search="puct"``: rank 0's per-iteration arena is a device-side match of the
+    network-guided search between the model and the best snapshot
+    (evaluate_model(search="puct"), colours alternating), so the win rate printed depends
+    on the two networks; the default arena plays the reference's search."""
     import math
     import os
     from gzero import dist as gdist
@@ -745,6 +774,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     from neural_network import GomokuModel
     if selfplay_precision is not None and search != "puct":
         raise ValueError("selfplay_precision needs search='puct'")
+    if arena_search not in ("reference", "puct"):
+        raise ValueError(f"arena_search must be 'reference' or 'puct', not {arena_search!r}")
     rank, ws = gdist.init_from_env()
     seed = int(seed if seed is not None else 20240101)
     random.seed(seed)  # every rank draws the same dataset / split / shuffles
@@ -773,6 +804,7 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
         # everywhere -- DeviceTrainer.validate_epoch all-reduces it -- so this only
         # guards the early stop and the torch-RNG use of the snapshot against drift)
         improved = bool(_broadcast_int(int(res["val_loss"] < best_val)))
+        previous_best = best_snapshot
         if improved:
             best_val, patience_count = res["val_loss"], 0
             best_path = os.path.join(models_dir, "alphazero_gomoku_best.pth")
@@ -783,8 +815,15 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
             best_snapshot.eval_mode()
         else:
             patience_count += 1
-        stats = _rng_isolated(evaluate_model, model, best_snapshot, games=eval_games, seed=seed + it,
-                              alternate=False) if rank == 0 else {}
+        if arena_search == "puct":
+            # against the best network before this iteration (the first one: against itself,
+            # which shows the first-move advantage only)
+            rival = previous_best if previous_best is not None else best_snapshot
+            stats = _rng_isolated(evaluate_model, model, rival, games=eval_games, seed=seed + it, search="puct",
+                                  puct={"temp_plies": temp_plies}) if rank == 0 and rival is not None else {}
+        else:
+            stats = _rng_isolated(evaluate_model, model, best_snapshot, games=eval_games, seed=seed + it,
+                                  alternate=False) if rank == 0 else {}
         res.update(eval=stats, elapsed=time.time() - t0)
         history.append(res)
         if rank == 0:

@@ -528,6 +528,64 @@ int gz_selfplay_puct_compact(void* d_slots, int32_t n_slots, int32_t n_active, i
                              int32_t leaves_per_round, int32_t move_trees, void* d_puct_workspace,
                              int32_t* d_order, int32_t* d_n_active, void* d_workspace, void* stream);
 
+/* The arena: two networks play each other (gz_selfplay_puct_run_active with the evaluator
+ * chosen per game).  The slots are gz_selfplay_init's, bounded with
+ * gz_selfplay_set_game_end so that each plays one game and goes idle.  Side A (index 0)
+ * and side B (index 1) each bring a weight blob and a precision; A plays black in game g
+ * iff ((g ^ a_black_parity) & 1) == 0.  The side that moves at a search's root evaluates
+ * every leaf of that search: each player searches with its own network.  Per ply, over
+ * the first n_active slots:
+ *   boards   gz_selfplay_boards;
+ *   plan     one workgroup: side[s] = the mover's side (-1: an idle slot, whose board is
+ *            marked over, so it takes no part in the search), row_of[s] = the slot's rank
+ *            among the slots of its side in ascending slot order, and the two counts;
+ *   rounds   the S+1 rounds of gz_puct_search, the evaluation of each being
+ *              gather    leaf row s (64 bytes) -> packed leaves of side[s], row row_of[s];
+ *              forward   gz_pv_forward(d_weights[i], packed i, n_active, &count[i], ...,
+ *                        precision[i]) for i = 0, 1: the counts stay on the device;
+ *              scatter   packed prior row (225 fp64) and value -> slot row s of the round
+ *                        buffers, on which select, backup and finish run as they are;
+ *   commit   the visit row is stashed and the move played as gz_selfplay_puct_run does:
+ *            records, visit rows and counters keep their meaning.
+ * Nothing synchronises the host.  search: the shared S, temp_plies, c_puct, seed and
+ * flags (0 or GZ_PUCT_ROOT_NOISE, then a gz_puct_noise_params); search->precision is not
+ * read.  A game's moves, visit rows and z depend only on (seed, game id, the two blobs
+ * and precisions, the search params, a_black_parity), not on n_slots, n_active, how
+ * plies are cut into calls, or compaction.  Workspace (gz_puct_match_workspace_bytes): it
+ * begins with the self-play workspace of n_slots slots (gz_selfplay_puct_workspace_bytes),
+ * so gz_selfplay_puct_layout and gz_selfplay_puct_compact(..., move_trees = 0, ...) work
+ * on it as they are; side and row_of (int32 [n_slots] each), the counts and the two
+ * packed buffer sets (leaves, logits, probs, value, prior and the forward's workspace,
+ * n_slots rows each) follow.  GZ_ERR_ARG before any launch: a NULL pointer, an unknown
+ * precision, a_black_parity outside {0, 1}, n_active outside [1, n_slots],
+ * GZ_PUCT_LEAF_BATCH in the flags.  Per-side simulation counts, leaf batching and tree
+ * reuse (a subtree holds the other side's evaluations) are not part of a match. */
+typedef struct gz_puct_match_params {
+    const gz_puct_params* search;
+    const float* d_weights[2];     /* side A, side B */
+    int32_t precision[2];          /* GZ_PV_FP32 / GZ_PV_F16X3 / GZ_PV_F16 per side */
+    int32_t a_black_parity;        /* 0 or 1 */
+    int32_t pad;
+} gz_puct_match_params;      /* 40 bytes */
+size_t gz_puct_match_workspace_bytes(int32_t n_slots, int32_t num_simulations);
+int gz_puct_match_run(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_match_params* mp,
+                      void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
+                      uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream);
+/* The score of a match from its records: adds to *d_tally (integer atomics; the caller
+ * zeroes it once per match and calls this after every step's records).  A game is
+ * counted once, at its ply-0 record (the mover is black, z black's result); plies counts
+ * records.  d_result (optional, int8 [n_games]): d_result[game_id - game_id_base] = +1 (A
+ * won), -1 (B won) or 0 (a draw); games not in d_records are left alone, ids outside
+ * [game_id_base, game_id_base + n_games) are tallied and not written. */
+typedef struct gz_puct_match_tally {
+    int64_t games, a_wins, b_wins, draws;
+    int64_t a_wins_black, a_wins_white, b_wins_black, b_wins_white;
+    int64_t plies;
+} gz_puct_match_tally;       /* 72 bytes */
+int gz_puct_match_results(const gz_record* d_records, int32_t n_records, int32_t a_black_parity,
+                          int64_t game_id_base, int32_t n_games, gz_puct_match_tally* d_tally, int8_t* d_result,
+                          void* stream);
+
 /* The noise sampler on its own (the device and host functions the search runs).
  * gz_puct_root_noise: d_eta [n][225] = eta at the empty cells of each board (ply =
  * n_moves) and 0 at stones; an all-zero row when the total is 0 or the board is full.
