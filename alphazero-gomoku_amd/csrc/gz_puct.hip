@@ -43,8 +43,20 @@
 // re-root for an inherited root (puct_reroot_kernel, puct_advance_kernel), on its
 // carried row with the key of its new ply.  No other node's row is touched.
 //
+// Playout cap randomization (opt-in, GZ_PUCT_PLAYOUT_CAP; tests/puct_cap_ref.py restates
+// it).  A root at ply n_moves is full when to_unit(draw(stream_key(seed, game, ply,
+// GZ_CAP_SIM), 0)) < full_prob and fast otherwise; its budget B is S when full, else F.
+// The budget and the full mark are decided when the node becomes a root -- begin_root for
+// a fresh one, after reroot() for an inherited one -- and kept in the PuctHdr, which
+// compaction moves byte for byte.  A search is finished when visits[0] >= B + 1 (without
+// the flag B = S everywhere: the tests of before).  An inherited root may arrive with
+// v >= B + 1 visits: it gets no simulation (an inactive row), its move is picked at the
+// next advance step (one round) and its visit row is the inherited child visits, v - 1.
+// Root noise is mixed into the rows of full roots only.  Not with leaf batching, not in
+// a match.
+//
 // Workspace (gz_puct_workspace_bytes(n, S), M = S+1 nodes per game):
-//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S, noise flag, alpha, eps), written
+//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S, flags, alpha, eps, F, p), written
 //                       by gz_puct_begin
 //   n x game_stride     per game, game_stride = al256(128 + 2334 M):
 //        PuctHdr  128 B   root position, game id, node count, pending node, ...
@@ -181,10 +193,13 @@ struct PuctCfg {
     uint64_t seed;
     int32_t temp_plies;
     int32_t S;
-    int32_t flags;  // GZ_PUCT_ROOT_NOISE
+    int32_t flags;  // GZ_PUCT_ROOT_NOISE | GZ_PUCT_PLAYOUT_CAP
     int32_t leaves;  // K of a batched search (GZ_PUCT_LEAF_BATCH), 0: one leaf per round
     double noise_alpha;
     double noise_eps;
+    int32_t fast;      // F of GZ_PUCT_PLAYOUT_CAP
+    int32_t pad;
+    double full_prob;  // p
 };
 static_assert(sizeof(PuctCfg) <= 256, "the configuration block");
 
@@ -211,6 +226,36 @@ __device__ inline PuctNoise noise_of(const PuctNoise& nz, const char* ws) {
     return r;
 }
 
+// The playout cap of a launch, by value.  on: 0 none (every root is full, budget S), 1 cap
+// with (fast, full_prob), -1 as gz_puct_begin stored it in the workspace's PuctCfg.
+struct PuctCap {
+    double full_prob;
+    int32_t fast;
+    int32_t on;
+};
+
+__device__ inline PuctCap cap_of(const PuctCap& cp, const char* ws) {
+    if (cp.on >= 0) return cp;
+    const PuctCfg* cfg = (const PuctCfg*)ws;
+    PuctCap r;
+    r.full_prob = cfg->full_prob;
+    r.fast = cfg->fast;
+    r.on = (cfg->flags & GZ_PUCT_PLAYOUT_CAP) ? 1 : 0;
+    return r;
+}
+
+// the (seed, game, ply, GZ_CAP_SIM) stream decides a ply: full or fast (host and device)
+constexpr int32_t GZ_CAP_SIM = 0x50434150;  // "PCAP"; simulation streams use sim <= 4095
+
+__host__ __device__ inline bool cap_is_full(uint64_t seed, int64_t game_id, int32_t ply, double full_prob) {
+    return to_unit(draw(stream_key(seed, game_id, ply, GZ_CAP_SIM), 0)) < full_prob;
+}
+
+// is the root of (game, ply) a full search?  Without the cap every root is.
+__device__ inline bool root_is_full(const PuctCap& cap, uint64_t seed, int64_t game_id, int32_t ply) {
+    return !cap.on || cap_is_full(seed, game_id, ply, cap.full_prob);
+}
+
 struct PuctHdr {  // 128 bytes
     uint32_t black[8];
     uint32_t white[8];
@@ -226,7 +271,9 @@ struct PuctHdr {  // 128 bytes
     int32_t new_evals;   // evaluations since the last move (gz_selfplay_puct_rounds' slot statistics)
     int32_t reuse;       // REUSE_MAGIC: a tree of gz_selfplay_puct_rounds (0: gz_puct_begin, a reset)
     int32_t rounds;      // rounds of gz_selfplay_puct_rounds since the last move
-    int32_t pad[3];
+    int32_t budget;      // B: the search is finished at B + 1 root visits (S, or F on a fast ply)
+    int32_t full;        // a full ply (always without GZ_PUCT_PLAYOUT_CAP): its root row takes the noise
+    int32_t pad[1];
 };
 constexpr int32_t REUSE_MAGIC = 0x52455553;
 static_assert(sizeof(PuctHdr) == 128, "puct header");
@@ -363,7 +410,7 @@ __device__ inline void new_node(const PuctTree& t, int j, int parent, int move, 
 
 // a one-node tree: the root waits for its evaluation (pending 0) unless the game is over
 __device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& white, int64_t game_id, int n_moves,
-                                  int player, bool over, int32_t reuse) {
+                                  int player, bool over, int32_t reuse, int budget, bool full) {
     new_node(t, 0, -1, 255, 0, black, white);
     if (lane_id() == 0) {
         PuctHdr* h = t.h;
@@ -380,13 +427,27 @@ __device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& 
         h->move = -1;
         h->new_evals = 0;
         h->reuse = reuse;
+        h->budget = budget;
+        h->full = full ? 1 : 0;
     }
+}
+
+// the budget of an inherited root, right after reroot() (every lane of one wave calls;
+// the header already holds the new ply); returns whether the ply is full
+__device__ inline bool set_budget(PuctHdr* h, const PuctCap& cap, uint64_t seed, int S) {
+    const bool full = root_is_full(cap, seed, h->game_id, h->n_moves);
+    if (lane_id() == 0) {
+        h->budget = full ? S : cap.fast;
+        h->full = full ? 1 : 0;
+    }
+    return full;
 }
 
 // ---------------------------------------------------------------- begin
 __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* boards, const int64_t* game_ids, int n,
-                                                          gz_puct_params p, PuctNoise nz, int K, int16_t* pend,
-                                                          char* ws, uint32_t* leaves, int32_t* active) {
+                                                          gz_puct_params p, PuctNoise nz, PuctCap cap, int K,
+                                                          int16_t* pend, char* ws, uint32_t* leaves,
+                                                          int32_t* active) {
     const int g = blockIdx.x;
     if (g >= n) return;
     const int lane = lane_id();
@@ -398,10 +459,13 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
         cfg->seed = p.seed;
         cfg->temp_plies = p.temp_plies;
         cfg->S = S;
-        cfg->flags = nz.on ? GZ_PUCT_ROOT_NOISE : 0;
+        cfg->flags = (nz.on ? GZ_PUCT_ROOT_NOISE : 0) | (cap.on ? GZ_PUCT_PLAYOUT_CAP : 0);
         cfg->leaves = K;
         cfg->noise_alpha = nz.alpha;
         cfg->noise_eps = nz.eps;
+        cfg->fast = cap.fast;
+        cfg->pad = 0;
+        cfg->full_prob = cap.full_prob;
     }
     PuctTree t = tree_of(ws, g, S);
     const gz_board_state& bs = boards[g];
@@ -409,7 +473,8 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
     load_bb(black, bs.black);
     load_bb(white, bs.white);
     const bool over = bs.over != 0 || !bb_any(empties(black, white));
-    begin_root(t, black, white, game_ids[g], bs.n_moves, bs.player, over, 0);
+    const bool full = root_is_full(cap, p.seed, game_ids[g], bs.n_moves);
+    begin_root(t, black, white, game_ids[g], bs.n_moves, bs.player, over, 0, full ? S : cap.fast, full);
     write_leaf(leaves, active, g * rows, black, white, !over);
     for (int k = 1; k < rows; k++) write_leaf(leaves, active, g * rows + k, black, white, false);
     if (pend)
@@ -419,8 +484,8 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
 // ---------------------------------------------------------------- select
 // One simulation's descent of game g's tree: the new leaf's board into row g, or an
 // empty row (a terminal node backed up, a game that is over, waits for a backup or
-// whose root already has its S+1 visits -- the last only with tree reuse, where a
-// game can reach its budget before the others).
+// whose root already has its budget's B+1 visits -- with tree reuse, where a game can
+// reach its budget before the others, and on the fast plies of a playout cap).
 __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, uint32_t* leaves, int32_t* active) {
     const int lane = lane_id();
     PuctHdr* h = t.h;
@@ -428,7 +493,7 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
     load_bb(black, h->black);
     load_bb(white, h->white);
     // (pending: the caller skipped a backup; keep the tree as it is)
-    if (h->over || h->pending >= 0 || t.visits[0] > S) {
+    if (h->over || h->pending >= 0 || t.visits[0] > h->budget) {
         write_leaf(leaves, active, g, black, white, false);
         return;
     }
@@ -529,7 +594,7 @@ __global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int 
     const int j = t.h->pending;
     if (j < 0) return;
     for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[(size_t)g * GZ_CELLS + c];
-    if (j == 0) {
+    if (j == 0 && t.h->full) {  // (a fast ply's root keeps the evaluator's row)
         const PuctNoise z = noise_of(nz, ws);
         if (z.on) mix_root_row(t, z);  // (each lane mixes the cells it has just stored)
     }
@@ -686,7 +751,7 @@ __global__ __launch_bounds__(WAVE) void puct_backup_batch_kernel(char* ws, int n
     if (j0 >= 0) {
         const size_t row = (size_t)g * K;
         for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j0 * GZ_CELLS + c] = prior[row * GZ_CELLS + c];
-        if (j0 == 0) {
+        if (j0 == 0 && h->full) {
             const PuctNoise z = noise_of(nz, ws);
             if (z.on) mix_root_row(t, z);  // (each lane mixes the cells it has just stored)
         }
@@ -724,7 +789,7 @@ __global__ void puct_remaining_kernel(char* ws, int n, int S, int32_t* remaining
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
     const PuctTree t = tree_of(ws, g, S);
-    int r = t.h->over ? 0 : S + 1 - t.visits[0];
+    int r = t.h->over ? 0 : t.h->budget + 1 - t.visits[0];
     if (r < 0) r = 0;
     if (remaining) remaining[g] = r;
     if (largest && r > 0) atomicMax(largest, r);
@@ -975,13 +1040,21 @@ __global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n
     __syncthreads();  // (every thread has read the header before any of it changes)
     if (c > 0) reroot(t, c, S, remap, remap + S + 1);
     if (threadIdx.x >= WAVE) return;
-    // an inherited live root: its carried row is mixed once, with the key of its new ply
-    // (a root that still waits for its evaluation is mixed at that backup)
-    if (c > 0 && !h->over && h->pending != 0) {
-        PuctNoise stored = {};
-        stored.on = -1;  // as gz_puct_begin stored it
-        const PuctNoise nz = noise_of(stored, ws);
-        if (nz.on) mix_root_row(t, nz);
+    PuctCap cap = {};
+    cap.on = -1;  // as gz_puct_begin stored it
+    cap = cap_of(cap, ws);
+    const uint64_t seed = ((const PuctCfg*)ws)->seed;
+    // an inherited root: the budget of its new ply; when live and full, its carried row is
+    // mixed once, with the key of that ply (a root that still waits for its evaluation is
+    // mixed at that backup)
+    if (c > 0) {
+        const bool full = set_budget(h, cap, seed, S);
+        if (full && !h->over && h->pending != 0) {
+            PuctNoise stored = {};
+            stored.on = -1;
+            const PuctNoise nz = noise_of(stored, ws);
+            if (nz.on) mix_root_row(t, nz);
+        }
     }
     bool live = false;
     if (play && c <= 0) {
@@ -993,12 +1066,16 @@ __global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n
         else bb_set(white, bit);
         const int64_t gid = h->game_id;
         const int32_t reuse = h->reuse;
-        begin_root(t, black, white, gid, cnt, 3 - mover, over, reuse);
+        const bool full = root_is_full(cap, seed, gid, cnt);
+        begin_root(t, black, white, gid, cnt, 3 - mover, over, reuse, full ? S : cap.fast, full);
         live = !over;
         __threadfence_block();
     }
     write_leaf(leaves, active, g, black, white, live);
-    if (remaining && threadIdx.x == 0) remaining[g] = h->over ? 0 : S + 1 - t.visits[0];
+    if (remaining && threadIdx.x == 0) {
+        const int r = h->over ? 0 : h->budget + 1 - t.visits[0];  // (thread 0 wrote the budget itself)
+        remaining[g] = r < 0 ? 0 : r;
+    }
 }
 
 // a tree of gz_selfplay_puct_rounds whose root is the slot's game and position
@@ -1013,13 +1090,14 @@ __device__ inline const SlotHeader* slot_of(const char* slots, int s) {
     return (const SlotHeader*)(slots + (size_t)s * slot_stride_bytes());
 }
 
-// Round step 1: a slot whose search is at its budget picks its move (wave 0), stashes
-// the visit row of the ply and hands move and statistics to selfplay_commit_kernel
+// Round step 1: a slot whose search is at its budget (B + 1 root visits or more) picks
+// its move (wave 0), stashes the visit row of the ply and hands move and statistics to
+// selfplay_commit_kernel
 // (move -1 leaves the slot alone); then the workgroup re-roots the tree under the move,
 // unless the move ends the game -- the tree of a move that ends it no longer matches
 // its slot after the commit, and puct_round_kernel begins a fresh one.
 __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* slots, int n, gz_puct_params p,
-                                                                  PuctNoise nz, char* ws, int32_t* moves,
+                                                                  PuctNoise nz, PuctCap cap, char* ws, int32_t* moves,
                                                                   gz_search_stats* stats, uint16_t* pend) {
     extern __shared__ __attribute__((aligned(16))) int16_t remap[];
     __shared__ int next_root;
@@ -1032,7 +1110,7 @@ __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* sl
         const int lane = lane_id();
         const SlotHeader* sh = slot_of(slots, s);
         const bool due = sh->game_id < sh->game_id_end && tree_matches(h, sh) && !h->over && h->pending < 0 &&
-                         t.visits[0] == S + 1 && h->n_moves >= 0 && h->n_moves < GZ_MAX_GAME_PLIES;
+                         t.visits[0] >= h->budget + 1 && h->n_moves >= 0 && h->n_moves < GZ_MAX_GAME_PLIES;
         int mv = -1, c = -1;
         if (due) {
             PuctCfg cfg;
@@ -1071,16 +1149,20 @@ __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* sl
     __syncthreads();
     if (next_root > 0) {
         reroot(t, next_root, S, remap, remap + S + 1);
-        // the inherited root (live, evaluated): its carried row, mixed with its new ply's key
-        if (nz.on && threadIdx.x < WAVE) mix_root_row(t, nz);
+        // the inherited root (live, evaluated): its new ply's budget and, on a full ply, its
+        // carried row mixed with that ply's key
+        if (threadIdx.x < WAVE) {
+            const bool full = set_budget(h, cap, p.seed, S);
+            if (nz.on && full) mix_root_row(t, nz);
+        }
     }
 }
 
 // Round step 3: a tree that is not the slot's (a new game, a reset, a move that ended
 // the game) gives way to a fresh root, whose board is its leaf of this round; every
 // other slot descends once.
-__global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int n, gz_puct_params p, char* ws,
-                                                          uint32_t* leaves, int32_t* active) {
+__global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int n, gz_puct_params p, PuctCap cap,
+                                                          char* ws, uint32_t* leaves, int32_t* active) {
     const int s = blockIdx.x;
     if (s >= n) return;
     const int S = p.num_simulations;
@@ -1098,7 +1180,9 @@ __global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int
     if (tree_matches(h, sh)) {
         descend(t, p.c_puct, S, s, leaves, active);
     } else {
-        begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC);
+        const bool full = root_is_full(cap, p.seed, sh->game_id, sh->n_moves);
+        begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC, full ? S : cap.fast,
+                   full);
         write_leaf(leaves, active, s, black, white, true);
     }
     if (lane_id() == 0) h->rounds = rounds + 1;
@@ -1164,6 +1248,14 @@ __global__ __launch_bounds__(WAVE) void puct_root_noise_kernel(const gz_board_st
 #pragma unroll
     for (int k = 0; k < 4; k++)
         if (lane + WAVE * k < GZ_CELLS) out[(size_t)g * GZ_CELLS + lane + WAVE * k] = eta[k];
+}
+
+// gz_puct_cap_full: one thread per record, the decision of its (game id, ply)
+__global__ __launch_bounds__(256) void puct_cap_full_kernel(const gz_record* records, int n, uint64_t seed,
+                                                            double full_prob, uint8_t* out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = cap_is_full(seed, records[i].game_id, records[i].ply, full_prob) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------- slot compaction
@@ -1465,6 +1557,32 @@ int read_leaves(const char* who, const gz_puct_params* p, int& K) {
     return GZ_OK;
 }
 
+int check_full_prob(const char* who, double full_prob) {
+    if (!(full_prob >= 0.0 && full_prob <= 1.0))  // (a NaN fails both)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": full_prob must be finite and in [0, 1]");
+    return GZ_OK;
+}
+
+// The playout cap p asks for.  Only with GZ_PUCT_PLAYOUT_CAP set is p a gz_puct_cap_params;
+// without it nothing past the batch struct is read.  (After check_S: F is held against S.)
+int read_cap(const char* who, const gz_puct_params* p, PuctCap& cap) {
+    cap.full_prob = 1.0;
+    cap.fast = p->num_simulations;
+    cap.on = 0;
+    if (!(p->flags & GZ_PUCT_PLAYOUT_CAP)) return GZ_OK;
+    if (p->flags & GZ_PUCT_LEAF_BATCH)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the playout cap with leaf batching is not supported");
+    const gz_puct_cap_params* q = (const gz_puct_cap_params*)p;
+    if (q->fast_simulations < 1 || q->fast_simulations > p->num_simulations)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": fast_simulations out of range [1, num_simulations]");
+    int rc = check_full_prob(who, q->full_prob);
+    if (rc) return rc;
+    cap.full_prob = q->full_prob;
+    cap.fast = q->fast_simulations;
+    cap.on = 1;
+    return GZ_OK;
+}
+
 // the n K rows of a round are indexed with int32
 int check_rows(const char* who, int32_t n, int32_t K) {
     if (K > 0 && (int64_t)n * K > INT32_MAX) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n x leaves_per_round too large");
@@ -1598,12 +1716,15 @@ int begin_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_
     if (rc) return rc;
     rc = check_rows("gz_puct_begin", n_cap, K);
     if (rc) return rc;
+    PuctCap cap;
+    rc = read_cap("gz_puct_begin", p, cap);
+    if (rc) return rc;
     if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
         return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
     if (n == 0) return GZ_OK;
     note_leaves(d_workspace, K);
     int16_t* pend = K > 0 ? (int16_t*)((char*)d_workspace + rounds_offset(n_cap, p->num_simulations)) : nullptr;
-    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, K, pend,
+    puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, cap, K, pend,
                                                          (char*)d_workspace, d_leaves, d_active);
     return gz_check_launch("puct_begin_kernel");
 }
@@ -1698,6 +1819,9 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     int K;
     rc = read_leaves(who, p, K);
     if (rc) return rc;
+    PuctCap cap;
+    rc = read_cap(who, p, cap);
+    if (rc) return rc;
     return check_rows(who, n, K);
 }
 
@@ -1785,15 +1909,18 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
     PuctNoise nz;
     rc = read_noise(who, p, nz);
     if (rc) return rc;
+    PuctCap cap;
+    rc = read_cap(who, p, cap);
+    if (rc) return rc;
     for (int it = 0; it < n_rounds; it++) {
-        puct_advance_kernel<<<n, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n, *p, nz, (char*)w.puct,
-                                                                   w.moves, w.stats, w.pend);
+        puct_advance_kernel<<<n, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n, *p, nz, cap,
+                                                                   (char*)w.puct, w.moves, w.stats, w.pend);
         rc = gz_check_launch("puct_advance_kernel");
         if (rc) return rc;
         rc = gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
                                          d_visits, stream);
         if (rc) return rc;
-        puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, (char*)w.puct, r.leaves, r.active);
+        puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, cap, (char*)w.puct, r.leaves, r.active);
         rc = gz_check_launch("puct_round_kernel");
         if (rc) return rc;
         rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
@@ -1845,6 +1972,8 @@ int match_impl(void* d_slots, int32_t n_slots, int32_t n, const gz_puct_match_pa
     if (rc) return rc;
     if (p->flags & GZ_PUCT_LEAF_BATCH)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": leaf batching is not supported in a match");
+    if (p->flags & GZ_PUCT_PLAYOUT_CAP)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the playout cap is not supported in a match");
     PuctNoise nz;
     rc = read_noise(who, p, nz);
     if (rc) return rc;
@@ -2145,6 +2274,20 @@ int gz_puct_root_noise(const gz_board_state* d_boards, const int64_t* d_game_ids
     if (n == 0) return GZ_OK;
     puct_root_noise_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, seed, alpha, d_eta);
     return gz_check_launch("puct_root_noise_kernel");
+}
+
+int gz_puct_cap_full(const gz_record* d_records, int32_t n, uint64_t seed, double full_prob, uint8_t* d_full,
+                     void* stream) {
+    int rc = check_full_prob("gz_puct_cap_full", full_prob);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!d_records || !d_full))) return gz_fail(GZ_ERR_ARG, "gz_puct_cap_full: bad arguments");
+    if (n == 0) return GZ_OK;
+    puct_cap_full_kernel<<<(n + 255) / 256, 256, 0, as_stream(stream)>>>(d_records, n, seed, full_prob, d_full);
+    return gz_check_launch("puct_cap_full_kernel");
+}
+
+int gz_puct_cap_full_host(uint64_t seed, int64_t game_id, int32_t ply, double full_prob) {
+    return cap_is_full(seed, game_id, ply, full_prob) ? 1 : 0;
 }
 
 int gz_puct_root_noise_host(uint64_t seed, int64_t game_id, int32_t ply, const uint8_t* empty225, double alpha,

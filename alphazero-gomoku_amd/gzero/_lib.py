@@ -22,6 +22,7 @@ GZ_PV_F16 = 2  # one-term fp16 tower (include/gzero.h); opt-in
 GZ_AUG_FIX_LABELS = 1
 GZ_PUCT_ROOT_NOISE = 1  # gz_puct_params.flags: the params are a gz_puct_noise_params
 GZ_PUCT_LEAF_BATCH = 2  # gz_puct_params.flags: the params are a gz_puct_batch_params
+GZ_PUCT_PLAYOUT_CAP = 4  # gz_puct_params.flags: the params are a gz_puct_cap_params
 GZ_PUCT_MAX_LEAVES = 32
 
 
@@ -74,6 +75,10 @@ class PuctBatchParams(PuctNoiseParams):  # gz_puct_batch_params: the noise struc
     _fields_ = [("leaves_per_round", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class PuctCapParams(PuctBatchParams):  # gz_puct_cap_params: the batch struct, then F and p (72 bytes)
+    _fields_ = [("fast_simulations", ctypes.c_int32), ("cap_pad", ctypes.c_int32), ("full_prob", ctypes.c_double)]
+
+
 class Record(ctypes.Structure):  # gz_record, 80 bytes
     _fields_ = [("black", ctypes.c_uint32 * 8), ("white", ctypes.c_uint32 * 8),
                 ("game_id", ctypes.c_int64), ("ply", ctypes.c_int16), ("move", ctypes.c_int16),
@@ -104,7 +109,7 @@ class PuctMatchTally(ctypes.Structure):  # gz_puct_match_tally, 72 bytes
 assert ctypes.sizeof(BoardState) == 80 and ctypes.sizeof(Record) == 80
 assert ctypes.sizeof(PuctMatchParams) == 40 and ctypes.sizeof(PuctMatchTally) == 72
 assert ctypes.sizeof(PuctParams) == 32 and ctypes.sizeof(PuctNoiseParams) == 48
-assert ctypes.sizeof(PuctBatchParams) == 56
+assert ctypes.sizeof(PuctBatchParams) == 56 and ctypes.sizeof(PuctCapParams) == 72
 assert ctypes.sizeof(SearchStats) == 24 and ctypes.sizeof(SelfplayCounters) == 40
 
 class SgdNet(ctypes.Structure):  # gz_sgd_net
@@ -216,6 +221,8 @@ SIGNATURES = {
                                          _P]),
     "gz_puct_match_results": (ctypes.c_int, [_P, _I32, _I32, _I64, _I32, _P, _P, _P]),
     "gz_puct_root_noise": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
+    "gz_puct_cap_full": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
+    "gz_puct_cap_full_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, ctypes.c_double]),
     "gz_puct_root_noise_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, ctypes.c_double, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),

@@ -328,7 +328,7 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 
 # ---------------------------------------------------------------- PUCT search
 def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
-                noise_eps=0.25, leaves_per_round=1):
+                noise_eps=0.25, leaves_per_round=1, fast_simulations=None, full_prob=0.25):
     """gz_puct_params; precision ("fp32" / "f16x3" / "f16") is the forward gz_puct_search runs.
     dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
     noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
@@ -336,7 +336,15 @@ def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision
     default): no noise, the plain 32-byte struct.
     leaves_per_round K > 1: leaf batching with virtual loss, K leaves per game per round
     (a gz_puct_batch_params with GZ_PUCT_LEAF_BATCH set); 1 (the default) is the
-    unbatched search with the flag clear."""
+    unbatched search with the flag clear.
+    fast_simulations F: playout cap randomization (a gz_puct_cap_params with
+    GZ_PUCT_PLAYOUT_CAP set): every ply is a full search of num_simulations with
+    probability full_prob, else a fast one of F simulations without root noise
+    (include/gzero.h).  None (the default): no cap, full_prob is not read.  Not with
+    leaves_per_round > 1."""
+    if fast_simulations is not None:
+        return _with_cap(puct_params(num_simulations, c_puct, temp_plies, seed, precision, dirichlet_alpha, noise_eps,
+                                     leaves_per_round), fast_simulations, full_prob)
     if precision not in PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}")
     mode = PRECISIONS[precision]
@@ -357,6 +365,36 @@ def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision
     return _lib.PuctNoiseParams(*base, _lib.GZ_PUCT_ROOT_NOISE, alpha, eps)
 
 
+def _with_cap(params, fast_simulations, full_prob):
+    """The gz_puct_cap_params of uncapped, unbatched params."""
+    F, prob = int(fast_simulations), float(full_prob)
+    if params.flags & _lib.GZ_PUCT_LEAF_BATCH:
+        raise ValueError("fast_simulations (the playout cap) is not supported with leaves_per_round > 1")
+    if not 1 <= F <= params.num_simulations:
+        raise ValueError(f"fast_simulations must be in [1, num_simulations], not {fast_simulations!r}")
+    if not 0.0 <= prob <= 1.0:  # (a NaN fails both)
+        raise ValueError(f"full_prob must be in [0, 1], not {full_prob!r}")
+    noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
+    alpha, eps = (params.noise_alpha, params.noise_eps) if noise else (0.0, 0.0)
+    return _lib.PuctCapParams(params.num_simulations, params.temp_plies, params.c_puct, params.seed, params.precision,
+                              noise | _lib.GZ_PUCT_PLAYOUT_CAP, alpha, eps, 1, 0, F, 0, prob)
+
+
+def cap_full(records_dev, seed, full_prob):
+    """Which records are full plies of a capped run with this seed and full_prob
+    (gz_puct_cap_full): records_dev a device uint8 tensor of gz_record (80 bytes each),
+    as SelfPlayEngine.records_device gives it; returns a device bool tensor [n]."""
+    lib = require_gpu()
+    prob = float(full_prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"full_prob must be in [0, 1], not {full_prob!r}")
+    n = records_dev.numel() // 80
+    d_full = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.gz_puct_cap_full(ptr(records_dev), n, int(seed) & ((1 << 64) - 1), prob, ptr(d_full), stream()),
+               "gz_puct_cap_full")
+    return d_full != 0
+
+
 def puct_leaves(params):
     """K of a batched params struct (GZ_PUCT_LEAF_BATCH), 0 for the unbatched search."""
     return int(params.leaves_per_round) if params.flags & _lib.GZ_PUCT_LEAF_BATCH else 0
@@ -372,6 +410,8 @@ def with_leaves(params, leaves_per_round):
         raise ValueError(f"leaves_per_round must be in [1, {_lib.GZ_PUCT_MAX_LEAVES}], not {leaves_per_round!r}")
     if K == 1 and not params.flags & _lib.GZ_PUCT_LEAF_BATCH:
         return params
+    if params.flags & _lib.GZ_PUCT_PLAYOUT_CAP:
+        raise ValueError("leaves_per_round > 1 is not supported with fast_simulations (the playout cap)")
     noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
     flags = noise | (_lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0)
     base = (params.num_simulations, params.temp_plies, params.c_puct, params.seed, params.precision)
@@ -478,6 +518,10 @@ class PuctStepper:
 
     prior float64 [n,225] and value float32 [n] in gz_pv_forward's layouts (device
     tensors or arrays); rows of inactive games are ignored.
+
+    With a playout cap (puct_params(fast_simulations=...)) a search has no fixed number of
+    rounds either: ``remaining()`` (and ``reroot()``'s result) count against each game's own
+    budget, and a game at or past it has an inactive row.
 
     With leaves_per_round K > 1 (here or in params) every buffer has n K rows, game g at
     rows g K .. g K + K - 1, and a search is no fixed number of rounds: after the root's

@@ -29,7 +29,7 @@ class SelfPlayEngine:
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
                  rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1,
-                 compact_slots=False):
+                 compact_slots=False, fast_simulations=None, full_prob=0.25):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -57,6 +57,15 @@ class SelfPlayEngine:
         num_simulations + 1 (GZ_PUCT_LEAF_BATCH, include/gzero.h) -- for small n_slots,
         where a forward of a few boards leaves the chip idle.  The search then
         synchronises with the host once per block of rounds.  Not with tree_reuse.
+        fast_simulations F (search="puct" only; default None = no cap): playout cap
+        randomization (GZ_PUCT_PLAYOUT_CAP, include/gzero.h): every ply is a full search
+        of num_simulations with probability full_prob, else a fast one of F simulations
+        without root noise, decided from (seed, game id, ply).  Every ply is recorded;
+        gzero.device.cap_full tells which records were full plies, the ones to train on.
+        With tree_reuse a move then takes B + 1 - v rounds (at least one), B its ply's
+        budget; the lock-step engine accepts the cap and gains nothing (every ply costs
+        num_simulations + 1 rounds).  rounds_per_step keeps its default.  Not with
+        leaves_per_round > 1.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -87,6 +96,11 @@ class SelfPlayEngine:
             raise ValueError("leaves_per_round needs search='puct'")
         if self.leaves_per_round > 1 and self.tree_reuse:
             raise ValueError("leaves_per_round > 1 is not supported with tree_reuse")
+        if fast_simulations is not None:
+            if search != "puct":
+                raise ValueError("fast_simulations needs search='puct'")
+            if self.leaves_per_round > 1:
+                raise ValueError("fast_simulations (the playout cap) is not supported with leaves_per_round > 1")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -135,7 +149,7 @@ class SelfPlayEngine:
         self.puct = self.d_puct_ws = self.d_visits = None
         if search == "puct":
             self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision, dirichlet_alpha,
-                                    noise_eps, self.leaves_per_round)
+                                    noise_eps, self.leaves_per_round, fast_simulations, full_prob)
             K = puct_leaves(self.puct)
             nbytes = self.lib.gz_selfplay_puct_batch_workspace_bytes(self.n_slots, S, K) if K else \
                 self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S)
@@ -282,11 +296,11 @@ class SelfPlayEngine:
         lock-step plies too, and the trees are reset afterwards (the next round begins
         every slot with a fresh root)."""
         if self.search == "puct":
-            # (the 32 bytes of the base struct: the burn-in has no root noise and one leaf
-            # per round, so the flags that would make the library read past the copy are
+            # (the 32 bytes of the base struct: the burn-in has no root noise, no playout cap and
+            # one leaf per round, so the flags that would make the library read past the copy are
             # cleared)
             p = _lib.PuctParams.from_buffer_copy(self.puct)
-            p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH)
+            p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH | _lib.GZ_PUCT_PLAYOUT_CAP)
             p.num_simulations = min(8, p.num_simulations)
             for _ in range(int(n_plies) if self.n_active > 0 else 0):
                 self.d_counters.zero_()

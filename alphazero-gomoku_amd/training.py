@@ -250,7 +250,7 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                          noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True,
-                         pv_weights=None):
+                         pv_weights=None, fast_simulations: Optional[int] = None, full_prob: float = 0.25):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -274,6 +274,11 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     counts the unwanted refill games' moves.  compact=False: continuous refill.
     pv_weights: the PVWeights the leaves are evaluated with (None: model.device_weights());
     its precision is the search's -- "f16" runs GZ_PV_F16, a third of the tower's MFMAs.
+    fast_simulations / full_prob: playout cap randomization (SelfPlayEngine(fast_simulations=...)):
+    every ply is a full search with probability full_prob, else one of fast_simulations
+    without noise.  The rows and visit rows of all plies are returned as ever;
+    stats["full_records"] counts the full plies among them (gz_puct_cap_full; without the
+    cap, all of them), the ones run_iteration trains on.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -285,7 +290,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          game_id_base=game_id_base, search="puct", temp_plies=temp_plies, tree_reuse=tree_reuse,
                          rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
                          dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round,
-                         game_id_end=game_id_base + n_games if compact else None, compact_slots=bool(compact))
+                         game_id_end=game_id_base + n_games if compact else None, compact_slots=bool(compact),
+                         fast_simulations=fast_simulations, full_prob=full_prob)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -337,8 +343,14 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     if n > cap:
         raise RuntimeError(f"selfplay_puct_device: {n} records for {n_games} games")
     order = torch.argsort(key[:n])
-    return (rows[:n][order].view(torch.uint8).view(n, 80), vis[:n][order], n,
-            {"games": games, "moves_played": moves, "steps": steps, "seconds": time.time() - t0})
+    recs = rows[:n][order].view(torch.uint8).view(n, 80)
+    full = n
+    if fast_simulations is not None and n > 0:
+        from gzero.device import cap_full
+        full = int(cap_full(recs, seed, full_prob).sum().item())
+    return (recs, vis[:n][order], n,
+            {"games": games, "moves_played": moves, "steps": steps, "seconds": time.time() - t0,
+             "full_records": full})
 
 
 def selfplay_device(n_games: int, id_lo: int, id_hi: int, num_simulations: int = 200, difficulty: str = "medium",
@@ -628,7 +640,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   planner=None, verbose: bool = True, search: str = "reference", temp_plies: int = 8,
                   tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                   noise_eps: float = 0.25, leaves_per_round: int = 1,
-                  selfplay_precision: Optional[str] = None) -> dict:
+                  selfplay_precision: Optional[str] = None, fast_simulations: Optional[int] = None,
+                  full_prob: float = 0.25) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -646,7 +659,12 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     ``selfplay_precision`` (search="puct"; "fp32" / "f16x3" / "f16"): self-play evaluates
     its leaves on a second pack of the current parameters at that precision
     (model.device_weights(precision=...)); predict, validation and the arena keep the
-    model's own."""
+    model's own.
+    ``fast_simulations`` / ``full_prob`` (search="puct"): playout cap randomization in
+    self-play (selfplay_puct_device).  Only the full plies are trained on: their records
+    and visit rows are selected on the device (gz_puct_cap_full's mask) before the dataset
+    is built, so policy and value targets both come from full searches.  ``records`` is
+    then the count kept and ``records_played`` the count of all plies."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     from gzero.weights import PRECISIONS
@@ -661,6 +679,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError("dirichlet_alpha needs search='puct'")
     if int(leaves_per_round) != 1 and search != "puct":
         raise ValueError("leaves_per_round needs search='puct'")
+    if fast_simulations is not None and search != "puct":
+        raise ValueError("fast_simulations needs search='puct'")
     if selfplay_precision is not None:
         if search != "puct":
             raise ValueError("selfplay_precision needs search='puct'")
@@ -676,7 +696,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                                                    model=model, temp_plies=temp_plies, tree_reuse=tree_reuse,
                                                    dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
                                                    leaves_per_round=leaves_per_round,
-                                                   pv_weights=model.device_weights(selfplay_precision))
+                                                   pv_weights=model.device_weights(selfplay_precision),
+                                                   fast_simulations=fast_simulations, full_prob=full_prob)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -689,8 +710,18 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     if ws > 1:
         import torch.distributed as tdist
         tdist.all_reduce(moves)
+    n_played = n_rec
+    if fast_simulations is not None and n_rec > 0:
+        # train on the full plies only: records and visit rows, by one mask
+        from gzero.device import cap_full
+        keep = torch.nonzero(cap_full(d, seed, full_prob)).reshape(-1)
+        d = d.view(n_rec, 80).index_select(0, keep).reshape(-1)
+        d_vis = d_vis.index_select(0, keep)
+        n_rec = int(keep.numel())
     t1 = time.time()
     out = {"iteration": it, "records": n_rec, "selfplay_s": t1 - t0, "moves_played": int(moves.item())}
+    if fast_simulations is not None:
+        out["records_played"] = n_played
     if n_rec == 0:
         return dict(out, skipped=True)
     ds = DeviceDataset(d, use_augmentation=True, augment_ratio=augment_ratio, n_records=n_rec, visits=d_vis)
@@ -751,7 +782,8 @@ def _broadcast_int(x: int) -> int:
 def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int] = None, models_dir: str = "models",
          num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
          temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
-         leaves_per_round: int = 1, selfplay_precision: Optional[str] = None, arena_search: str = "reference"):
+         leaves_per_round: int = 1, selfplay_precision: Optional[str] = None, arena_search: str = "reference",
+         tree_reuse: bool = False, fast_simulations: Optional[int] = None, full_prob: float = 0.25):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -762,7 +794,9 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     Dirichlet noise at its search roots, ``leaves_per_round`` K > 1 evaluates K leaves per
     game per round (worth it at the default 10 games per iteration),
     ``selfplay_precision="f16"`` runs self-play's leaf evaluations in GZ_PV_F16 while the
-    model itself stays f16x3.
+    model itself stays f16x3.  ``fast_simulations`` / ``full_prob``: playout cap
+    randomization in self-play, training on the full plies only (run_iteration); it pays
+    with ``tree_reuse=True``, the own-clock engine, where a fast ply costs fewer rounds.
     ``arena_search="puct"``: rank 0's per-iteration arena is a device-side match of the
     network-guided search between the model and the best snapshot
     (evaluate_model(search="puct"), colours alternating), so the win rate printed depends
@@ -774,6 +808,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     from neural_network import GomokuModel
     if selfplay_precision is not None and search != "puct":
         raise ValueError("selfplay_precision needs search='puct'")
+    if (tree_reuse or fast_simulations is not None) and search != "puct":
+        raise ValueError("tree_reuse and fast_simulations need search='puct'")
     if arena_search not in ("reference", "puct"):
         raise ValueError(f"arena_search must be 'reference' or 'puct', not {arena_search!r}")
     rank, ws = gdist.init_from_env()
@@ -793,7 +829,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
         res = run_iteration(model, trainer, it, games_per_iteration, num_simulations=num_simulations,
                             planner_steps=planner_steps, seed=seed, verbose=rank == 0, search=search,
                             temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
-                            leaves_per_round=leaves_per_round, selfplay_precision=selfplay_precision)
+                            leaves_per_round=leaves_per_round, selfplay_precision=selfplay_precision,
+                            tree_reuse=tree_reuse, fast_simulations=fast_simulations, full_prob=full_prob)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

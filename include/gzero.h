@@ -340,7 +340,7 @@ typedef struct gz_puct_params {
     double c_puct;
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
     int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3 / GZ_PV_F16: the forward of every search and self-play entry */
-    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH */
+    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP */
 } gz_puct_params;
 /* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).
  * With GZ_PUCT_ROOT_NOISE in flags the p given to gz_puct_begin, gz_puct_search,
@@ -409,6 +409,52 @@ typedef struct gz_puct_batch_params {
     int32_t leaves_per_round;     /* K */
     int32_t pad;
 } gz_puct_batch_params;      /* 56 bytes */
+/* Playout cap randomization (opt-in; KataGo's way to cheaper training games): every ply
+ * is independently a full search (S simulations, root noise, a training target) with
+ * probability full_prob, or a fast one (F = fast_simulations, no noise, played and not
+ * trained on).  With GZ_PUCT_PLAYOUT_CAP in flags p points at a gz_puct_cap_params (its
+ * noise fields are read only with GZ_PUCT_ROOT_NOISE, leaves_per_round not at all);
+ * without it nothing past the 32 / 48 / 56 bytes is read and every entry point computes
+ * what it did before.
+ *   full(seed, game, ply) = to_unit(draw(stream_key(seed, game, ply, 0x50434150), 0)) < full_prob
+ * (gzero/rng.py; the constant spells "PCAP"): a pure function of (seed, game id, ply), with
+ * no counter, independent of the move-sampling stream (..., 0) and of the noise stream.
+ * The budget B of the root at ply n_moves is S on a full ply and F on a fast one; it is
+ * decided when the node becomes a root (a fresh root: gz_puct_begin, a new game, a move
+ * without a child; an inherited one: right after the re-root) and kept with the tree.  A
+ * search is finished when its root has B+1 visits or more.  An inherited root may arrive
+ * with v >= B+1 visits (a fast ply after a full one whose chosen child was visited more
+ * than F times): it gets no simulation -- gz_puct_select gives it an inactive row,
+ * gz_selfplay_puct_rounds picks its move in the next round -- and its visit row is the
+ * inherited child visits as they are, summing to v-1 >= B; every other row sums to B.  A
+ * move takes B+1 rounds on a fresh root and max(1, B+1-v) on an inherited one.  A tree
+ * still never exceeds S+1 nodes: workspaces, the tree stride and the export layout are
+ * unchanged.  With GZ_PUCT_ROOT_NOISE only the roots of full plies are mixed (at the same
+ * two places); a fast root's row is left alone, also one inherited from a full ply (as a
+ * child it never was mixed).  gz_puct_remaining and gz_puct_reroot's d_remaining return
+ * max(0, B+1-visits[0]); gz_puct_finish and the move choice are unchanged (temp_plies
+ * applies to fast plies too).  Accepted by gz_puct_begin (which keeps F and full_prob in
+ * the workspace for select, backup and reroot), gz_puct_search, gz_puct_reroot,
+ * gz_selfplay_puct_rounds(_active) and gz_selfplay_puct_run(_active) -- the last two are
+ * correct but gain nothing: the lock-step engine runs S+1 rounds for everybody, and only
+ * the own-clock engine turns a smaller budget into fewer rounds.  GZ_ERR_ARG before any
+ * launch: fast_simulations outside [1, S], full_prob not finite or outside [0, 1], the
+ * flag together with GZ_PUCT_LEAF_BATCH, the flag in gz_puct_match_run's search params.
+ * The record format is unchanged; gz_puct_cap_full tells which records were full plies. */
+#define GZ_PUCT_PLAYOUT_CAP 4
+typedef struct gz_puct_cap_params {
+    gz_puct_batch_params batch;  /* base; the noise fields are read only with GZ_PUCT_ROOT_NOISE */
+    int32_t fast_simulations;    /* F, 1..num_simulations */
+    int32_t pad;
+    double  full_prob;           /* p, finite, in [0, 1] */
+} gz_puct_cap_params;            /* 72 bytes */
+/* Which plies were full: d_full [n] uint8 = full(seed, d_records[i].game_id,
+ * d_records[i].ply) for every record (one thread each; the same seed and full_prob as the
+ * run that made them).  gz_puct_cap_full_host: one decision, 0 or 1, by the same code on
+ * the host, no GPU. */
+int gz_puct_cap_full(const gz_record* d_records, int32_t n, uint64_t seed, double full_prob, uint8_t* d_full,
+                     void* stream);
+int gz_puct_cap_full_host(uint64_t seed, int64_t game_id, int32_t ply, double full_prob);
 /* includes the forward's workspace and gz_puct_search's leaf / output rows */
 size_t gz_puct_workspace_bytes(int32_t n, int32_t num_simulations);
 size_t gz_puct_batch_workspace_bytes(int32_t n, int32_t num_simulations, int32_t leaves_per_round);
@@ -425,7 +471,7 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t num_simulations, const 
                    const float* d_value, void* stream);
 int gz_puct_finish(void* d_workspace, int32_t n, int32_t num_simulations, int32_t* d_moves, int32_t* d_visits,
                    double* d_root_q, void* stream);
-/* simulations left to each game's budget, 0 when the game is over (any search of this mode) */
+/* simulations left to each game's budget (never below 0), 0 when the game is over (any search of this mode) */
 int gz_puct_remaining(void* d_workspace, int32_t n, int32_t num_simulations, int32_t* d_remaining, void* stream);
 /* begin, the S+1 rounds with gz_pv_forward(d_pv_weights, p->precision), finish */
 int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
@@ -548,7 +594,7 @@ int gz_selfplay_puct_compact(void* d_slots, int32_t n_slots, int32_t n_active, i
  *   commit   the visit row is stashed and the move played as gz_selfplay_puct_run does:
  *            records, visit rows and counters keep their meaning.
  * Nothing synchronises the host.  search: the shared S, temp_plies, c_puct, seed and
- * flags (0 or GZ_PUCT_ROOT_NOISE, then a gz_puct_noise_params); search->precision is not
+ * flags (0 or GZ_PUCT_ROOT_NOISE, then a gz_puct_noise_params; not GZ_PUCT_PLAYOUT_CAP); search->precision is not
  * read.  A game's moves, visit rows and z depend only on (seed, game id, the two blobs
  * and precisions, the search params, a_black_parity), not on n_slots, n_active, how
  * plies are cut into calls, or compaction.  Workspace (gz_puct_match_workspace_bytes): it

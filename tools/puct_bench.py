@@ -69,6 +69,21 @@ against the parent build, as --leaves 1 measures it.
     python tools/puct_bench.py --compact --precisions f16x3 --steps 3 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/compact_bench.json
 
+--cap F,P measures playout cap randomization (SelfPlayEngine(tree_reuse=True,
+fast_simulations=F, full_prob=P)) on the own-clock engine, for the init weights and for
+every --policy-scale: two engines of this build in one process (same slots, simulations,
+burn-in, seed and weights), without the cap -- the path of before, the baseline -- and with
+it, take turns at one window of 2 x (S+1) rounds each, --steps times, after the warm-up of
+--reuse.  Per engine: ms per round (median, and every window: the baseline's spread), the
+moves played, mean rounds per move (slot statistics) and moves/s = slots / (rounds per move
+x ms per round).  Then one training.selfplay_puct_device iteration of --cap-games games on
+as many slots each way (wall clock, after one untimed iteration that warms the allocator):
+seconds, plies, and full-ply records; from the capped iteration's whole games the share of
+full plies and of plies that needed no new simulation (the root arrived with at least its
+budget + 1 visits: the previous row's count at the move played).
+
+    python tools/puct_bench.py --cap 40,0.25 --precisions f16x3 --out profiles/puct/cap_bench.json
+
 --precision f16x3|f16|fp32 runs the lock-step, --reuse or --leaves measurement at that one
 precision (it replaces --precisions).  "f16" is the one-term fp16 tower (GZ_PV_F16); a child
 that loads another build (--forward-library, --lockstep-library: the parent commit, which
@@ -119,6 +134,8 @@ ap.add_argument("--compact-games", default="512,4096", help="--compact: games = 
 ap.add_argument("--compact-noise", default="0.3,0.25", metavar="ALPHA,EPS", help="--compact: the root noise of the noisy runs")
 ap.add_argument("--compact-child", default=None, metavar="on|off:NOISE",
                 help="(child) compaction on or off, then off or ALPHA,EPS: one iteration of --slots games on request")
+ap.add_argument("--cap", default=None, metavar="F,P", help="measure playout cap randomization (see above)")
+ap.add_argument("--cap-games", type=int, default=512, help="--cap: games (= slots) of the self-play iteration")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 precisions = [a.precision] if a.precision else a.precisions.split(",")
@@ -297,6 +314,94 @@ def reuse_run(prec, scale):
           f"{out['moves_per_s']:.0f} moves/s (lock-step {out['lockstep']['moves_per_s']:.0f})")
     del eng
     torch.cuda.empty_cache()
+    return out
+
+
+def cap_run(prec, scale, F, prob):
+    """One weight set: windows of the uncapped and the capped engine in turn, then one
+    self-play iteration each way."""
+    import time
+    import numpy as np
+    import torch
+    import training
+    from gzero.boards import RECORD_DTYPE
+    from gzero.device import cap_full
+    from gzero.selfplay import SelfPlayEngine
+    S, n = a.sims, a.slots
+    window = 2 * (S + 1)
+    w = bench_weights(prec, scale)
+    engines = {}
+    for name, kw in (("uncapped", {}), ("capped", {"fast_simulations": F, "full_prob": prob})):
+        eng = SelfPlayEngine(n_slots=n, num_simulations=S, seed=1, pv_weights=w, search="puct",
+                             temp_plies=a.temp_plies, tree_reuse=True, rounds_per_step=window, **kw)
+        eng.advance(a.burn)
+        eng.step()
+        eng.step()  # warm-up: 4 x (S+1) rounds
+        torch.cuda.synchronize()
+        engines[name] = (eng, int(eng.draws()[:, 2].sum()), [])
+    for _ in range(a.steps):
+        for name, (eng, _, wins) in engines.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng.step()
+            e1.record()
+            torch.cuda.synchronize()
+            c = eng.counters()
+            assert c["records_dropped"] == 0
+            wins.append({"ms": e0.elapsed_time(e1), "moves": int(c["moves"]), "games": int(c["games"])})
+    out = {"policy_fc_scale": scale, "rounds_per_window": window}
+    for name, (eng, took0, wins) in engines.items():
+        took = int(eng.draws()[:, 2].sum()) - took0
+        round_ms = [x["ms"] / window for x in wins]
+        moves = sum(x["moves"] for x in wins)
+        rpm = took / moves
+        out[name] = {"windows": wins, "round_ms": round_ms, "round_ms_median": median(round_ms),
+                     "round_ms_min": min(round_ms), "round_ms_max": max(round_ms), "moves": moves,
+                     "mean_rounds_per_move": rpm, "moves_per_s": n / (rpm * median(round_ms) / 1e3),
+                     "moves_per_s_counted_in_windows": moves / (sum(x["ms"] for x in wins) / 1e3)}
+    del engines, eng
+    torch.cuda.empty_cache()
+    base, cap = out["uncapped"], out["capped"]
+    out["round_ms_capped_over_uncapped"] = cap["round_ms_median"] / base["round_ms_median"]
+    out["uncapped_round_ms_spread"] = (base["round_ms_max"] - base["round_ms_min"]) / base["round_ms_median"]
+    out["rounds_per_move_arithmetic"] = prob * (S + 1) + (1.0 - prob) * (F + 1)
+    out["measured_speedup_moves_per_s"] = cap["moves_per_s"] / base["moves_per_s"]
+    # one self-play iteration each way (the model only names the weights: pv_weights is given)
+    games = a.cap_games
+    its = {}
+    for name, kw in (("warm_up", {}), ("uncapped", {}), ("capped", {"fast_simulations": F, "full_prob": prob})):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        d, d_vis, n_rec, st = training.selfplay_puct_device(games, num_simulations=S, seed=1, n_slots=games,
+                                                            model="bench weights", temp_plies=a.temp_plies,
+                                                            tree_reuse=True, pv_weights=w, **kw)
+        torch.cuda.synchronize()
+        its[name] = {"seconds": time.time() - t0, "plies": n_rec, "full_ply_records": st["full_records"],
+                     "steps": st["steps"]}
+        if name == "capped":
+            recs = np.frombuffer(d.cpu().numpy().tobytes(), RECORD_DTYPE)
+            vis = d_vis.cpu().numpy().view(np.uint16)
+            full = cap_full(d.reshape(-1), 1, prob).cpu().numpy()
+            # the visits a root arrived with: the previous ply's count at the move played
+            # (rows are sorted by (game id, ply)); a game's first root is fresh
+            prev = np.concatenate([[0], vis[np.arange(n_rec - 1), recs["move"][:-1].astype(np.int64)]]).astype(np.int64)
+            prev[recs["ply"] == 0] = 0
+            budget = np.where(full, S, F)
+            zero = prev >= budget + 1
+            its[name].update({"share_full_plies": float(full.mean()), "share_zero_simulation_plies": float(zero.mean()),
+                              "share_zero_simulation_among_fast_plies": float(zero[~full].mean()),
+                              "mean_visit_row_sum_fast_plies": float(vis[~full].astype(np.int64).sum(axis=1).mean())})
+        del d, d_vis
+    del its["warm_up"]
+    out["selfplay_iteration"] = dict(its, games=games, slots=games,
+                                     seconds_capped_over_uncapped=its["capped"]["seconds"] / its["uncapped"]["seconds"])
+    print(f"{prec} policy x{scale:g}: round {base['round_ms_median']:.3f} ms uncapped "
+          f"[{base['round_ms_min']:.3f}, {base['round_ms_max']:.3f}], {cap['round_ms_median']:.3f} ms capped; "
+          f"rounds per move {base['mean_rounds_per_move']:.1f} -> {cap['mean_rounds_per_move']:.1f} "
+          f"(arithmetic {out['rounds_per_move_arithmetic']:.1f}); moves/s {base['moves_per_s']:.0f} -> "
+          f"{cap['moves_per_s']:.0f}; {games}-game iteration {its['uncapped']['seconds']:.2f} s "
+          f"({its['uncapped']['full_ply_records']} records) -> {its['capped']['seconds']:.2f} s "
+          f"({its['capped']['full_ply_records']} full of {its['capped']['plies']})", flush=True)
     return out
 
 
@@ -737,6 +842,34 @@ if a.noise:
     sys.exit(0)
 if a.lockstep_child is not None:
     lockstep_child()
+    sys.exit(0)
+if a.cap:
+    prec = precisions[0]
+    F, prob = a.cap.split(",")
+    F, prob = int(F), float(prob)
+    res = {"config": {"slots": a.slots, "simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies,
+                      "precision": prec, "fast_simulations": F, "full_prob": prob, "steps": a.steps,
+                      "warm_up_rounds": 4 * (a.sims + 1),
+                      "timing": "device events around windows of 2 x (S+1) rounds; the uncapped engine (the flag "
+                                "clear: the path of before) and the capped one, both of this build and in one "
+                                "process, take turns; the iteration is wall clock around "
+                                "training.selfplay_puct_device",
+                      "claims": "cost per round, rounds per move and moves/s only; the scaled-policy runs are "
+                                "synthetic and nothing is claimed about playing strength or learning"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    res["results"]["init_weights"] = cap_run(prec, 1.0, F, prob)
+    for scale in (float(x) for x in a.policy_scale.split(",") if x):
+        res["results"][f"policy_fc_x{scale:g}_synthetic"] = cap_run(prec, scale, F, prob)
+    import torch
+    res["device"] = torch.cuda.get_device_name(0)
+    print("PUCT_CAP_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.reuse:
     prec = precisions[0]
