@@ -393,10 +393,15 @@ __device__ inline void write_leaf(uint32_t* leaves, int32_t* active, int g, cons
     if (lane == 0) active[g] = live ? 1 : 0;
 }
 
+// unevaluated: the node never gets an evaluation (a terminal node, the root of a board that
+// is over), so no backup stores its prior row: it is zeroed here, and gz_puct_trees exports
+// a row that does not depend on what the workspace held
 __device__ inline void new_node(const PuctTree& t, int j, int parent, int move, int term, const BB& black,
-                                const BB& white) {
+                                const BB& white, bool unevaluated) {
     const int lane = lane_id();
     for (int c = lane; c < GZ_CELLS; c += WAVE) t.child[(size_t)j * GZ_CELLS + c] = -1;
+    if (unevaluated)
+        for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = 0.0;
     if (lane < 16) t.board[(size_t)j * 16 + lane] = lane < 8 ? bb_word(black, lane) : bb_word(white, lane - 8);
     if (lane == 0) {
         t.parent[j] = (int16_t)parent;
@@ -411,7 +416,7 @@ __device__ inline void new_node(const PuctTree& t, int j, int parent, int move, 
 // a one-node tree: the root waits for its evaluation (pending 0) unless the game is over
 __device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& white, int64_t game_id, int n_moves,
                                   int player, bool over, int32_t reuse, int budget, bool full) {
-    new_node(t, 0, -1, 255, 0, black, white);
+    new_node(t, 0, -1, 255, 0, black, white, over);
     if (lane_id() == 0) {
         PuctHdr* h = t.h;
         store_bb(h->black, black);
@@ -560,7 +565,7 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
         else bb_set(white, bit);
         cnt++;
         const int term = win ? mover : ((ne == 1 || cnt >= GZ_MAX_GAME_PLIES) ? 3 : 0);
-        new_node(t, j, i, bi, term, black, white);
+        new_node(t, j, i, bi, term, black, white, term != 0);
         if (lane == 0) {
             t.child[(size_t)i * GZ_CELLS + bi] = (int16_t)j;
             h->n_nodes = j + 1;
@@ -709,7 +714,7 @@ __global__ __launch_bounds__(WAVE) void puct_select_batch_kernel(char* ws, int n
             else bb_set(white, bit);
             cnt++;
             const int term = win ? mover : ((ne == 1 || cnt >= GZ_MAX_GAME_PLIES) ? 3 : 0);
-            new_node(t, j, i, bi, term, black, white);
+            new_node(t, j, i, bi, term, black, white, term != 0);
             if (lane == 0) {
                 t.child[(size_t)i * GZ_CELLS + bi] = (int16_t)j;
                 h->n_nodes = j + 1;

@@ -544,6 +544,7 @@ __global__ __launch_bounds__(WAVE, GZ_SP_WPE) void selfplay_kernel(char* slots, 
             r.move = (int16_t)mv;
             r.player = (int8_t)player;
             r.z = 0;
+            r.pad[0] = r.pad[1] = 0;  // (a record is 80 written bytes, whatever d_slots held)
             // board.make_move (gomoku_board.py:84-113)
             if (player == 1) bb_set(rs.black, bit);
             else bb_set(rs.white, bit);
@@ -635,6 +636,7 @@ __global__ __launch_bounds__(WAVE) void selfplay_commit_kernel(char* slots, int 
         r.move = (int16_t)mv;
         r.player = (int8_t)player;
         r.z = 0;
+        r.pad[0] = r.pad[1] = 0;  // (a record is 80 written bytes, whatever d_slots held)
     }
     bb_set(mine, bit);
     const int over = win ? player : ((ne == 1 || n_moves + 1 >= 200) ? 3 : 0);

@@ -68,16 +68,21 @@ class PuctMatch:
         n = self.n_slots
         self.n_active = n
         self.compacting = bool(compact)
-        self.d_slots = torch.zeros(n * self.lib.gz_slot_bytes(S), dtype=torch.uint8, device="cuda")
+        # (gz_selfplay_init writes every slot's whole header; records and visit rows at or past
+        # the counters' record count are not written and not read)
+        self.d_slots = torch.empty(n * self.lib.gz_slot_bytes(S), dtype=torch.uint8, device="cuda")
         self.d_ws = torch.empty(self.lib.gz_puct_match_workspace_bytes(n, S), dtype=torch.uint8, device="cuda")
         self.record_cap = n * _lib.GZ_MAX_GAME_PLIES  # one game per slot
-        self.d_records = torch.zeros(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        self.d_visits = torch.zeros(self.record_cap * 225, dtype=torch.int16, device="cuda")
+        self.d_records = torch.empty(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self.d_visits = torch.empty(self.record_cap * 225, dtype=torch.int16, device="cuda")
+        # in/out (gzero.h: "d_counters is added to, never cleared: the caller zeroes it")
         self.d_counters = torch.zeros(COUNTER_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        # in/out (gzero.h: "the caller zeroes it once per match")
         self.d_tally = torch.zeros(len(TALLY_FIELDS), dtype=torch.int64, device="cuda")
         self.span = (n - 1) * self.stride + 1
+        # in/out (gzero.h: "games not in d_records are left alone")
         self.d_result = torch.full((self.span,), _UNPLAYED, dtype=torch.int8, device="cuda")
-        self.d_order = torch.zeros(n, dtype=torch.int32, device="cuda")
+        self.d_order = torch.empty(n, dtype=torch.int32, device="cuda")
         self.d_n_active = torch.full((1,), n, dtype=torch.int32, device="cuda")
         self.d_compact_ws = torch.empty(self.lib.gz_selfplay_puct_compact_workspace_bytes(n), dtype=torch.uint8,
                                         device="cuda")
@@ -203,8 +208,8 @@ class PuctMatch:
 
     def boards(self):
         """(states, game ids) of every slot, in slot order (permuted by a compaction)."""
-        out = torch.zeros(self.n_slots * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        gids = torch.zeros(self.n_slots, dtype=torch.int64, device="cuda")
+        out = torch.empty(self.n_slots * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        gids = torch.empty(self.n_slots, dtype=torch.int64, device="cuda")
         _lib.check(self.lib.gz_selfplay_boards(ptr(self.d_slots), self.n_slots, self.S, ptr(out), ptr(gids),
                                                stream()), "gz_selfplay_boards")
         return np.frombuffer(out.cpu().numpy().tobytes(), STATE_DTYPE), gids.cpu().numpy()

@@ -55,8 +55,8 @@ def board_step(states, moves):
     n = len(states)
     d_states = to_dev(states)
     d_moves = torch.as_tensor(np.asarray(moves, np.int32)).cuda()
-    d_ok = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_legal = torch.zeros(n * 4, dtype=torch.int64, device="cuda")
+    d_ok = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_legal = torch.empty(n * 4, dtype=torch.int64, device="cuda")
     _lib.check(lib.gz_board_step(ptr(d_states), ptr(d_moves), n, ptr(d_ok), ptr(d_legal), stream()), "gz_board_step")
     torch.cuda.synchronize()
     return (from_dev(d_states, STATE_DTYPE), d_ok.cpu().numpy(),
@@ -70,8 +70,8 @@ def policy_move(states, keys):
     n = len(states)
     d_states = to_dev(states)
     d_keys = torch.as_tensor(np.asarray(keys, np.uint64).view(np.int64)).cuda()
-    d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_draws = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_moves = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_draws = torch.empty(n, dtype=torch.int32, device="cuda")
     _lib.check(lib.gz_policy_move(ptr(d_states), ptr(d_keys), n, ptr(d_moves), ptr(d_draws), stream()),
                "gz_policy_move")
     torch.cuda.synchronize()
@@ -85,9 +85,9 @@ def rollout(states, ai, keys, max_depth=100):
     d_states = to_dev(states)
     d_ai = torch.as_tensor(np.asarray(ai, np.int32)).cuda()
     d_keys = torch.as_tensor(np.asarray(keys, np.uint64).view(np.int64)).cuda()
-    d_vals = torch.zeros(n, dtype=torch.float64, device="cuda")
-    d_fin = torch.zeros(n * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-    d_draws = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_vals = torch.empty(n, dtype=torch.float64, device="cuda")
+    d_fin = torch.empty(n * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_draws = torch.empty(n, dtype=torch.int32, device="cuda")
     _lib.check(lib.gz_rollout(ptr(d_states), ptr(d_ai), ptr(d_keys), n, int(max_depth), ptr(d_vals), ptr(d_fin),
                               ptr(d_draws), stream()), "gz_rollout")
     torch.cuda.synchronize()
@@ -100,8 +100,8 @@ def pattern_score(states, players):
     n = len(states)
     d_states = to_dev(states)
     d_pl = torch.as_tensor(np.asarray(players, np.int32)).cuda()
-    d_s = torch.zeros(n, dtype=torch.int64, device="cuda")
-    d_bg = torch.zeros(n, dtype=torch.float64, device="cuda")
+    d_s = torch.empty(n, dtype=torch.int64, device="cuda")
+    d_bg = torch.empty(n, dtype=torch.float64, device="cuda")
     _lib.check(lib.gz_pattern_score(ptr(d_states), ptr(d_pl), n, ptr(d_s), ptr(d_bg), stream()), "gz_pattern_score")
     torch.cuda.synchronize()
     return d_s.cpu().numpy(), d_bg.cpu().numpy()
@@ -130,12 +130,13 @@ def search(states, game_ids, params, want_trees=False, leaf_cap=0):
     n = len(states)
     d_states = to_dev(states)
     d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
-    d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_stats = torch.zeros(n * ctypes.sizeof(_lib.SearchStats), dtype=torch.uint8, device="cuda")
+    d_moves = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_stats = torch.empty(n * ctypes.sizeof(_lib.SearchStats), dtype=torch.uint8, device="cuda")
     tb = lib.gz_tree_bytes(params.num_simulations)
-    d_trees = torch.zeros(n * tb, dtype=torch.uint8, device="cuda") if want_trees else None
+    d_trees = torch.empty(n * tb, dtype=torch.uint8, device="cuda") if want_trees else None
     gather = (params.flags & _lib.GZ_FLAG_GATHER_LEAVES) != 0
-    d_leaves = torch.zeros(max(1, leaf_cap) * 16, dtype=torch.int32, device="cuda") if gather else None
+    d_leaves = torch.empty(max(1, leaf_cap) * 16, dtype=torch.int32, device="cuda") if gather else None
+    # in/out (gzero.h: "*d_leaf_count (the caller zeroes it) is advanced by every leaf produced")
     d_lc = torch.zeros(1, dtype=torch.int32, device="cuda") if gather else None
     _lib.check(lib.gz_search(ptr(d_states), ptr(d_gids), n, ctypes.byref(params), ptr(d_trees), ptr(d_moves),
                              ptr(d_stats), ptr(d_leaves), int(leaf_cap), ptr(d_lc), stream()), "gz_search")
@@ -244,7 +245,7 @@ def pv_forward_tree(weights, leaf_rows, meta, root_cap=None, d_count=None):
     _lib.check(lib.gz_pv_forward_tree(ptr(weights.tensor), ptr(d_b), ptr(d_m), n, ptr(d_count), int(root_cap),
                                       ptr(d_lg), ptr(d_v), ptr(d_p), ptr(d_pr), ptr(ws), stream()),
                "gz_pv_forward_tree")
-    st = torch.zeros(6, dtype=torch.int32, device="cuda")
+    st = torch.empty(6, dtype=torch.int32, device="cuda")
     _lib.check(lib.gz_pv_tree_stats(ptr(ws), n, ptr(st), stream()), "gz_pv_tree_stats")
     torch.cuda.synchronize()
     return (d_lg.cpu().numpy().reshape(n, 225), d_v.cpu().numpy(), d_p.cpu().numpy().reshape(n, 225),
@@ -300,13 +301,14 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
     n = len(states)
     d_states = to_dev(states)
     d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
-    d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_stats = torch.zeros(n * ctypes.sizeof(_lib.SearchStats), dtype=torch.uint8, device="cuda")
+    d_moves = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_stats = torch.empty(n * ctypes.sizeof(_lib.SearchStats), dtype=torch.uint8, device="cuda")
     S = params.num_simulations
     tb = lib.gz_tree_bytes(S)
-    d_trees = torch.zeros(n * tb, dtype=torch.uint8, device="cuda") if want_trees else None
+    d_trees = torch.empty(n * tb, dtype=torch.uint8, device="cuda") if want_trees else None
     gather = (params.flags & _lib.GZ_FLAG_GATHER_LEAVES) != 0
-    d_leaves = torch.zeros(max(1, leaf_cap) * 16, dtype=torch.int32, device="cuda") if gather else None
+    d_leaves = torch.empty(max(1, leaf_cap) * 16, dtype=torch.int32, device="cuda") if gather else None
+    # in/out (gzero.h: "*d_leaf_count (the caller zeroes it) is advanced by every leaf produced")
     d_lc = torch.zeros(1, dtype=torch.int32, device="cuda") if gather else None
     ws = torch.empty(lib.gz_plan_workspace_bytes(n, S), dtype=torch.uint8, device="cuda")
     _lib.check(lib.gz_plan_search(ptr(d_states), ptr(d_gids), n, ctypes.byref(params), ctypes.byref(pparams),
@@ -389,7 +391,7 @@ def cap_full(records_dev, seed, full_prob):
     if not 0.0 <= prob <= 1.0:
         raise ValueError(f"full_prob must be in [0, 1], not {full_prob!r}")
     n = records_dev.numel() // 80
-    d_full = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    d_full = torch.empty(n, dtype=torch.uint8, device="cuda")
     _lib.check(lib.gz_puct_cap_full(ptr(records_dev), n, int(seed) & ((1 << 64) - 1), prob, ptr(d_full), stream()),
                "gz_puct_cap_full")
     return d_full != 0
@@ -436,7 +438,7 @@ def puct_root_noise(states, game_ids, seed, alpha):
     n = len(states)
     d_states = to_dev(states)
     d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
-    d_eta = torch.zeros(n * 225, dtype=torch.float64, device="cuda")
+    d_eta = torch.empty(n * 225, dtype=torch.float64, device="cuda")
     _lib.check(lib.gz_puct_root_noise(ptr(d_states), ptr(d_gids), n, int(seed) & ((1 << 64) - 1), float(alpha),
                                       ptr(d_eta), stream()), "gz_puct_root_noise")
     return d_eta.cpu().numpy().reshape(n, 225)
@@ -476,7 +478,7 @@ def parse_puct_tree(raw, num_simulations):
 
 def _puct_trees(lib, ws, n, S):
     tb = lib.gz_puct_tree_bytes(S)
-    d_out = torch.zeros(n * tb, dtype=torch.uint8, device="cuda")
+    d_out = torch.empty(n * tb, dtype=torch.uint8, device="cuda")
     _lib.check(lib.gz_puct_trees(ptr(ws), n, S, ptr(d_out), stream()), "gz_puct_trees")
     raw = d_out.cpu().numpy().reshape(n, tb)
     return [parse_puct_tree(raw[i], S) for i in range(n)]
@@ -495,9 +497,9 @@ def puct_search(states, game_ids, params, pv_weights, want_trees=False, leaves_p
     S = params.num_simulations
     d_states = to_dev(states)
     d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
-    d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_visits = torch.zeros(n * 225, dtype=torch.int32, device="cuda")
-    d_q = torch.zeros(n, dtype=torch.float64, device="cuda")
+    d_moves = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_visits = torch.empty(n * 225, dtype=torch.int32, device="cuda")
+    d_q = torch.empty(n, dtype=torch.float64, device="cuda")
     ws = torch.empty(_puct_workspace_bytes(lib, n, params), dtype=torch.uint8, device="cuda")
     _lib.check(lib.gz_puct_search(ptr(d_states), ptr(d_gids), n, ctypes.byref(params), ptr(pv_weights.tensor),
                                   ptr(ws), ptr(d_moves), ptr(d_visits), ptr(d_q), stream()), "gz_puct_search")
@@ -538,8 +540,8 @@ class PuctStepper:
         self.params = params
         d_states = to_dev(states)
         d_gids = torch.as_tensor(np.asarray(game_ids, np.int64)).cuda()
-        self.d_leaves = torch.zeros(self.rows * 16, dtype=torch.int32, device="cuda")
-        self.d_active = torch.zeros(self.rows, dtype=torch.int32, device="cuda")
+        self.d_leaves = torch.empty(self.rows * 16, dtype=torch.int32, device="cuda")
+        self.d_active = torch.empty(self.rows, dtype=torch.int32, device="cuda")
         self.ws = torch.empty(_puct_workspace_bytes(self.lib, self.n, params), dtype=torch.uint8, device="cuda")
         _lib.check(self.lib.gz_puct_begin(ptr(d_states), ptr(d_gids), self.n, ctypes.byref(params), ptr(self.ws),
                                           ptr(self.d_leaves), ptr(self.d_active), stream()), "gz_puct_begin")
@@ -552,7 +554,7 @@ class PuctStepper:
     def remaining(self):
         """Simulations left to each game's budget, int32 [n] (0: the game is over or its
         search is finished); gz_puct_remaining, synchronising."""
-        d_rem = torch.zeros(self.n, dtype=torch.int32, device="cuda")
+        d_rem = torch.empty(self.n, dtype=torch.int32, device="cuda")
         _lib.check(self.lib.gz_puct_remaining(ptr(self.ws), self.n, self.S, ptr(d_rem), stream()),
                    "gz_puct_remaining")
         return d_rem.cpu().numpy()
@@ -573,9 +575,9 @@ class PuctStepper:
                    "gz_puct_backup")
 
     def finish(self):
-        d_moves = torch.zeros(self.n, dtype=torch.int32, device="cuda")
-        d_visits = torch.zeros(self.n * 225, dtype=torch.int32, device="cuda")
-        d_q = torch.zeros(self.n, dtype=torch.float64, device="cuda")
+        d_moves = torch.empty(self.n, dtype=torch.int32, device="cuda")
+        d_visits = torch.empty(self.n * 225, dtype=torch.int32, device="cuda")
+        d_q = torch.empty(self.n, dtype=torch.float64, device="cuda")
         _lib.check(self.lib.gz_puct_finish(ptr(self.ws), self.n, self.S, ptr(d_moves), ptr(d_visits), ptr(d_q),
                                            stream()), "gz_puct_finish")
         torch.cuda.synchronize()
@@ -592,7 +594,7 @@ class PuctStepper:
         d_moves = torch.as_tensor(np.asarray(moves, np.int32).reshape(-1)).cuda()
         if d_moves.numel() != self.n:
             raise ValueError("reroot() wants one move per game")
-        d_rem = torch.zeros(self.n, dtype=torch.int32, device="cuda")
+        d_rem = torch.empty(self.n, dtype=torch.int32, device="cuda")
         _lib.check(self.lib.gz_puct_reroot(ptr(self.ws), self.n, self.S, ptr(d_moves), ptr(self.d_leaves),
                                            ptr(self.d_active), ptr(d_rem), stream()), "gz_puct_reroot")
         return d_rem.cpu().numpy()
@@ -610,8 +612,8 @@ def planner_move(states, ais, keys, pparams, gn_weights):
     d_states = to_dev(states)
     d_ai = torch.as_tensor(np.asarray(ais, np.int32)).cuda()
     d_keys = torch.as_tensor(np.asarray(keys, np.uint64).view(np.int64)).cuda()
-    d_moves = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_draws = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_moves = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_draws = torch.empty(n, dtype=torch.int32, device="cuda")
     ws = torch.empty(lib.gz_planner_move_workspace_bytes(n), dtype=torch.uint8, device="cuda")
     _lib.check(lib.gz_planner_move(ptr(d_states), ptr(d_ai), ptr(d_keys), n, ctypes.byref(pparams),
                                    ptr(gn_weights.tensor), ptr(ws), ptr(d_moves), ptr(d_draws), stream()),

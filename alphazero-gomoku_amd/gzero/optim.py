@@ -31,6 +31,7 @@ class DeviceAdam(torch.optim.Optimizer):
                     raise ValueError("DeviceAdam: parameters must be contiguous float32 CUDA tensors")
         dev = self.param_groups[0]["params"][0].device
         self._ws = torch.empty(int(self._lib.gz_adam_workspace_bytes()), dtype=torch.uint8, device=dev)
+        # (gzero.h: "d_norm ... written only when max_norm > 0": 0 until the first clipped step)
         self.last_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self._tables = {}  # per group: (the tensors' data pointers, the ctypes table built from them)
 

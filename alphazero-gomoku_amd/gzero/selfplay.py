@@ -136,7 +136,9 @@ class SelfPlayEngine:
             raise ValueError(f"pv_mode={pv_mode!r} needs f16x3 weights")
         S = self.params.num_simulations
         slot_bytes = self.lib.gz_slot_bytes(S)
-        self.d_slots = torch.zeros(self.n_slots * slot_bytes, dtype=torch.uint8, device="cuda")
+        # (gzero.h: "gz_selfplay_init writes the whole 128-byte header of every slot; the record
+        # area behind it is written ply by ply before it is read")
+        self.d_slots = torch.empty(self.n_slots * slot_bytes, dtype=torch.uint8, device="cuda")
         self.rounds_per_step = (S + 1 if rounds_per_step is None else int(rounds_per_step)) if self.tree_reuse else 0
         if self.tree_reuse and self.rounds_per_step < 1:
             raise ValueError("rounds_per_step must be at least 1")
@@ -144,7 +146,8 @@ class SelfPlayEngine:
         # tree reuse: at most 199 earlier plies plus one per round)
         self.record_cap = self.n_slots * (_lib.GZ_MAX_GAME_PLIES +
                                           (self.rounds_per_step if self.tree_reuse else self.plies_per_step))
-        self.d_records = torch.zeros(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self.d_records = torch.empty(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        # in/out (gzero.h: "d_counters is added to, never cleared: the caller zeroes it")
         self.d_counters = torch.zeros(COUNTER_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self.puct = self.d_puct_ws = self.d_visits = None
         if search == "puct":
@@ -156,12 +159,12 @@ class SelfPlayEngine:
             self.d_puct_ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
             # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
             # has no uint16 arithmetic; a count is at most GZ_MAX_SIMULATIONS)
-            self.d_visits = torch.zeros(self.record_cap * 225, dtype=torch.int16, device="cuda")
+            self.d_visits = torch.empty(self.record_cap * 225, dtype=torch.int16, device="cuda")
             if self.tree_reuse:
                 self._puct_reset()
         self.leaf_cap = self.n_slots * self.plies_per_step * (S + 1) if self.gather else 0
         if self.gather:
-            self.d_leaves = torch.zeros(self.leaf_cap * 16, dtype=torch.int32, device="cuda")
+            self.d_leaves = torch.empty(self.leaf_cap * 16, dtype=torch.int32, device="cuda")
             self.d_logits = torch.empty(self.leaf_cap * 225, dtype=torch.float32, device="cuda")
             self.d_value = torch.empty(self.leaf_cap, dtype=torch.float32, device="cuda")
             self.d_probs = torch.empty(self.leaf_cap * 225, dtype=torch.float32, device="cuda")
@@ -183,12 +186,12 @@ class SelfPlayEngine:
         if game_id_end is not None:
             _lib.check(self.lib.gz_selfplay_set_game_end(ptr(self.d_slots), self.n_slots, int(game_id_end), stream()),
                        "gz_selfplay_set_game_end")
-            self.d_n_active = torch.zeros(1, dtype=torch.int32, device="cuda")
+            self.d_n_active = torch.empty(1, dtype=torch.int32, device="cuda")
         self.d_order = None
         if self.compact_slots:  # in place: no second slot buffer
             self.d_compact_ws = torch.empty(self.lib.gz_selfplay_puct_compact_workspace_bytes(self.n_slots),
                                             dtype=torch.uint8, device="cuda")
-            self.d_order = torch.zeros(self.n_slots, dtype=torch.int32, device="cuda")
+            self.d_order = torch.empty(self.n_slots, dtype=torch.int32, device="cuda")
         elif game_id_end is not None:
             self.d_slots_alt = torch.empty_like(self.d_slots)
             self.d_compact_ws = torch.empty(self.lib.gz_selfplay_compact_workspace_bytes(self.n_slots),
@@ -342,7 +345,7 @@ class SelfPlayEngine:
         """List sizes of the last tree forward: roots seen, roots with maps,
         incremental root children, full-forward boards, incremental grandchildren,
         patch slots claimed (synchronising)."""
-        out = torch.zeros(6, dtype=torch.int32, device="cuda")
+        out = torch.empty(6, dtype=torch.int32, device="cuda")
         _lib.check(self.lib.gz_pv_tree_stats(ptr(self.d_tree_ws), self.leaf_cap, ptr(out), stream()),
                    "gz_pv_tree_stats")
         return [int(x) for x in out.cpu()]
@@ -389,8 +392,8 @@ class SelfPlayEngine:
 
     def boards(self):
         """(states, game ids) of every slot, in slot order (permuted by a compaction)."""
-        out = torch.zeros(self.n_slots * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        gids = torch.zeros(self.n_slots, dtype=torch.int64, device="cuda")
+        out = torch.empty(self.n_slots * STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        gids = torch.empty(self.n_slots, dtype=torch.int64, device="cuda")
         _lib.check(self.lib.gz_selfplay_boards(ptr(self.d_slots), self.n_slots, self.params.num_simulations,
                                                ptr(out), ptr(gids), stream()), "gz_selfplay_boards")
         return np.frombuffer(out.cpu().numpy().tobytes(), STATE_DTYPE), gids.cpu().numpy()
@@ -401,7 +404,7 @@ class SelfPlayEngine:
         RNG draws) summed over every search each slot ran since the engine was created
         (gz_selfplay_draws).  The totals travel with the slot buffers: after a compaction
         the rows are permuted (and, in the default mode, the active slots' come first)."""
-        out = torch.zeros(self.n_slots * 3, dtype=torch.int64, device="cuda")
+        out = torch.empty(self.n_slots * 3, dtype=torch.int64, device="cuda")
         _lib.check(self.lib.gz_selfplay_draws(ptr(self.d_slots), self.n_slots, ptr(out), stream()),
                    "gz_selfplay_draws")
         return out.cpu().numpy().reshape(self.n_slots, 3)

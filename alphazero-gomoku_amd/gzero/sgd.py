@@ -176,7 +176,9 @@ class NetStep:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise ValueError("gz_sgd: parameters must be contiguous float32 CUDA tensors")
         dev = self.params[0].device
-        self.grads = torch.zeros(sum(p.numel() for p in self.params), dtype=torch.float32, device=dev)
+        # (gz_sgd_grads / gz_sgd_fc_grads: "outputs (overwritten, not accumulated)" -- every
+        # parameter is one of theirs, checked below)
+        self.grads = torch.empty(sum(p.numel() for p in self.params), dtype=torch.float32, device=dev)
         off = 0
         self._views = []
         for p in self.params:
@@ -206,11 +208,15 @@ class NetStep:
         if (tuple(fcs[0].shape) != (225, 450) or tuple(fcs[2].shape) != (64, 225)
                 or tuple(fcs[4].shape) != (1, 64)):
             raise ValueError("gz_sgd: FC heads must be policy_fc 450 -> 225, value_fc1 225 -> 64, value_fc2 64 -> 1")
-        self.fc = _lib.SgdFc(*[t.data_ptr() for t in fcs])
+        written = {id(t) for t in tp} | {id(t) for t in fcs}
+        if any(id(p) not in written for p in self.params):
+            raise ValueError("gz_sgd: the net has a parameter that is neither the tower's nor an FC head's "
+                             "(its gradient would never be written)")
+        self.fc =_lib.SgdFc(*[t.data_ptr() for t in fcs])
         self.fcg = _lib.SgdFc(*[t.grad.data_ptr() for t in fcs])
         self.st, self.gr = st, gr
         self.counts = [bn.num_batches_tracked for bn in bns if bn.track_running_stats]
-        self.loss = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.loss = torch.empty(3, dtype=torch.float32, device=dev)
         self._bufs = {}
 
     def _buffers(self, B, dev):

@@ -129,7 +129,8 @@ int gz_pattern_score(const gz_board_state* d_boards, const int32_t* d_player, in
 
 /* ---- K2+K3: one AlphaZeroGomokuAI.get_move per board (ai_agent.py:109-222) ----
  * One wavefront per board.  d_trees: n * gz_tree_bytes(num_simulations)
- * scratch holding each search tree (layout in DESIGN.md; readable by tests).
+ * scratch holding each search tree (layout in DESIGN.md; readable by tests: entries
+ * [0, n_nodes) of every array are the tree, the entries past them are undefined).
  * d_moves[i] = chosen cell or -1 (None).  Leaves are appended to d_leaves
  * ([leaf_cap][16] uint32: black[8], white[8]) when GZ_FLAG_GATHER_LEAVES.
  * *d_leaf_count (the caller zeroes it) is advanced by every leaf produced, also
@@ -148,7 +149,15 @@ int gz_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t
  * d_leaf_meta (optional, [leaf_cap] int32) tags every gathered leaf for
  * gz_pv_forward_tree: -1 = a search root, i >= 0 = a child of the node at leaf
  * index i (one stone more; that node is the root or one of its children), -2 =
- * any deeper node. */
+ * any deeper node.
+ * Memory contract.  d_slots needs no initialisation: gz_selfplay_init writes the whole
+ * 128-byte header of every slot; the record area behind it is written ply by ply before
+ * it is read.  d_counters is added to, never cleared: the caller zeroes it (before the
+ * first call, or before every call for per-call counts; leaves_dropped is never written).
+ * d_records, d_visits (PUCT entries), d_leaves and d_leaf_meta are written at the rows the
+ * counters count and nowhere else: rows at or past min(records, record_cap), or
+ * min(leaves, leaf_cap), keep what they held.  Every byte of a written record is
+ * defined (pad is 0). */
 size_t gz_slot_bytes(int32_t num_simulations);
 int gz_selfplay_init(void* d_slots, int32_t n_slots, int32_t num_simulations, int64_t game_id_base,
                      int64_t game_id_stride, void* stream);
@@ -189,7 +198,10 @@ int gz_selfplay_boards(const void* d_slots, int32_t n_slots, int32_t num_simulat
  * d_weights: packed blob of gz_pv_weight_floats() floats (layout in
  * csrc/gz_pvnet.h / gzero/weights.py).  Boards [n][16] uint32 bit planes.  If
  * d_count is not NULL it holds the number of valid boards on the device
- * (n = capacity).  Outputs: logits [n][225], value [n] (tanh), probs
+ * (n = capacity; output rows at or past min(*d_count, n) are not written and keep what
+ * they held).  The workspace needs no initialisation, here and in every other entry point
+ * that takes one, unless its comment says otherwise (gz_selfplay_puct_reset, the GraphNet
+ * statistics).  Outputs: logits [n][225], value [n] (tanh), probs
  * [n][225] (softmax) or NULL; prior (optional, needs probs) = [n][225] float64
  * MCTSNode._get_prior_probability (ai_agent.py:564-582): the softmax at the empty
  * cells renormalised by their float64 sum (numpy's pairwise order), 0 at stones --
@@ -480,7 +492,11 @@ int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, in
 /* the trees of the last search on this workspace, gz_puct_tree_bytes(S) per game:
  * int32 n_nodes, evaluated nodes, main-stream draws, move; then in creation order
  * W f64[S+1], prior f64[S+1][225], visits i32[S+1], leaf value f32[S+1], board
- * u32[S+1][16], parent i16[S+1], move u8[S+1] (255 = root), term u8[S+1] */
+ * u32[S+1][16], parent i16[S+1], move u8[S+1] (255 = root), term u8[S+1].
+ * Entries [0, n_nodes) of every array are the tree; the entries past them are undefined.
+ * A node that is never evaluated (a terminal node, the root of a board that is over) has
+ * an all-zero prior row and value 0; a node that still waits for its evaluation (between
+ * a select, begin or reroot and the backup) has no prior row yet: it is undefined. */
 size_t gz_puct_tree_bytes(int32_t num_simulations);
 int gz_puct_trees(const void* d_workspace, int32_t n, int32_t num_simulations, void* d_out, void* stream);
 /* Self-play with this search (slots as gz_selfplay_init): per ply the slots'
@@ -790,7 +806,8 @@ int gz_sgd_saved(const void* d_workspace, int32_t boards, int32_t which, float* 
  * <= 0: no clipping.  step = the step number after this update (1 on the first).  Then per
  * element g' = g + wd p; m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2;
  * p -= (lr / (1-b1^step)) m / (sqrt(v) / sqrt(1-b2^step) + eps).  d_norm (optional): the
- * pre-clip norm (float32, as clip_grad_norm_ returns).  d_workspace:
+ * pre-clip norm (float32, as clip_grad_norm_ returns), written only when max_norm > 0
+ * (without clipping no norm is computed and *d_norm keeps its value).  d_workspace:
  * gz_adam_workspace_bytes(). */
 #define GZ_ADAM_MAX_TENSORS 48
 typedef struct gz_adam_tensor {
