@@ -23,7 +23,8 @@ the move from the visit counts below ``temp_plies`` plies (default 0: always the
 visited cell) and sets ``last_search_visits`` / ``last_root_value``.
 ``leaves_per_round=K`` (default 1) evaluates K leaves per board per round with virtual
 loss (``device.puct_params``): a move of one board then takes about ``1 + S/K``
-forwards instead of ``S + 1``.  Play (here and in
+forwards instead of ``S + 1``.  ``leaf_symmetry=True`` (default off) evaluates every
+leaf under one of the 8 board symmetries, picked by (seed, position).  Play (here and in
 the arena) is always noise-free: the Dirichlet noise at the search root
 (``SelfPlayEngine(dirichlet_alpha=...)``) is self-play exploration only.
 ``time_limit`` is accepted for compatibility; the GPU completes every
@@ -48,7 +49,7 @@ class AlphaZeroGomokuAI:
                  device: Optional[str] = None, beta: float = 0.2, planner_steps: int = 5,
                  time_limit: float = 5.0, time_reward_factor: float = 0.1, seed: Optional[int] = None,
                  game_id: int = 0, compute_priors: bool = True, search: str = "reference",
-                 temp_plies: int = 0, leaves_per_round: int = 1):
+                 temp_plies: int = 0, leaves_per_round: int = 1, leaf_symmetry: bool = False):
         if search not in ("reference", "puct"):
             raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
         self.search = search
@@ -56,6 +57,9 @@ class AlphaZeroGomokuAI:
         self.leaves_per_round = int(leaves_per_round)
         if self.leaves_per_round != 1 and search != "puct":
             raise ValueError("leaves_per_round needs search='puct'")
+        self.leaf_symmetry = bool(leaf_symmetry)
+        if self.leaf_symmetry and search != "puct":
+            raise ValueError("leaf_symmetry needs search='puct'")
         self.last_search_visits = None  # puct: int32 [n, 225] root visit counts of the last call
         self.last_root_value = None     # puct: the roots' mean value for the side to move
         self.player = player
@@ -171,7 +175,8 @@ class AlphaZeroGomokuAI:
         if boards:
             w = self.model.device_weights()
             p = device.puct_params(self.params.get("num_simulations", 200), self.params["c_puct"], self.temp_plies,
-                                   self.seed, w.precision, leaves_per_round=self.leaves_per_round)
+                                   self.seed, w.precision, leaves_per_round=self.leaves_per_round,
+                                   leaf_symmetry=self.leaf_symmetry)
             states = np.concatenate([b.to_state() for b in boards])
             mv, visits, q, _ = device.puct_search(states, [int(g) for g in game_ids], p, w)
             self.last_search_visits, self.last_root_value = visits, q

@@ -41,6 +41,14 @@ int gz_internal_gn_forward_tagged(const float* d_weights, const uint32_t* d_rows
                                   const int32_t* d_inc_list, const int32_t* d_inc_count, const void* d_tags,
                                   void* d_slots, float* d_p, float* d_q, float* d_rec, float* d_hscratch,
                                   int32_t* d_queue, void* stream);
+
+// gz_pvsym.hip: row i of d_out = row i of d_in under its symmetry t (d_sym_in[i] & 7, or
+// sym_of(seed, row) when d_sym_in is NULL), t into d_sym_out[i]; d_out may be d_in
+int gz_internal_sym_boards(const uint32_t* d_in, uint32_t* d_out, int32_t n, const int32_t* d_count,
+                           const uint8_t* d_sym_in, uint64_t seed, uint8_t* d_sym_out, void* stream);
+// gz_pvsym.hip: the non-NULL 225-wide rows mapped back in place, row i by d_sym[i]
+int gz_internal_sym_rows(float* d_logits, float* d_probs, double* d_prior, int32_t n, const int32_t* d_count,
+                         const uint8_t* d_sym, void* stream);
 }  // extern "C"
 
 // The stages of gz_pv_forward_tree (gz_pvnet.hip) on the carved workspace t.  C++

@@ -171,6 +171,19 @@
 // Match workspace (gz_puct_match_workspace_bytes(n, S)): the self-play workspace of n slots,
 // then side i32 [n], row_of i32 [n], the counts (256 bytes) and per side the round buffers of
 // n rows (leaves, an unused active column, logits, probs, value, prior, the forward's scratch).
+//
+// Leaf symmetry (opt-in, GZ_PUCT_LEAF_SYM; gz_sym.h, gz_pvsym.hip, tests/puct_sym_ref.py):
+// every leaf is evaluated on its board under t = sym_of(seed, leaf row), one of the 8
+// symmetries, and the prior row is mapped back; the value is a scalar.  Two launches per
+// round around the forward, in all five paths:
+//   select / begin / round -> sym_leaves (leaf rows in place, t per row) -> gz_pv_forward
+//   -> sym_priors (the f64 prior rows in place) -> backup (the root noise as ever, on the
+//   mapped-back row);
+// the match turns the slot rows before the gather and maps the slot rows back after the
+// scatter, so both sides see the same t and a round still has two extra launches.  The
+// select, backup, re-root and compaction kernels do not know about it.  t lives behind the
+// flag-clear workspace: gz_puct_sym_bytes(rows) more bytes, touched only with the flag set.
+// The step API accepts the flag and ignores it (its caller evaluates: gz_pv_forward_sym).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -1621,6 +1634,35 @@ int backup_impl(void* ws, int32_t n, int32_t S, const double* d_prior, const flo
     return gz_check_launch("puct_backup_kernel");
 }
 
+// GZ_PUCT_LEAF_SYM (gz_sym.h, gz_pvsym.hip): t is the extra region behind the flag-clear
+// workspace, one byte per row of the round buffers; nullptr with the flag clear, and then
+// neither step launches anything.  sym_leaves turns the round's leaf rows in place -- the
+// select, begin and round kernels rewrite every row of every round and nothing but the
+// forward reads the buffer (the backup kernels take no leaf pointer; a node's board is in
+// its tree) -- and sym_priors maps the forward's prior rows back before the backup, which
+// reads nothing else of the 225-wide buffers.
+struct LeafSym {
+    uint8_t* t;
+    uint64_t seed;
+};
+
+LeafSym leaf_sym(const gz_puct_params* p, void* ws, size_t flag_clear_bytes) {
+    LeafSym ls;
+    ls.t = (p->flags & GZ_PUCT_LEAF_SYM) ? (uint8_t*)ws + flag_clear_bytes : nullptr;
+    ls.seed = p->seed;
+    return ls;
+}
+
+int sym_leaves(const LeafSym& ls, uint32_t* leaves, int32_t rows, void* stream) {
+    if (!ls.t) return GZ_OK;
+    return gz_internal_sym_boards(leaves, leaves, rows, nullptr, nullptr, ls.seed, ls.t, stream);
+}
+
+int sym_priors(const LeafSym& ls, double* prior, int32_t rows, void* stream) {
+    if (!ls.t) return GZ_OK;
+    return gz_internal_sym_rows(nullptr, nullptr, prior, rows, nullptr, ls.t, stream);
+}
+
 struct RoundBufs {
     uint32_t* leaves;
     int32_t* active;
@@ -1743,6 +1785,7 @@ int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids,
     const int S = p->num_simulations;
     const BatchBufs b = carve_batch(ws, n_cap, S, K);
     const RoundBufs& r = b.r;
+    const LeafSym ls = leaf_sym(p, ws, gz_puct_batch_workspace_bytes(n_cap, S, K));
     hipStream_t st = as_stream(stream);
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
@@ -1758,8 +1801,12 @@ int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids,
                 if (rc) return rc;
             }
             root = false;
+            rc = sym_leaves(ls, r.leaves, n * K, stream);
+            if (rc) return rc;
             rc = gz_pv_forward(d_pv_weights, r.leaves, n * K, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
                                p->precision, stream);
+            if (rc) return rc;
+            rc = sym_priors(ls, r.prior, n * K, stream);
             if (rc) return rc;
             rc = backup_batch_impl(ws, n_cap, n, S, K, r.prior, r.value, nz, stream);
             if (rc) return rc;
@@ -1793,6 +1840,7 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
     }
     const int S = p->num_simulations;
     const RoundBufs r = carve_rounds(ws, n_cap, S);
+    const LeafSym ls = leaf_sym(p, ws, gz_puct_workspace_bytes(n_cap, S));
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
     if (rc) return rc;
@@ -1803,8 +1851,12 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
             rc = gz_puct_select(ws, n, S, r.leaves, r.active, stream);
             if (rc) return rc;
         }
+        rc = sym_leaves(ls, r.leaves, n, stream);
+        if (rc) return rc;
         rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
                            p->precision, stream);
+        if (rc) return rc;
+        rc = sym_priors(ls, r.prior, n, stream);
         if (rc) return rc;
         rc = backup_impl(ws, n, S, r.prior, r.value, nz, stream);
         if (rc) return rc;
@@ -1910,6 +1962,7 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
     const int S = p->num_simulations;
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
     const RoundBufs r = carve_rounds(w.puct, n_slots, S);
+    const LeafSym ls = leaf_sym(p, w.puct, gz_puct_workspace_bytes(n_slots, S));
     hipStream_t st = as_stream(stream);
     PuctNoise nz;
     rc = read_noise(who, p, nz);
@@ -1928,8 +1981,12 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
         puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, cap, (char*)w.puct, r.leaves, r.active);
         rc = gz_check_launch("puct_round_kernel");
         if (rc) return rc;
+        rc = sym_leaves(ls, r.leaves, n, stream);
+        if (rc) return rc;
         rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
                            p->precision, stream);
+        if (rc) return rc;
+        rc = sym_priors(ls, r.prior, n, stream);
         if (rc) return rc;
         rc = backup_impl(w.puct, n, S, r.prior, r.value, nz, stream);
         if (rc) return rc;
@@ -1994,6 +2051,8 @@ int match_impl(void* d_slots, int32_t n_slots, int32_t n, const gz_puct_match_pa
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
     const RoundBufs r = carve_rounds(w.puct, n_slots, S);
     const MatchWs m = carve_match(d_workspace, n_slots, S);
+    // (both sides under the same t: the slot rows turn before the gather and back after the scatter)
+    const LeafSym ls = leaf_sym(p, d_workspace, gz_puct_match_workspace_bytes(n_slots, S));
     hipStream_t st = as_stream(stream);
     for (int it = 0; it < n_plies; it++) {
         rc = gz_selfplay_boards(d_slots, n, S, w.boards, w.gids, stream);
@@ -2009,6 +2068,8 @@ int match_impl(void* d_slots, int32_t n_slots, int32_t n, const gz_puct_match_pa
                 rc = gz_puct_select(w.puct, n, S, r.leaves, r.active, stream);
                 if (rc) return rc;
             }
+            rc = sym_leaves(ls, r.leaves, n, stream);
+            if (rc) return rc;
             puct_match_gather_kernel<<<(n * 4 + 255) / 256, 256, 0, st>>>(r.leaves, n, m.side, m.row_of,
                                                                           m.pk[0].leaves, m.pk[1].leaves);
             rc = gz_check_launch("puct_match_gather_kernel");
@@ -2022,6 +2083,8 @@ int match_impl(void* d_slots, int32_t n_slots, int32_t n, const gz_puct_match_pa
             puct_match_scatter_kernel<<<(n + 3) / 4, 256, 0, st>>>(n, m.side, m.row_of, m.pk[0].prior, m.pk[1].prior,
                                                                    m.pk[0].value, m.pk[1].value, r.prior, r.value);
             rc = gz_check_launch("puct_match_scatter_kernel");
+            if (rc) return rc;
+            rc = sym_priors(ls, r.prior, n, stream);
             if (rc) return rc;
             rc = backup_impl(w.puct, n, S, r.prior, r.value, nz, stream);
             if (rc) return rc;
@@ -2090,6 +2153,8 @@ int gz_puct_remaining(void* d_workspace, int32_t n, int32_t S, int32_t* d_remain
                                                                          nullptr);
     return gz_check_launch("puct_remaining_kernel");
 }
+
+size_t gz_puct_sym_bytes(int32_t rows) { return al256((size_t)(rows < 1 ? 1 : rows)); }
 
 size_t gz_puct_batch_workspace_bytes(int32_t n, int32_t S, int32_t K) {
     if (n < 1) n = 1;

@@ -23,6 +23,7 @@ GZ_AUG_FIX_LABELS = 1
 GZ_PUCT_ROOT_NOISE = 1  # gz_puct_params.flags: the params are a gz_puct_noise_params
 GZ_PUCT_LEAF_BATCH = 2  # gz_puct_params.flags: the params are a gz_puct_batch_params
 GZ_PUCT_PLAYOUT_CAP = 4  # gz_puct_params.flags: the params are a gz_puct_cap_params
+GZ_PUCT_LEAF_SYM = 8  # gz_puct_params.flags: every leaf is evaluated under a board symmetry (no struct of its own)
 GZ_PUCT_MAX_LEAVES = 32
 
 
@@ -173,6 +174,10 @@ SIGNATURES = {
     "gz_pv_weight_floats": (_SZ, []),
     "gz_pv_workspace_bytes": (_SZ, [_I32]),
     "gz_pv_forward": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "gz_pv_sym": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, _P, _P]),
+    "gz_pv_sym_host": (ctypes.c_int, [ctypes.c_uint64, _P]),
+    "gz_pv_sym_workspace_bytes": (_SZ, [_I32]),
+    "gz_pv_forward_sym": (ctypes.c_int, [_P, _P, _I32, _P, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _I32, _P]),
     "gz_pv_tree_workspace_bytes": (_SZ, [_I32, _I32]),
     "gz_pv_forward_tree": (ctypes.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "gz_pv_tree_stats": (ctypes.c_int, [_P, _I32, _P, _P]),
@@ -216,6 +221,7 @@ SIGNATURES = {
     "gz_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "gz_selfplay_puct_batch_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "gz_puct_remaining": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
+    "gz_puct_sym_bytes": (_SZ, [_I32]),
     "gz_puct_match_workspace_bytes": (_SZ, [_I32, _I32]),
     "gz_puct_match_run": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(PuctMatchParams), _P, _I32, _P, _I32, _P, _P,
                                          _P]),

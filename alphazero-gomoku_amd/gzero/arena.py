@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .boards import RECORD_DTYPE, STATE_DTYPE
-from .device import PVWeights, ptr, puct_params, require_gpu, stream
+from .device import PVWeights, ptr, puct_params, puct_sym_bytes, require_gpu, stream
 from .selfplay import COUNTER_DTYPE
 
 TALLY_FIELDS = ("games", "a_wins", "b_wins", "draws", "a_wins_black", "a_wins_white", "b_wins_black",
@@ -41,11 +41,12 @@ class PuctMatch:
     the id game_id_base + i * game_id_stride.  :meth:`step` plays plies and tallies the games
     they finished; :meth:`run` steps (compacting the live slots to the front after every
     step unless compact=False) until every game is over.  dirichlet_alpha: root noise as in
-    SelfPlayEngine (None: none)."""
+    SelfPlayEngine (None: none).  leaf_symmetry: every leaf under a board symmetry picked by
+    (seed, position), the same for both sides (GZ_PUCT_LEAF_SYM; default off)."""
 
     def __init__(self, weights_a, weights_b, games, num_simulations=200, c_puct=1.6, temp_plies=8, seed=0,
                  dirichlet_alpha=None, noise_eps=0.25, game_id_base=0, a_black_parity=0, game_id_stride=1,
-                 compact=True):
+                 compact=True, leaf_symmetry=False):
         self.lib = require_gpu()
         if not isinstance(weights_a, PVWeights) or not isinstance(weights_b, PVWeights):
             raise ValueError("a match needs two PVWeights")
@@ -59,7 +60,8 @@ class PuctMatch:
         self.base = int(game_id_base)
         self.weights = (weights_a, weights_b)
         # (the precision field of the shared params is not read by a match)
-        self.search = puct_params(num_simulations, c_puct, temp_plies, seed, "f16x3", dirichlet_alpha, noise_eps)
+        self.search = puct_params(num_simulations, c_puct, temp_plies, seed, "f16x3", dirichlet_alpha, noise_eps,
+                                  leaf_symmetry=leaf_symmetry)
         S = self.S = self.search.num_simulations
         self.params = _lib.PuctMatchParams(
             ctypes.cast(ctypes.pointer(self.search), ctypes.c_void_p),
@@ -71,7 +73,8 @@ class PuctMatch:
         # (gz_selfplay_init writes every slot's whole header; records and visit rows at or past
         # the counters' record count are not written and not read)
         self.d_slots = torch.empty(n * self.lib.gz_slot_bytes(S), dtype=torch.uint8, device="cuda")
-        self.d_ws = torch.empty(self.lib.gz_puct_match_workspace_bytes(n, S), dtype=torch.uint8, device="cuda")
+        self.d_ws = torch.empty(self.lib.gz_puct_match_workspace_bytes(n, S) + puct_sym_bytes(self.lib, n, self.search),
+                                dtype=torch.uint8, device="cuda")
         self.record_cap = n * _lib.GZ_MAX_GAME_PLIES  # one game per slot
         self.d_records = torch.empty(self.record_cap * RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self.d_visits = torch.empty(self.record_cap * 225, dtype=torch.int16, device="cuda")
@@ -113,10 +116,10 @@ class PuctMatch:
 
     def advance(self, n_plies):
         """Benchmark burn-in (as SelfPlayEngine.advance): n_plies plies at 8 simulations
-        without root noise, in the match's own workspace.  Games that end here are neither
-        tallied nor kept."""
+        without root noise (leaf_symmetry stays), in the match's own workspace.  Games that end
+        here are neither tallied nor kept."""
         p = _lib.PuctParams.from_buffer_copy(self.search)
-        p.flags = 0
+        p.flags &= _lib.GZ_PUCT_LEAF_SYM
         p.num_simulations = min(8, p.num_simulations)
         mp = _lib.PuctMatchParams.from_buffer_copy(self.params)
         mp.search = ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
@@ -230,7 +233,7 @@ def summarise(tally):
 
 def play_match(model_a, model_b, games=64, num_simulations=200, c_puct=1.6, temp_plies=8, seed=0, precision_a=None,
                precision_b=None, dirichlet_alpha=None, noise_eps=0.25, game_id_base=0, return_games=False,
-               a_black_parity=None, plies_per_step=1):
+               a_black_parity=None, plies_per_step=1, leaf_symmetry=False):
     """A match of ``games`` games between two models (GomokuModel: the blobs are
     model.device_weights(precision), None = the model's own precision), colours alternating
     by game: A is black in the first game (a_black_parity None = game_id_base & 1).  Returns
@@ -242,7 +245,7 @@ def play_match(model_a, model_b, games=64, num_simulations=200, c_puct=1.6, temp
     parity = int(game_id_base) & 1 if a_black_parity is None else int(a_black_parity)
     m = PuctMatch(wa, wb, games, num_simulations=num_simulations, c_puct=c_puct, temp_plies=temp_plies, seed=seed,
                   dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, game_id_base=game_id_base,
-                  a_black_parity=parity)
+                  a_black_parity=parity, leaf_symmetry=leaf_symmetry)
     out = summarise(m.run(plies_per_step))
     out["precisions"] = (wa.precision, wb.precision)
     if return_games:

@@ -217,6 +217,72 @@ def pv_forward(weights, leaf_rows, want_prior=False):
     return out
 
 
+def pv_sym(rows, seed):
+    """t uint8 [n] of gz_pv_sym: the board symmetry (0..7, t = 2 k + f) under which the
+    leaf-symmetry search evaluates each [16] uint32 row -- a function of (seed, row) alone."""
+    lib = require_gpu()
+    rows = np.ascontiguousarray(rows, np.uint32).reshape(-1, 16)
+    n = rows.shape[0]
+    d_b = torch.from_numpy(rows.view(np.int32).copy()).cuda()
+    d_t = torch.empty(max(1, n), dtype=torch.uint8, device="cuda")
+    _lib.check(lib.gz_pv_sym(ptr(d_b), n, int(seed) & ((1 << 64) - 1), ptr(d_t), stream()), "gz_pv_sym")
+    return d_t.cpu().numpy()[:n]
+
+
+def pv_sym_host(seed, row):
+    """gz_pv_sym_host: the same for one row, on the host (no GPU)."""
+    row = np.ascontiguousarray(row, np.uint32)
+    if row.shape != (16,):
+        raise ValueError("row must have 16 words")
+    return int(_lib.load().gz_pv_sym_host(int(seed) & ((1 << 64) - 1), row.ctypes.data))
+
+
+def _sym_workspace(weights, n):
+    need = _lib.load().gz_pv_sym_workspace_bytes(int(max(1, n)))
+    if weights.workspace.numel() < need:
+        weights.workspace = torch.empty(need, dtype=torch.uint8, device="cuda")
+    return weights.workspace
+
+
+def pv_forward_sym_dev(weights, d_boards, n, d_sym=None, seed=0, d_count=None, d_logits=None, d_value=None,
+                       d_probs=None, d_prior=None):
+    """pv_forward_dev under a board symmetry per row (gz_pv_forward_sym): d_sym uint8 [n]
+    on the device, or None for gz_pv_sym(seed, row).  The 225-wide outputs come back in the
+    boards' own frame; d_boards is not modified."""
+    lib = require_gpu()
+    if d_logits is None:
+        d_logits = torch.empty(n * 225, dtype=torch.float32, device="cuda")
+    if d_value is None:
+        d_value = torch.empty(n, dtype=torch.float32, device="cuda")
+    _lib.check(lib.gz_pv_forward_sym(ptr(weights.tensor), ptr(d_boards), int(n), ptr(d_count), ptr(d_sym),
+                                     int(seed) & ((1 << 64) - 1), ptr(d_logits), ptr(d_value), ptr(d_probs),
+                                     ptr(d_prior), ptr(_sym_workspace(weights, n)), weights.mode, stream()),
+               "gz_pv_forward_sym")
+    return d_logits, d_value, d_probs
+
+
+def pv_forward_sym(weights, leaf_rows, sym=None, seed=0, want_prior=False):
+    """pv_forward under a board symmetry per row: sym uint8 [n] (t = 2 k + f), or None for
+    the transform the leaf-symmetry search picks, pv_sym(rows, seed)."""
+    rows = np.ascontiguousarray(leaf_rows, np.uint32).reshape(-1, 16)
+    n = rows.shape[0]
+    d_b = torch.from_numpy(rows.view(np.int32).copy()).cuda()
+    d_sym = None
+    if sym is not None:
+        sym = np.ascontiguousarray(sym, np.uint8).reshape(-1)
+        if sym.shape[0] != n:
+            raise ValueError("sym wants one transform per row")
+        d_sym = torch.from_numpy(sym.copy()).cuda()
+    d_probs = torch.empty(n * 225, dtype=torch.float32, device="cuda")
+    d_prior = torch.empty(n * 225, dtype=torch.float64, device="cuda") if want_prior else None
+    lg, v, pr = pv_forward_sym_dev(weights, d_b, n, d_sym=d_sym, seed=seed, d_probs=d_probs, d_prior=d_prior)
+    torch.cuda.synchronize()
+    out = (lg.cpu().numpy().reshape(n, 225), v.cpu().numpy(), pr.cpu().numpy().reshape(n, 225))
+    if want_prior:
+        out += (d_prior.cpu().numpy().reshape(n, 225),)
+    return out
+
+
 def pv_forward_tree(weights, leaf_rows, meta, root_cap=None, d_count=None):
     """Host convenience for gz_pv_forward_tree: [n,16] uint32 leaf rows and their
     int32 meta (-1 root, >= 0 the parent's index for a root child or a child of
@@ -330,7 +396,7 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 
 # ---------------------------------------------------------------- PUCT search
 def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
-                noise_eps=0.25, leaves_per_round=1, fast_simulations=None, full_prob=0.25):
+                noise_eps=0.25, leaves_per_round=1, fast_simulations=None, full_prob=0.25, leaf_symmetry=False):
     """gz_puct_params; precision ("fp32" / "f16x3" / "f16") is the forward gz_puct_search runs.
     dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
     noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
@@ -343,7 +409,15 @@ def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision
     GZ_PUCT_PLAYOUT_CAP set): every ply is a full search of num_simulations with
     probability full_prob, else a fast one of F simulations without root noise
     (include/gzero.h).  None (the default): no cap, full_prob is not read.  Not with
-    leaves_per_round > 1."""
+    leaves_per_round > 1.
+    leaf_symmetry: every leaf is evaluated under one of the 8 board symmetries, picked by
+    (seed, position), and its prior mapped back (GZ_PUCT_LEAF_SYM; the struct is the one
+    the other options give).  False (the default): the flag is clear."""
+    if leaf_symmetry:
+        p = puct_params(num_simulations, c_puct, temp_plies, seed, precision, dirichlet_alpha, noise_eps,
+                        leaves_per_round, fast_simulations, full_prob)
+        p.flags |= _lib.GZ_PUCT_LEAF_SYM
+        return p
     if fast_simulations is not None:
         return _with_cap(puct_params(num_simulations, c_puct, temp_plies, seed, precision, dirichlet_alpha, noise_eps,
                                      leaves_per_round), fast_simulations, full_prob)
@@ -377,9 +451,10 @@ def _with_cap(params, fast_simulations, full_prob):
     if not 0.0 <= prob <= 1.0:  # (a NaN fails both)
         raise ValueError(f"full_prob must be in [0, 1], not {full_prob!r}")
     noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
+    sym = params.flags & _lib.GZ_PUCT_LEAF_SYM
     alpha, eps = (params.noise_alpha, params.noise_eps) if noise else (0.0, 0.0)
     return _lib.PuctCapParams(params.num_simulations, params.temp_plies, params.c_puct, params.seed, params.precision,
-                              noise | _lib.GZ_PUCT_PLAYOUT_CAP, alpha, eps, 1, 0, F, 0, prob)
+                              noise | sym | _lib.GZ_PUCT_PLAYOUT_CAP, alpha, eps, 1, 0, F, 0, prob)
 
 
 def cap_full(records_dev, seed, full_prob):
@@ -415,19 +490,26 @@ def with_leaves(params, leaves_per_round):
     if params.flags & _lib.GZ_PUCT_PLAYOUT_CAP:
         raise ValueError("leaves_per_round > 1 is not supported with fast_simulations (the playout cap)")
     noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
-    flags = noise | (_lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0)
+    sym = params.flags & _lib.GZ_PUCT_LEAF_SYM
+    flags = noise | sym | (_lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0)
     base = (params.num_simulations, params.temp_plies, params.c_puct, params.seed, params.precision)
     alpha, eps = (params.noise_alpha, params.noise_eps) if noise else (0.0, 0.0)
     if K > 1:
         return _lib.PuctBatchParams(*base, flags, alpha, eps, K, 0)
-    return _lib.PuctNoiseParams(*base, flags, alpha, eps) if noise else _lib.PuctParams(*base, 0)
+    return _lib.PuctNoiseParams(*base, flags, alpha, eps) if noise else _lib.PuctParams(*base, sym)
 
 
 def _puct_workspace_bytes(lib, n, params):
     # (an S out of range is the library's error to report: size the workspace for a legal one)
     S = max(0, min(params.num_simulations, _lib.GZ_MAX_SIMULATIONS))
     K = puct_leaves(params)
-    return lib.gz_puct_batch_workspace_bytes(n, S, K) if K else lib.gz_puct_workspace_bytes(n, S)
+    size = lib.gz_puct_batch_workspace_bytes(n, S, K) if K else lib.gz_puct_workspace_bytes(n, S)
+    return size + puct_sym_bytes(lib, n * max(1, K), params)
+
+
+def puct_sym_bytes(lib, rows, params):
+    """What GZ_PUCT_LEAF_SYM adds behind a flag-clear workspace (0 with the flag clear)."""
+    return lib.gz_puct_sym_bytes(int(rows)) if params.flags & _lib.GZ_PUCT_LEAF_SYM else 0
 
 
 def puct_root_noise(states, game_ids, seed, alpha):
@@ -573,6 +655,20 @@ class PuctStepper:
             raise ValueError("backup() wants prior float64 [n,225] and value float32 [n] (n K rows when batched)")
         _lib.check(self.lib.gz_puct_backup(ptr(self.ws), self.n, self.S, ptr(prior), ptr(value), stream()),
                    "gz_puct_backup")
+
+    def evaluate(self, weights):
+        """The current round's leaves through the network, for backup(): (prior, value)
+        device tensors.  With leaf_symmetry in params the step API leaves the transform to
+        its caller, so this is pv_forward_sym_dev with the params' seed; without it,
+        pv_forward_dev.  weights.mode is the precision (params.precision is not read)."""
+        d_probs = torch.empty(self.rows * 225, dtype=torch.float32, device="cuda")
+        d_prior = torch.empty(self.rows * 225, dtype=torch.float64, device="cuda")
+        if self.params.flags & _lib.GZ_PUCT_LEAF_SYM:
+            _, v, _ = pv_forward_sym_dev(weights, self.d_leaves, self.rows, seed=self.params.seed, d_probs=d_probs,
+                                         d_prior=d_prior)
+        else:
+            _, v, _ = pv_forward_dev(weights, self.d_leaves, self.rows, d_probs=d_probs, d_prior=d_prior)
+        return d_prior, v
 
     def finish(self):
         d_moves = torch.empty(self.n, dtype=torch.int32, device="cuda")

@@ -16,7 +16,8 @@ import torch
 
 from . import _lib
 from .boards import RECORD_DTYPE, STATE_DTYPE, words_to_cells
-from .device import GNWeights, PVWeights, ptr, puct_leaves, puct_params, require_gpu, search_params, stream
+from .device import (GNWeights, PVWeights, ptr, puct_leaves, puct_params, puct_sym_bytes, require_gpu, search_params,
+                     stream)
 
 COUNTER_DTYPE = np.dtype([("records", "<i4"), ("leaves", "<i4"), ("records_dropped", "<i4"),
                           ("leaves_dropped", "<i4"), ("moves", "<i8"), ("games", "<i8"),
@@ -29,7 +30,7 @@ class SelfPlayEngine:
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
                  rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1,
-                 compact_slots=False, fast_simulations=None, full_prob=0.25):
+                 compact_slots=False, fast_simulations=None, full_prob=0.25, leaf_symmetry=False):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -66,6 +67,11 @@ class SelfPlayEngine:
         budget; the lock-step engine accepts the cap and gains nothing (every ply costs
         num_simulations + 1 rounds).  rounds_per_step keeps its default.  Not with
         leaves_per_round > 1.
+        leaf_symmetry (search="puct" only; default False): every leaf is evaluated under one
+        of the 8 board symmetries, picked by (seed, position), and its prior mapped back
+        (GZ_PUCT_LEAF_SYM, include/gzero.h), so the network's orientation bias averages out
+        over a search.  Lock-step and tree_reuse alike, with every other option; the burn-in
+        of :meth:`advance` keeps it.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -101,6 +107,9 @@ class SelfPlayEngine:
                 raise ValueError("fast_simulations needs search='puct'")
             if self.leaves_per_round > 1:
                 raise ValueError("fast_simulations (the playout cap) is not supported with leaves_per_round > 1")
+        self.leaf_symmetry = bool(leaf_symmetry)
+        if self.leaf_symmetry and search != "puct":
+            raise ValueError("leaf_symmetry needs search='puct'")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -152,10 +161,13 @@ class SelfPlayEngine:
         self.puct = self.d_puct_ws = self.d_visits = None
         if search == "puct":
             self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision, dirichlet_alpha,
-                                    noise_eps, self.leaves_per_round, fast_simulations, full_prob)
+                                    noise_eps, self.leaves_per_round, fast_simulations, full_prob,
+                                    self.leaf_symmetry)
             K = puct_leaves(self.puct)
             nbytes = self.lib.gz_selfplay_puct_batch_workspace_bytes(self.n_slots, S, K) if K else \
                 self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S)
+            # (the transform of every round row, behind the flag-clear workspace)
+            nbytes += puct_sym_bytes(self.lib, self.n_slots * max(1, K), self.puct)
             self.d_puct_ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
             # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
             # has no uint16 arithmetic; a count is at most GZ_MAX_SIMULATIONS)
@@ -301,7 +313,7 @@ class SelfPlayEngine:
         if self.search == "puct":
             # (the 32 bytes of the base struct: the burn-in has no root noise, no playout cap and
             # one leaf per round, so the flags that would make the library read past the copy are
-            # cleared)
+            # cleared; leaf_symmetry has no struct of its own and stays: the burn-in is a search too)
             p = _lib.PuctParams.from_buffer_copy(self.puct)
             p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH | _lib.GZ_PUCT_PLAYOUT_CAP)
             p.num_simulations = min(8, p.num_simulations)

@@ -250,7 +250,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          n_slots: int = 4096, game_id_base: int = 0, model=None, temp_plies: int = 8,
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                          noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True,
-                         pv_weights=None, fast_simulations: Optional[int] = None, full_prob: float = 0.25):
+                         pv_weights=None, fast_simulations: Optional[int] = None, full_prob: float = 0.25,
+                         leaf_symmetry: bool = False):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -279,6 +280,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     without noise.  The rows and visit rows of all plies are returned as ever;
     stats["full_records"] counts the full plies among them (gz_puct_cap_full; without the
     cap, all of them), the ones run_iteration trains on.
+    leaf_symmetry: every leaf is evaluated under a board symmetry picked by (seed, position)
+    (SelfPlayEngine(leaf_symmetry=True)); off by default.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -291,7 +294,7 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
                          dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round,
                          game_id_end=game_id_base + n_games if compact else None, compact_slots=bool(compact),
-                         fast_simulations=fast_simulations, full_prob=full_prob)
+                         fast_simulations=fast_simulations, full_prob=full_prob, leaf_symmetry=leaf_symmetry)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -505,7 +508,7 @@ def evaluate_model(current, baseline, device=None, games: int = 8, eval_difficul
     search instead (gzero.arena.play_match: ``eval_num_sim`` simulations, the difficulty's
     c_puct, colours alternating, ``current`` black in the first game); it needs a baseline
     -- a random opponent is not a network -- and ``puct`` holds further play_match
-    keywords (temp_plies, precision_a, precision_b, dirichlet_alpha, noise_eps)."""
+    keywords (temp_plies, precision_a, precision_b, dirichlet_alpha, noise_eps, leaf_symmetry)."""
     if search != "reference":
         return _evaluate_puct(current, baseline, search, games, eval_difficulty, eval_num_sim, seed, return_games,
                               alternate, game_id_base, puct)
@@ -641,7 +644,7 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                   noise_eps: float = 0.25, leaves_per_round: int = 1,
                   selfplay_precision: Optional[str] = None, fast_simulations: Optional[int] = None,
-                  full_prob: float = 0.25) -> dict:
+                  full_prob: float = 0.25, leaf_symmetry: bool = False) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -664,7 +667,10 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     self-play (selfplay_puct_device).  Only the full plies are trained on: their records
     and visit rows are selected on the device (gz_puct_cap_full's mask) before the dataset
     is built, so policy and value targets both come from full searches.  ``records`` is
-    then the count kept and ``records_played`` the count of all plies."""
+    then the count kept and ``records_played`` the count of all plies.
+    ``leaf_symmetry`` (search="puct"): self-play evaluates every leaf under a random board
+    symmetry (selfplay_puct_device), which averages the network's orientation bias out of the
+    visit distributions it then trains on."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     from gzero.weights import PRECISIONS
@@ -681,6 +687,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError("leaves_per_round needs search='puct'")
     if fast_simulations is not None and search != "puct":
         raise ValueError("fast_simulations needs search='puct'")
+    if leaf_symmetry and search != "puct":
+        raise ValueError("leaf_symmetry needs search='puct'")
     if selfplay_precision is not None:
         if search != "puct":
             raise ValueError("selfplay_precision needs search='puct'")
@@ -697,7 +705,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                                                    dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
                                                    leaves_per_round=leaves_per_round,
                                                    pv_weights=model.device_weights(selfplay_precision),
-                                                   fast_simulations=fast_simulations, full_prob=full_prob)
+                                                   fast_simulations=fast_simulations, full_prob=full_prob,
+                                                   leaf_symmetry=leaf_symmetry)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -783,7 +792,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
          num_simulations: int = 200, planner_steps: int = 5, eval_games: int = 6, search: str = "reference",
          temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
          leaves_per_round: int = 1, selfplay_precision: Optional[str] = None, arena_search: str = "reference",
-         tree_reuse: bool = False, fast_simulations: Optional[int] = None, full_prob: float = 0.25):
+         tree_reuse: bool = False, fast_simulations: Optional[int] = None, full_prob: float = 0.25,
+         leaf_symmetry: bool = False):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -797,6 +807,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     model itself stays f16x3.  ``fast_simulations`` / ``full_prob``: playout cap
     randomization in self-play, training on the full plies only (run_iteration); it pays
     with ``tree_reuse=True``, the own-clock engine, where a fast ply costs fewer rounds.
+    ``leaf_symmetry=True``: self-play and the PUCT arena evaluate every leaf under a random
+    board symmetry (run_iteration, evaluate_model(puct={"leaf_symmetry": True})).
     ``arena_search="puct"``: rank 0's per-iteration arena is a device-side match of the
     network-guided search between the model and the best snapshot
     (evaluate_model(search="puct"), colours alternating), so the win rate printed depends
@@ -810,6 +822,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
         raise ValueError("selfplay_precision needs search='puct'")
     if (tree_reuse or fast_simulations is not None) and search != "puct":
         raise ValueError("tree_reuse and fast_simulations need search='puct'")
+    if leaf_symmetry and search != "puct":
+        raise ValueError("leaf_symmetry needs search='puct'")
     if arena_search not in ("reference", "puct"):
         raise ValueError(f"arena_search must be 'reference' or 'puct', not {arena_search!r}")
     rank, ws = gdist.init_from_env()
@@ -830,7 +844,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
                             planner_steps=planner_steps, seed=seed, verbose=rank == 0, search=search,
                             temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
                             leaves_per_round=leaves_per_round, selfplay_precision=selfplay_precision,
-                            tree_reuse=tree_reuse, fast_simulations=fast_simulations, full_prob=full_prob)
+                            tree_reuse=tree_reuse, fast_simulations=fast_simulations, full_prob=full_prob,
+                            leaf_symmetry=leaf_symmetry)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")
@@ -857,7 +872,7 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
             # which shows the first-move advantage only)
             rival = previous_best if previous_best is not None else best_snapshot
             stats = _rng_isolated(evaluate_model, model, rival, games=eval_games, seed=seed + it, search="puct",
-                                  puct={"temp_plies": temp_plies}) if rank == 0 and rival is not None else {}
+                                  puct={"temp_plies": temp_plies, "leaf_symmetry": leaf_symmetry}) if rank == 0 and rival is not None else {}
         else:
             stats = _rng_isolated(evaluate_model, model, best_snapshot, games=eval_games, seed=seed + it,
                                   alternate=False) if rank == 0 else {}

@@ -231,6 +231,30 @@ int gz_pv_forward(const float* d_weights, const uint32_t* d_boards, int32_t n, c
                   float* d_logits, float* d_value, float* d_probs, double* d_prior, void* d_workspace,
                   int32_t precision, void* stream);
 
+/* The forward under a board symmetry.  t = 2 k + f, k in 0..3 rotations, f in {0, 1}:
+ * y = flip^f(rot90^k(x)) -- np.rot90 (counter-clockwise), then np.flip along the columns,
+ * both colour planes together (training.py's _transform_planes) -- and a 225-wide row o_y
+ * computed on y goes back to x's frame as np.rot90(np.flip(o_y, 1) if f else o_y, -k);
+ * t = 0 is the identity.  gz_pv_sym: d_sym [n] uint8 = the transform of every row, a pure
+ * function of the seed and the row's 16 words (gzero/rng.py's mix64 / draw):
+ *   key = mix64(seed + GOLDEN); for i in 0..7: key = mix64(key ^ (row[i] | row[8+i] << 32))
+ *   t   = draw(key, 0x53594D4D) >> 61
+ * gz_pv_sym_host: one row by the same code on the host, no GPU, 0..7.
+ * gz_pv_forward_sym is gz_pv_forward of the transformed boards with every non-NULL
+ * 225-wide output (logits, probs, prior) mapped back and the value as it is: the prior is
+ * the row gz_pv_forward gives for y (renormalised in y's cell order), permuted, not a prior
+ * recomputed in x's order.  d_sym not NULL: row i uses d_sym[i] & 7 and the seed is not
+ * read; d_sym NULL: row i uses gz_pv_sym's t.  d_boards is not modified; rows at or past
+ * min(*d_count, n) are not written.  d_workspace: gz_pv_sym_workspace_bytes(n) =
+ * gz_pv_workspace_bytes(n), the transformed boards (64 n) and one byte per row, each
+ * rounded up to 256.  Argument errors as gz_pv_forward, before any launch. */
+int gz_pv_sym(const uint32_t* d_boards, int32_t n, uint64_t seed, uint8_t* d_sym, void* stream);
+int gz_pv_sym_host(uint64_t seed, const uint32_t row[16]);
+size_t gz_pv_sym_workspace_bytes(int32_t n);
+int gz_pv_forward_sym(const float* d_weights, const uint32_t* d_boards, int32_t n, const int32_t* d_count,
+                      const uint8_t* d_sym, uint64_t seed, float* d_logits, float* d_value, float* d_probs,
+                      double* d_prior, void* d_workspace, int32_t precision, void* stream);
+
 /* Incremental forward of the nodes of MCTS searches (MCTSNode.__init__ ->
  * GomokuModel.predict, ai_agent.py:522-523; neural_network.py:132-159), f16x3:
  * d_meta as written by gz_selfplay_run.  Roots and untagged nodes run the full
@@ -352,7 +376,7 @@ typedef struct gz_puct_params {
     double c_puct;
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
     int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3 / GZ_PV_F16: the forward of every search and self-play entry */
-    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP */
+    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP | GZ_PUCT_LEAF_SYM */
 } gz_puct_params;
 /* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).
  * With GZ_PUCT_ROOT_NOISE in flags the p given to gz_puct_begin, gz_puct_search,
@@ -467,6 +491,26 @@ typedef struct gz_puct_cap_params {
 int gz_puct_cap_full(const gz_record* d_records, int32_t n, uint64_t seed, double full_prob, uint8_t* d_full,
                      void* stream);
 int gz_puct_cap_full_host(uint64_t seed, int64_t game_id, int32_t ply, double full_prob);
+/* Leaf symmetry (opt-in; AlphaGo Zero's random board symmetry per leaf evaluation): with
+ * GZ_PUCT_LEAF_SYM in flags every leaf x is evaluated as
+ *   t = gz_pv_sym(seed, x);  (prior_y, value) = gz_pv_forward(T_t(x));  prior[c] mapped back
+ * (gz_pv_forward_sym below, with d_sym NULL and seed = p->seed, is exactly that), at the
+ * search's precision.  No new params struct: the seed is gz_puct_params.seed, and the flag
+ * combines with GZ_PUCT_ROOT_NOISE, GZ_PUCT_LEAF_BATCH and GZ_PUCT_PLAYOUT_CAP wherever those
+ * combine; without it every entry point computes what it did before.  t is a function of
+ * the seed and the position alone -- not of the game, the ply or the row -- so a position
+ * met twice is evaluated the same way, tree reuse and compaction carry valid evaluations
+ * and the step API's caller needs no state.  Root noise is mixed into the mapped-back row.
+ * Honoured by gz_puct_search (also batched), gz_selfplay_puct_run(_active),
+ * gz_selfplay_puct_rounds(_active) and gz_puct_match_run (both sides under the same t).
+ * The step API (gz_puct_begin / select / backup / reroot / finish) accepts the flag and does
+ * nothing with it: there the caller is the evaluator and calls gz_pv_forward_sym itself.
+ * Workspace: the *_workspace_bytes functions return what they did; with the flag set the
+ * caller allocates that size plus gz_puct_sym_bytes(rows), rows = n K (gz_puct_search) or
+ * n_slots K (self-play, the match: K = 1), and the extra region starts at the flag-clear
+ * size.  With the flag clear nothing past the flag-clear size is touched. */
+#define GZ_PUCT_LEAF_SYM 8
+size_t gz_puct_sym_bytes(int32_t rows);
 /* includes the forward's workspace and gz_puct_search's leaf / output rows */
 size_t gz_puct_workspace_bytes(int32_t n, int32_t num_simulations);
 size_t gz_puct_batch_workspace_bytes(int32_t n, int32_t num_simulations, int32_t leaves_per_round);

@@ -41,6 +41,14 @@ noise on and off.
     python tools/puct_bench.py --noise 0.3,0.25 --reuse --precisions f16x3 --steps 5 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/noise_bench.json
 
+--sym measures the leaf symmetry (SelfPlayEngine(leaf_symmetry=True)) the way --noise
+measures the noise: three child processes -- the parent build, this build with the flag
+clear, this build with the flag set -- take turns at one timed step each, lock-step and
+with --reuse; then the orientation dependence of the search (orientation_dependence).
+
+    python tools/puct_bench.py --sym --reuse --precision f16x3 --steps 5 \\
+        --lockstep-library parent/libgzero.so --out profiles/puct/sym_bench.json
+
 --leaves K,K,... measures leaf batching with virtual loss (SelfPlayEngine(leaves_per_round=K))
 at small slot counts: for every count of --sweep-slots two child processes -- this build with
 one engine per K, and --lockstep-library (a build of the parent commit, which has no K > 1: the
@@ -124,6 +132,10 @@ ap.add_argument("--noise", default=None, metavar="ALPHA,EPS", help="measure the 
 ap.add_argument("--distinct-plies", type=int, default=8, help="--noise: plies of the distinct-positions count")
 ap.add_argument("--noise-child", default=None, metavar="MODE:NOISE",
                 help="(child) lockstep or reuse, then off or ALPHA,EPS: time steps on request")
+ap.add_argument("--sym", action="store_true", help="measure the leaf symmetry (see above)")
+ap.add_argument("--sym-child", default=None, metavar="MODE:on|off",
+                help="(child) one engine of --sym: lockstep or reuse, with or without leaf_symmetry")
+ap.add_argument("--sym-positions", type=int, default=64, help="--sym: positions of the orientation measurement")
 ap.add_argument("--leaves", default=None, metavar="K,K,...",
                 help="measure leaf batching (SelfPlayEngine(leaves_per_round=K)) over --sweep-slots (see above)")
 ap.add_argument("--sweep-slots", default="1,8,64,256", help="--leaves: the slot counts (comma-separated)")
@@ -414,18 +426,25 @@ def noise_args(spec):
 
 
 def noise_child():
+    mode, spec = a.noise_child.split(":")
+    step_child(mode, noise_args(spec))
+
+
+def sym_child():
+    mode, spec = a.sym_child.split(":")
+    step_child(mode, {"leaf_symmetry": True} if spec == "on" else {})
+
+
+def step_child(mode, engine_kw):
     """Per line on stdin: one lock-step step (or one window of 2 x (S+1) rounds of a
     tree-reuse engine) timed with device events; its ms and moves on stdout."""
-    import ctypes
     import torch
-    from gzero import _lib
     from gzero.selfplay import SelfPlayEngine
-    have = bind_older_build()
-    mode, spec = a.noise_child.split(":")
+    bind_older_build()
     reuse = mode == "reuse"
     eng = SelfPlayEngine(n_slots=a.slots, num_simulations=a.sims, seed=1, pv_weights=bench_weights(precisions[0], 1.0),
                          search="puct", temp_plies=a.temp_plies, tree_reuse=reuse,
-                         rounds_per_step=2 * (a.sims + 1) if reuse else None, **noise_args(spec))
+                         rounds_per_step=2 * (a.sims + 1) if reuse else None, **engine_kw)
     eng.advance(a.burn)
     for _ in range(2 if reuse else 1):  # warm-up (with reuse 4 x (S+1) rounds: the clocks drift apart)
         eng.step()
@@ -445,10 +464,20 @@ def noise_child():
 
 
 def noise_mode_run(prec, mode):
+    kinds = [("parent", "off", a.lockstep_library), ("noise_off", "off", None), ("noise_on", a.noise, None)]
+    return three_way_run(prec, mode, "--noise-child", kinds, "noise")
+
+
+def sym_mode_run(prec, mode):
+    kinds = [("parent", "off", a.lockstep_library), ("sym_off", "off", None), ("sym_on", "on", None)]
+    return three_way_run(prec, mode, "--sym-child", kinds, "sym")
+
+
+def three_way_run(prec, mode, child_flag, kinds, what):
     """The three engines of one mode, taking turns: {name: per-step ms, moves, medians}."""
     S = a.sims
     rounds = 2 * (S + 1) if mode == "reuse" else S + 1
-    kinds = [("parent", "off", a.lockstep_library), ("noise_off", "off", None), ("noise_on", a.noise, None)]
+    off_name, on_name = kinds[1][0], kinds[2][0]
     kids = {}
     try:
         for name, spec, library in kinds:
@@ -456,7 +485,7 @@ def noise_mode_run(prec, mode):
             if library:
                 env["GZ_LIBRARY"] = os.path.abspath(library)
             kids[name] = subprocess.Popen(
-                [sys.executable, os.path.abspath(__file__), "--noise-child", f"{mode}:{spec}", "--slots", str(a.slots),
+                [sys.executable, os.path.abspath(__file__), child_flag, f"{mode}:{spec}", "--slots", str(a.slots),
                  "--sims", str(S), "--burn", str(a.burn), "--precisions", prec, "--temp-plies", str(a.temp_plies)],
                 env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
         for name, kid in kids.items():
@@ -482,11 +511,46 @@ def noise_mode_run(prec, mode):
         r["rounds_per_step"] = rounds
         r["round_ms_median"] = r["step_ms_median"] / rounds
     base = out["parent"]["round_ms_median"]
-    for name in ("noise_off", "noise_on"):
+    for name in (off_name, on_name):
         out[name]["round_ms_over_parent"] = out[name]["round_ms_median"] / base
-    print(f"{prec} {mode}: round ms parent {base:.4f}, noise off {out['noise_off']['round_ms_median']:.4f} "
-          f"(x{out['noise_off']['round_ms_over_parent']:.4f}), noise on {out['noise_on']['round_ms_median']:.4f} "
-          f"(x{out['noise_on']['round_ms_over_parent']:.4f})")
+    print(f"{prec} {mode}: round ms parent {base:.4f}, {what} off {out[off_name]['round_ms_median']:.4f} "
+          f"(x{out[off_name]['round_ms_over_parent']:.4f}), {what} on {out[on_name]['round_ms_median']:.4f} "
+          f"(x{out[on_name]['round_ms_over_parent']:.4f})")
+    return out
+
+
+def orientation_dependence(prec):
+    """Does the search depend on the board's orientation?  --sym-positions mid-game positions
+    (one per slot of a lock-step engine after --burn plies), each searched as it is and
+    rotated by 90 degrees (np.rot90 of the cells); the L1 distance between the visit
+    distribution of the position and the rotated image's distribution rotated back, with
+    the flag off and on (--sims simulations, temp_plies 0, init weights)."""
+    import numpy as np
+    from gzero import boards, device
+    from gzero.selfplay import SelfPlayEngine
+    n = a.sym_positions
+    w = bench_weights(prec, 1.0)
+    eng = SelfPlayEngine(n_slots=n, num_simulations=a.sims, seed=1, pv_weights=w, search="puct",
+                         temp_plies=a.temp_plies)
+    eng.advance(a.burn)
+    st, _ = eng.boards()
+    cells = boards.words_to_cells(st["black"], st["white"])
+    turned = np.stack([np.rot90(c.reshape(15, 15)).reshape(225) for c in cells])
+    st_t = boards.make_states(turned, n_moves=st["n_moves"], player=st["player"], over=st["over"],
+                              winner=st["winner"])
+    gids = list(range(n))
+    live = st["over"] == 0
+    out = {"positions": int(live.sum()), "plies": [int(x) for x in st["n_moves"][live]]}
+    for name, flag in (("sym_off", False), ("sym_on", True)):
+        p = device.puct_params(a.sims, 1.6, 0, 1, prec, leaf_symmetry=flag)
+        vis = device.puct_search(st, gids, p, w)[1].astype(np.float64)[live]
+        vis_t = device.puct_search(st_t, gids, p, w)[1].astype(np.float64)[live]
+        back = np.stack([np.rot90(v.reshape(15, 15), k=-1).reshape(225) for v in vis_t])
+        l1 = np.abs(vis / vis.sum(axis=1, keepdims=True) - back / back.sum(axis=1, keepdims=True)).sum(axis=1)
+        out[name] = {"l1_mean": float(l1.mean()), "l1_median": float(np.median(l1)), "l1_max": float(l1.max()),
+                     "same_move": int((vis.argmax(axis=1) == back.argmax(axis=1)).sum())}
+    print(f"{prec}: L1(visits, rotated-back visits of the rotated board) over {out['positions']} positions: "
+          f"{out['sym_off']['l1_mean']:.4f} without the flag, {out['sym_on']['l1_mean']:.4f} with")
     return out
 
 
@@ -809,6 +873,33 @@ if a.leaves:
     sys.exit(0)
 if a.noise_child is not None:
     noise_child()
+    sys.exit(0)
+if a.sym_child is not None:
+    sym_child()
+    sys.exit(0)
+if a.sym:
+    prec = precisions[0]
+    res = {"config": {"slots": a.slots, "simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies,
+                      "precision": prec, "steps": a.steps,
+                      "timing": "device events around one lock-step step (S+1 rounds) or one window of 2 x (S+1) "
+                                "rounds with tree reuse; three child processes (parent build, this build with the "
+                                "flag clear and with leaf_symmetry) take turns",
+                      "parent_library": "another build (--lockstep-library)" if a.lockstep_library else "this build"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    for mode in ("lockstep", "reuse") if a.reuse else ("lockstep",):
+        res["results"][mode] = sym_mode_run(prec, mode)
+    if a.sym_positions > 0:
+        res["results"]["orientation"] = orientation_dependence(prec)
+    import torch
+    res["device"] = torch.cuda.get_device_name(0)
+    print("PUCT_SYM_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.noise:
     prec = precisions[0]
