@@ -56,11 +56,10 @@ int gz_internal_sym_rows(float* d_logits, float* d_probs, double* d_prior, int32
 // gz_pvinc.hip: counters and lists (roots, full, children, grandchildren, patch slots)
 int gz_internal_tree_classify(const gzpv::TreeWs& t, const uint32_t* d_boards, const int32_t* d_meta, int32_t n,
                               const int32_t* d_count, int32_t root_cap, void* stream);
-// gz_pvinc.hip: the root children (gz_internal_tree_delta), then the grandchildren
-// through pv_sib_kernel
+// gz_pvinc.hip: the root children and the grandchildren (gz_internal_tree_delta)
 int gz_internal_tree_children(const gzpv::TreeWs& t, const float* d_weights, const uint32_t* d_boards,
                               const int32_t* d_meta, int32_t n, const int32_t* d_count, int grid, void* stream);
-// gz_pvdg.hip: the root children through pv_dg_kernel
+// gz_pvdg.hip: the root children, then the grandchildren, through pv_dg_kernel
 int gz_internal_tree_delta(const gzpv::TreeWs& t, const float* d_weights, const uint32_t* d_boards,
                            const int32_t* d_meta, int grid, void* stream);
 

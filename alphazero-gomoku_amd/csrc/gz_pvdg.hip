@@ -37,13 +37,23 @@
 // passes that read them -- except where the next pass is the next layer of the same
 // first nodes (y1 -> x1 of nodes 0-2, y2 -> x2 of node 2k): those squares go from the
 // epilogue straight into the next pass's LDS image.  A node with grandchildren also
-// writes its CHILD values into its patch slot for pv_sib_kernel (gz_pvinc.hip).
+// writes its pre-ReLU values of the squares (and x2's, radius 5) into its patch slot in
+// fp32, position-major: a lane's 8 channels are 32 contiguous bytes of a row.
+//
+// Grandchildren (OVERLAY instantiation, a second launch over t.grand): G = C + a stone
+// at m2, C = R + a stone at m1, evaluated as a delta of the parent C exactly as above,
+//     G(p) = relu(z_C(p) + s * sum_t W_t D(p + t) + D_skip(p)),   D_next = G - relu(z_C),
+// where z_C is C's patch row inside C's changed square (radius L + 2 around m1) and the
+// root's z elsewhere (fp32: a channel the ReLU clipped in C can be lifted by G's delta);
+// conv0's reference x0 is C's within radius 1 of m1; the record's base is C's record.
+// Everything else -- rows, classes, k-loop, fills, scratch, queue -- is the children's code.
 // A lane owns the 8 channels of one 16-byte slot of those layouts (dg_ch0 below), so
 // per row and plane each of these is ONE 16-byte access: the D store, the patch store,
 // the LDS hand-off write, the skip load and conv0's root-x0 load.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "gz_dgclass.h"
 #include "gz_internal.h"
@@ -129,11 +139,11 @@ constexpr int SCR_HALVES = (348 + 81) * 256;
 static_assert(348 + 3 * 25 <= 348 + 81 && 54 + 49 * 6 == 348, "scratch regions");
 
 struct DgUnit {
-    const _Float16* gm;  // the root's maps x0, y1, x1, y2 (hi / lo)
+    const _Float16* gm;  // the root's x0 map (hi / lo)
     const float* pre;    // the root's pre-ReLU values of y1, x1, y2, x2
     _Float16* own;       // the workgroup's scratch: this node's D square of map k at own + sq[k]
-    _Float16* patch;     // its patch slot (child values for its grandchildren), or nullptr
-    int leaf, base, cell, pad0;
+    float* patch;        // a child's own patch slot (or nullptr); a grandchild's PARENT's patch
+    int leaf, base, cell, pcell;  // node, record base (root / parent), stone; grandchild: the parent's stone
     int sq[4];           // halves offsets of its D squares x0 r1, y1 r2, x1 r3, y2 r4 (scr_sq)
     uint32_t board[16];  // the node's bit-plane board (conv0's input)
 };
@@ -147,7 +157,7 @@ struct DgArgs {
     const int32_t* pslot;
     const _Float16* maps;
     const float* pres;
-    _Float16* patches;
+    float* patches;
     float* hbuf;
     int32_t* tiles;  // += executed tile-taps (one 16-row tile x one tap x 128 x 128)
     int32_t* queue;  // [8] per-XCD chunk heads, zero at the launch
@@ -441,6 +451,11 @@ __device__ __forceinline__ void put_hl(_Float16* p, int plane_halves, const H8x2
     gst<h8>(p, x.h);
     gst<h8>(p + plane_halves, x.l);
 }
+// the lane's 8 channels in fp32 at p (a patch row: 32 contiguous bytes)
+__device__ __forceinline__ void put_f8(float* p, const f32x4 (&v)[2]) {
+    gst<f32x4>(p, v[0]);
+    gst<f32x4>(p + 4, v[1]);
+}
 // the same into LDS
 __device__ __forceinline__ void put_hl_lds(_Float16* p, int plane_halves, const H8x2& x) {
     *(h8*)p = x.h;
@@ -449,10 +464,13 @@ __device__ __forceinline__ void put_hl_lds(_Float16* p, int plane_halves, const 
 
 // The epilogue of a pass (layer L, nodes U[0, g), row table rt): per row,
 //   child = relu(z + s * acc + D_skip),  root = relu(z),  D = child - root
-// into the node's D square of map L + 1 (its patch: the child value); x2 reduces the
+// into the node's D square of map L + 1 (its patch: the pre-ReLU value); x2 reduces the
 // child values into the 1x1 heads' partial sums (hpart, per wave) instead.  Rows in
 // groups of GB tiles, loads ST - 1 groups ahead.
-template <int L>
+// OVERLAY (a grandchild, the delta of its parent): z is the parent's -- its patch row
+// inside its changed square (radius L + 2 around its stone), the root's elsewhere --
+// and nothing is written to a patch.
+template <int L, bool OVERLAY>
 __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const uint32_t* rt, int np, int lane,
                                             const f32x4 (&acc)[2][K::NMAX], int nt, int ldsg) {
     constexpr int RO = L + 2, SO = dg_so(L), SSO = SO * SO;
@@ -490,9 +508,15 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
             const int pos = v ? (cr + dy) * BN + (cc + dx) : 0;
             const bool near = SKIP && v && iabs(dy) <= RS && iabs(dx) <= RS;
             const int sidx = near ? (dy + RS) * SK + (dx + RS) : 0;
+            const float* zp = u.pre + L * PV_PRE_FLOATS + pos * CH;
+            if (OVERLAY) {
+                const int pcell = u.pcell, r1 = pcell / BN, c1 = pcell - (pcell / BN) * BN;
+                const int oy = cr + dy - r1, ox = cc + dx - c1;
+                if (v && iabs(oy) <= RO && iabs(ox) <= RO)
+                    zp = u.patch + (PATCH_POS[L + 1] + (oy + RO) * SO + (ox + RO)) * CH;
+            }
 #pragma unroll
-            for (int n = 0; n < 2; n++)
-                z[st][j][n] = gld<f32x4>(u.pre + L * PV_PRE_FLOATS + pos * CH + dg_ch0(np, q, n));
+            for (int n = 0; n < 2; n++) z[st][j][n] = gld<f32x4>(zp + dg_ch0(np, q, n));
             if (SKIP) {
                 const _Float16* p = u.own + u.sq[L - 1] + (cg * SSK + sidx) * 8;
                 dk[st][j] = H8x2{gld<h8>(p), gld<h8>(p + 16 * SSK * 8)};
@@ -525,13 +549,13 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
                     const float zr = z[st][j][n][r];
                     float tc = __builtin_fmaf(acc[n][m][r], es[n][r], zr);
                     if (SKIP) tc += near ? h2f(dk[st][j], 4 * n + r) : 0.f;
+                    if (!OVERLAY) y[n][r] = tc;  // (the patch: pre-ReLU)
                     tc = tc > 0.f ? tc : 0.f;
                     if (L == 3) {
                         s0 = __builtin_fmaf(e0[n][r], tc, s0);
                         s1 = __builtin_fmaf(e1[n][r], tc, s1);
                         sv = __builtin_fmaf(ev[n][r], tc, sv);
                     } else {
-                        y[n][r] = tc;
                         d[n][r] = tc - (zr > 0.f ? zr : 0.f);
                     }
                 }
@@ -545,7 +569,11 @@ __device__ __forceinline__ void dg_epilogue(char* lds, const DgUnit* U, const ui
                 } else {
                     put_hl(u.own + u.sq[L + 1] + (cg * SSO + oidx) * 8, 16 * SSO * 8, dd);
                 }
-                if (u.patch) put_hl(u.patch + PATCH_OFF[L + 1] + (cg * SSO + oidx) * 8, 16 * SSO * 8, split_hl(y));
+                if (!OVERLAY && u.patch) put_f8(u.patch + (PATCH_POS[L + 1] + oidx) * CH + 8 * cg, y);
+            }
+            if (!OVERLAY && L == 3 && v) {  // a parent's x2 square (one node per x2 pass)
+                float* const pp = U[0].patch;
+                if (pp) put_f8(pp + (PATCH_POS[4] + oidx) * CH + 8 * cg, y);
             }
             if (L == 3) {
                 s0 += __shfl_xor(s0, 16);
@@ -669,7 +697,9 @@ __device__ __forceinline__ void dg_col(_Float16* col, const DgUnit* U, int ng, i
 }
 
 // conv0 + BN + ReLU at the <= 9 positions around each node's stone, D(x0) = child -
-// root into the y1 pass's LDS image and the node's x0 square (its patch: the child value)
+// root into the y1 pass's LDS image and the node's x0 square (its patch: the child value).
+// OVERLAY: the reference x0 is the parent's -- its patch within radius 1 of its stone
+template <bool OVERLAY>
 __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const DgUnit* U, int ng,
                                          const float* __restrict__ W, int np, int lane) {
     constexpr int NPOS = K::npos(0);
@@ -688,6 +718,8 @@ __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const D
     _Float16* in = (_Float16*)(lds + K::IN);
     // every node's root x0 values first (one round of latency for the chunk), then the MFMAs
     h8 rxh[K::C], rxl[K::C];
+    f32x4 rxp[OVERLAY ? K::C : 1][2];  // OVERLAY: the parent's patch row where it covers the position
+    bool inp[OVERLAY ? K::C : 1];
 #pragma unroll
     for (int g = 0; g < K::C; g++) {
         const DgUnit& u = U[g < ng ? g : 0];
@@ -699,6 +731,16 @@ __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const D
         const _Float16* rp = u.gm + (cg * 256 + pos) * 8;
         rxh[g] = gld<h8>(rp);
         rxl[g] = gld<h8>(rp + PV_MAP_PLANE);
+        if (OVERLAY) {
+            const int pcell = u.pcell, oy = pr - pcell / BN, ox = pc - (pcell - (pcell / BN) * BN);
+            inp[g] = iabs(oy) <= 1 && iabs(ox) <= 1;
+            rxp[g][0] = rxp[g][1] = zero4();
+            if (inp[g]) {  // (a written row: the position is on the board and in the parent's square)
+                const float* pp = u.patch + (PATCH_POS[0] + (oy + 1) * 3 + (ox + 1)) * CH + 8 * cg;
+                rxp[g][0] = gld<f32x4>(pp);
+                rxp[g][1] = gld<f32x4>(pp + 4);
+            }
+        }
     }
 #pragma unroll
     for (int g = 0; g < K::C; g++) {
@@ -722,15 +764,16 @@ __device__ __forceinline__ void dg_conv0(char* lds, const _Float16* col, const D
                 float t = __builtin_fmaf(acc[r], ws[n][r], wt[n][r]);
                 t = t > 0.f ? t : 0.f;
                 y[n][r] = t;
-                d[n][r] = t - ((float)rxh[g][4 * n + r] + (float)rxl[g][4 * n + r]);  // the root's x0
+                float ref = (float)rxh[g][4 * n + r] + (float)rxl[g][4 * n + r];  // the root's x0
+                if (OVERLAY) ref = inp[g] ? rxp[g][n][r] : ref;
+                d[n][r] = t - ref;
             }
         }
         if (rowok) {
             const H8x2 dd = split_hl(d);
             put_hl_lds(in + (cg * NPOS + g * 9 + idx) * 8, 16 * NPOS * 8, dd);
-            const int o = PATCH_OFF[0] + (cg * 9 + idx) * 8;
-            put_hl(u.own + u.sq[0] + o, 16 * 9 * 8, dd);
-            if (u.patch) put_hl(u.patch + o, 16 * 9 * 8, split_hl(y));
+            put_hl(u.own + u.sq[0] + (cg * 9 + idx) * 8, 16 * 9 * 8, dd);
+            if (!OVERLAY && u.patch) put_f8(u.patch + (PATCH_POS[0] + idx) * CH + 8 * cg, y);
         }
     }
 }
@@ -800,6 +843,11 @@ __device__ __forceinline__ void dg_pass_of(int p, int ng, int& L, int& u0, int& 
     if (L == 0) u0 = 0, g = ng;
 }
 
+// OVERLAY = false: the root children (list: t.children), each a delta of its root.
+// OVERLAY = true: the grandchildren (list: t.grand, a parent's adjacent), each a delta of
+// its parent: the same passes with the parent's values (its patch inside its changed
+// squares, the root's elsewhere) in place of the root's, its record on the parent's.
+template <bool OVERLAY>
 __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* __restrict__ scratch,
                                                            const int32_t* __restrict__ list,
                                                            const int32_t* __restrict__ list_count) {
@@ -836,7 +884,7 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
             cst[i] = v;
         }
     }
-    DgStamp st;
+    typename std::conditional<OVERLAY, PhaseStamp<nullptr>, DgStamp>::type st;
     for (;;) {
         __syncthreads();  // the previous chunk's readers of U, hpart, the tables and POS are done
         if (threadIdx.x == 0) {
@@ -863,19 +911,24 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
             DgUnit u;
             const int ci = A.cinfo[b];
             const int o = (ci >> 8) & 0x3fffff;
-            u.gm = A.maps + (size_t)o * 4 * PV_MAP_HALVES;
+            u.gm = A.maps + (size_t)o * PV_MAP_HALVES;
             u.pre = A.pres + (size_t)o * 4 * PV_PRE_FLOATS;
             u.own = myscr;
             u.sq[0] = scr_sq(0, lane);
             u.sq[1] = scr_sq(1, lane);
             u.sq[2] = scr_sq(2, lane);
             u.sq[3] = scr_sq(3, lane);
-            const int ps = A.pslot[b];
-            u.patch = ps >= 0 ? A.patches + (size_t)ps * PATCH_HALVES : nullptr;
             u.leaf = b;
             u.base = A.meta[b];
             u.cell = ci & 0xff;
-            u.pad0 = 0;
+            if (OVERLAY) {  // the parent (u.base): a root child with a patch slot (tree_lists_kernel)
+                u.patch = A.patches + (size_t)A.pslot[u.base] * PATCH_FLOATS;
+                u.pcell = A.cinfo[u.base] & 0xff;
+            } else {
+                const int ps = A.pslot[b];
+                u.patch = ps >= 0 ? A.patches + (size_t)ps * PATCH_FLOATS : nullptr;
+                u.pcell = 0;
+            }
 #pragma unroll
             for (int w = 0; w < 16; w++) u.board[w] = A.boards[(size_t)b * 16 + w];
             U[lane] = u;
@@ -895,7 +948,7 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
             __syncthreads();
             const float* Wp = W;
             asm volatile("" : "+s"(Wp));
-            dg_conv0(lds, (const _Float16*)(lds + K::COL), U, ng, Wp, np, t & 63);
+            dg_conv0<OVERLAY>(lds, (const _Float16*)(lds + K::COL), U, ng, Wp, np, t & 63);
             dg_rows_all(lds, U, ng, t);
             __syncthreads();  // the y1 image, the row tables and tap masks
 #ifdef GZ_DG_CHK
@@ -915,7 +968,7 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
         }
         st(0);
 #ifdef GZ_PVDG_STAMPS
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&gz_pvdg_stamps_n[0], (unsigned long long)ng);
+        if (!OVERLAY && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&gz_pvdg_stamps_n[0], (unsigned long long)ng);
 #endif
         for (int p = 0; p < K::NPASS; p++) {
             int L, u0, g;
@@ -958,10 +1011,10 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
             // epilogue's scattered stores of the D squares are 15 % of the kernel.)
             const int ldsg = more && L2 == L + 1 && v0 == u0 && (L == 0 || L == 2) ? g2 : 0;
             const bool to_lds = ldsg > 0;
-            if (L == 0) dg_epilogue<0>(lds, U + u0, rt, np, t & 63, acc, nt, ldsg);
-            else if (L == 1) dg_epilogue<1>(lds, U + u0, rt, np, t & 63, acc, nt, 0);
-            else if (L == 2) dg_epilogue<2>(lds, U + u0, rt, np, t & 63, acc, nt, ldsg);
-            else dg_epilogue<3>(lds, U + u0, rt, np, t & 63, acc, nt, 0);
+            if (L == 0) dg_epilogue<0, OVERLAY>(lds, U + u0, rt, np, t & 63, acc, nt, ldsg);
+            else if (L == 1) dg_epilogue<1, OVERLAY>(lds, U + u0, rt, np, t & 63, acc, nt, 0);
+            else if (L == 2) dg_epilogue<2, OVERLAY>(lds, U + u0, rt, np, t & 63, acc, nt, ldsg);
+            else dg_epilogue<3, OVERLAY>(lds, U + u0, rt, np, t & 63, acc, nt, 0);
             if (to_lds) {  // the image's zero slots past the nodes' squares (dg_fill writes them)
                 const int NPN = L == 0 ? K::npos(1) : K::npos(3), z0 = ldsg * (L == 0 ? dg_ss(1) : dg_ss(3));
                 for (int e = t; e < 32 * (NPN - z0); e += NTD) {
@@ -1007,13 +1060,14 @@ __global__ __launch_bounds__(NTD, K::WPS) void pv_dg_kernel(DgArgs A, _Float16* 
 }  // namespace
 
 // the root children (t.children, t.ctr[CTR_CHILDREN] entries) of gz_pv_forward_tree
-// through pv_dg_kernel; t.scratch: PV_SCRATCH_PATCHES patch-sized areas per CU (grid = CUs)
+// through pv_dg_kernel, then the grandchildren (t.grand, t.ctr[CTR_GRAND] entries, parent
+// order) through its overlay form; t.scratch: PV_SCRATCH_AREAS areas per CU (grid = CUs)
 int gz_internal_tree_delta(const TreeWs& t, const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta,
                            int grid, void* stream) {
     DgArgs A{t.cinfo, d_weights, d_boards, d_meta, t.pslot, t.maps, t.pres, t.patches, t.hbuf,
              t.ctr + CTR_TILES, t.ctr + CTR_DG_QUEUE};
     // K::WPS workgroups per grid entry (CU), K::C patch-sized scratch areas each
-    static_assert(K::WPS * SCR_HALVES <= PV_SCRATCH_PATCHES * PATCH_HALVES, "scratch");
+    static_assert(K::WPS * SCR_HALVES <= PV_SCRATCH_AREAS * PV_SCRATCH_AREA_HALVES, "scratch");
 #ifdef GZ_PVDG_STAMPS
     // stamp builds: GZ_PVDG_WPS=1 runs one workgroup per CU (the k-loop without a co-resident one)
     static const int wps = std::getenv("GZ_PVDG_WPS") && std::getenv("GZ_PVDG_WPS")[0] == '1' ? 1 : K::WPS;
@@ -1023,12 +1077,17 @@ int gz_internal_tree_delta(const TreeWs& t, const float* d_weights, const uint32
 #ifdef GZ_DG_CHK
     {
         const char* lo = (const char*)t.hbuf;
-        const char* hi = (const char*)(t.scratch + (size_t)grid * PV_SCRATCH_PATCHES * PATCH_HALVES);
+        const char* hi = (const char*)(t.scratch + (size_t)grid * PV_SCRATCH_AREAS * PV_SCRATCH_AREA_HALVES);
         hipMemcpyToSymbolAsync(HIP_SYMBOL(gz_dg_lo), &lo, sizeof(lo), 0, hipMemcpyHostToDevice, (hipStream_t)stream);
         hipMemcpyToSymbolAsync(HIP_SYMBOL(gz_dg_hi), &hi, sizeof(hi), 0, hipMemcpyHostToDevice, (hipStream_t)stream);
     }
 #endif
-    pv_dg_kernel<<<grid * wps, NTD, 0, (hipStream_t)stream>>>(A, t.scratch, t.children, t.ctr + CTR_CHILDREN);
+    pv_dg_kernel<false><<<grid * wps, NTD, 0, (hipStream_t)stream>>>(A, t.scratch, t.children, t.ctr + CTR_CHILDREN);
+    // the grandchildren: their parents' patches and records are written; tile-taps to the
+    // grandchildren's counter, a queue of their own
+    A.tiles = t.ctr + CTR_TILES + 1;
+    A.queue = t.ctr + CTR_GRAND_QUEUE;
+    pv_dg_kernel<true><<<grid * wps, NTD, 0, (hipStream_t)stream>>>(A, t.scratch, t.grand, t.ctr + CTR_GRAND);
     return gz_check_launch("tree delta");
 }
 

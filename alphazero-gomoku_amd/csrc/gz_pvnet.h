@@ -62,13 +62,23 @@ constexpr int PV_MAP_HALVES = 2 * PV_MAP_PLANE;
 // of the 4 residual layers (y1, x1, y2, x2: z = BN(conv) [+ skip input]), fp32
 // position-major [256 positions][128 channels] -- PV_PRE_FLOATS floats per layer
 constexpr int PV_PRE_FLOATS = 256 * CH;
-// a root child's recomputed squares / D squares (x0 r1, y1 r2, x1 r3, y2 r4: 164
-// positions x 256 halves), the unit of the patch slots and of the tree scratch
-constexpr int PV_PATCH_HALVES = 164 * 256;
-// tree scratch per grid entry (one per CU): PV_SCRATCH_PATCHES patch-sized areas,
-// shared by the workgroups of pv_sib_kernel / pv_dg_kernel on that entry (each kernel
-// static_asserts its workgroups x nodes per chunk against it)
-constexpr int PV_SCRATCH_PATCHES = 12;
+// a root child's patch (written when it has children of its own, read by their delta
+// pass): fp32, position-major [position][128 channels] -- its x0 (post-ReLU) in the
+// radius-1 square around its stone, then its pre-ReLU values of y1 r2, x1 r3, y2 r4 and
+// x2 r5: 9 + 25 + 49 + 81 + 121 = 285 positions x 512 B (counted in halves)
+constexpr int PV_PATCH_POS = 285;
+constexpr int PV_PATCH_HALVES = PV_PATCH_POS * 256;
+// Of a root's maps only x0 is stored (conv0's reference of its children); y1, x1, y2 are
+// relu of the pre-ReLU values and nothing reads them.  The patch slots share one pool:
+// per root map slot the bytes of those three maps and of the 16 patches of 164 positions
+// that the workspace held before the patches grew -- so gz_pv_tree_workspace_bytes is what
+// it was, and the pool holds 11.9 patch slots per root map slot
+constexpr size_t PV_PATCH_POOL_BYTES = 3 * (size_t)PV_MAP_HALVES * 2 + 16 * (size_t)164 * 512;
+// tree scratch per grid entry (one per CU): PV_SCRATCH_AREAS areas of a node's D
+// squares (x0 r1, y1 r2, x1 r3, y2 r4: 164 positions x 256 halves), shared by the
+// workgroups of pv_dg_kernel on that entry (it static_asserts its need against it)
+constexpr int PV_SCRATCH_AREAS = 12;
+constexpr int PV_SCRATCH_AREA_HALVES = 164 * 256;
 // per-board record of the 1x1 head convs' outputs between the tower and the FC heads
 // (gz_pvnet.hip / gz_pvinc.hip -> pv_heads_kernel): hp [0, 450) channel-major, zero to
 // HP_K; hv [HV_OFF, HV_OFF + 225), zero to HSTRIDE
@@ -85,26 +95,28 @@ constexpr long long MACS = 133690114LL;
 
 // ---------------------------------------------------------------- tree forward (host)
 // The counter block of a tree forward (TreeWs::ctr, zeroed by gz_internal_tree_classify):
-// list counts, then the 16-row MFMA tile-taps the incremental kernels executed, then the
-// per-XCD chunk queue heads of pv_dg_kernel and pv_sib_kernel
+// list counts, then the 16-row MFMA tile-taps the incremental kernel executed, then the
+// per-XCD chunk queue heads of pv_dg_kernel's two launches
 enum TreeCtr {
     CTR_ROOTS_SEEN = 0,  // leaves tagged as roots (with or without a map slot)
     CTR_ROOTS = 1,       // roots with a map slot: full forward, maps stored
     CTR_CHILDREN = 2,    // root children (pv_dg_kernel)
     CTR_FULL = 3,        // every other board without a stored root or patch: full forward
-    CTR_GRAND = 4,       // grandchildren (pv_sib_kernel)
+    CTR_GRAND = 4,       // grandchildren (pv_dg_kernel, the overlay form)
     CTR_PATCHES = 5,     // patch slots claimed
     CTR_STATS = 6,       // gz_pv_tree_stats copies [0, CTR_STATS)
     CTR_TILES = 8,       // [2] executed tile-taps: root children, grandchildren
-    CTR_DG_QUEUE = 16,   // [8] pv_dg_kernel's queue heads
-    CTR_SIB_QUEUE = 24,  // [8] pv_sib_kernel's queue heads
+    CTR_DG_QUEUE = 16,   // [8] pv_dg_kernel's queue heads, the children's launch
+    CTR_GRAND_QUEUE = 24,  // [8] the same of the grandchildren's launch
     CTR_COUNT = 32
 };
-static_assert(CTR_STATS <= CTR_TILES && CTR_TILES + 2 <= CTR_DG_QUEUE && CTR_DG_QUEUE + 8 == CTR_SIB_QUEUE &&
-                  CTR_SIB_QUEUE + 8 == CTR_COUNT, "counter slots");
+static_assert(CTR_STATS <= CTR_TILES && CTR_TILES + 2 <= CTR_DG_QUEUE && CTR_DG_QUEUE + 8 == CTR_GRAND_QUEUE &&
+                  CTR_GRAND_QUEUE + 8 == CTR_COUNT, "counter slots");
 
 constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-constexpr int32_t patch_cap_of(int32_t root_cap) { return 16 * (root_cap < 0 ? 0 : root_cap); }
+constexpr int32_t patch_cap_of(int32_t root_cap) {
+    return (int32_t)((size_t)(root_cap < 0 ? 0 : root_cap) * PV_PATCH_POOL_BYTES / ((size_t)PV_PATCH_HALVES * 2));
+}
 
 // The tree-forward workspace, described once: byte offsets of its regions for n leaves,
 // root_cap root map slots and `grid` scratch entries (one per CU), in order; `end` is
@@ -114,17 +126,16 @@ struct TreeLayout {
     size_t ord, pslot, roots, full, grand, gnext, cinfo;  // [n] i32 each
     size_t children;  // [n] i32 + the per-wave counts of tree_lists_kernel [n / 64 + 1]
     size_t ctr;       // [CTR_COUNT] i32
-    size_t ghead;     // [patch_cap] i32
-    size_t maps;      // [root_cap][4][PV_MAP_HALVES] f16
+    size_t ghead;     // [16 root_cap >= patch_cap] i32
+    size_t maps;      // [root_cap][PV_MAP_HALVES] f16: x0
     size_t pres;      // [root_cap][4][PV_PRE_FLOATS] f32
-    size_t patches;   // [patch_cap][PV_PATCH_HALVES] f16
-    size_t scratch;   // [grid][PV_SCRATCH_PATCHES][PV_PATCH_HALVES] f16
+    size_t patches;   // [patch_cap][PV_PATCH_POS][128] f32
+    size_t scratch;   // [grid][PV_SCRATCH_AREAS][PV_SCRATCH_AREA_HALVES] f16
     size_t hf;        // HF_BYTES
     size_t end;
 };
 constexpr TreeLayout tree_layout(int32_t n, int32_t root_cap, int grid) {
     const size_t m = (size_t)(n < 1 ? 1 : n), rc = (size_t)(root_cap < 0 ? 0 : root_cap);
-    const size_t pc = (size_t)patch_cap_of(root_cap);
     TreeLayout l{};
     size_t p = 0;
     const auto take = [&p](size_t bytes) {
@@ -136,11 +147,11 @@ constexpr TreeLayout tree_layout(int32_t n, int32_t root_cap, int grid) {
     for (size_t* a : {&l.ord, &l.pslot, &l.roots, &l.full, &l.grand, &l.gnext, &l.cinfo}) *a = take(al256(m * 4));
     l.children = take(al256((m + m / 64 + 1) * 4));
     l.ctr = take(al256(CTR_COUNT * sizeof(int32_t)));
-    l.ghead = take(al256(pc * 4));
-    l.maps = take(rc * 4 * PV_MAP_HALVES * sizeof(_Float16));
+    l.ghead = take(al256(16 * rc * 4));
+    l.maps = take(rc * PV_MAP_HALVES * sizeof(_Float16));
     l.pres = take(rc * 4 * PV_PRE_FLOATS * sizeof(float));
-    l.patches = take(pc * PV_PATCH_HALVES * sizeof(_Float16));
-    l.scratch = take((size_t)grid * PV_SCRATCH_PATCHES * PV_PATCH_HALVES * sizeof(_Float16));
+    l.patches = take(rc * PV_PATCH_POOL_BYTES);
+    l.scratch = take((size_t)grid * PV_SCRATCH_AREAS * PV_SCRATCH_AREA_HALVES * sizeof(_Float16));
     l.hf = take(HF_BYTES);
     l.end = p;
     return l;
@@ -152,8 +163,8 @@ struct TreeWs {
     int32_t *ord, *pslot, *roots, *full, *grand, *gnext, *cinfo, *children, *ghead, *ctr;
     _Float16* maps;
     float* pres;        // the roots' pre-BN accumulators (pv_dg_kernel)
-    _Float16* patches;
-    _Float16* scratch;  // pv_sib_kernel / pv_dg_kernel: PV_SCRATCH_PATCHES patch-sized areas per grid entry
+    float* patches;     // the parents' patches (pv_dg_kernel)
+    _Float16* scratch;  // pv_dg_kernel: PV_SCRATCH_AREAS areas per grid entry
     _Float16* hf;       // the heads' fp16 fragments
     int32_t patch_cap;
 };

@@ -159,8 +159,8 @@ __device__ __forceinline__ void f16_load(const ActF16x3& act, f32x4 (&out)[2][NM
 }
 
 // f16_put4 that also stores the result to the global copy g of the map (the same
-// [hi plane][lo plane] layout as LDS) when g != nullptr: a root board's
-// intermediate maps for the incremental forward of its children (gz_pvinc.hip)
+// [hi plane][lo plane] layout as LDS) when g != nullptr: a root board's x0 map
+// for the incremental forward of its children (conv0_f16; gz_pvdg.hip)
 template <bool SKIP>
 __device__ __forceinline__ void pv_put4(ActF16x3& act, const f32x4& acc, const f32x4& s, const f32x4& t,
                                         const f32x4& skip, int ch0, int pos, _Float16* __restrict__ g,
@@ -193,7 +193,7 @@ __device__ __forceinline__ void pv_put4(ActF16x3& act, const f32x4& acc, const f
 template <int NM, bool SKIP>
 __device__ __forceinline__ void f16_store(ActF16x3& act, const f32x4 (&acc)[2][NM], const float* __restrict__ S,
                                           const float* __restrict__ T, const f32x4 (&skip)[2][NM], int np, int m0,
-                                          int lane, _Float16* __restrict__ g, float* __restrict__ pre) {
+                                          int lane, float* __restrict__ pre) {
     asm volatile("" : "+v"(lane));  // addresses are recomputed per layer, not hoisted (and spilled)
     lane &= 63;
 #pragma unroll
@@ -203,7 +203,7 @@ __device__ __forceinline__ void f16_store(ActF16x3& act, const f32x4 (&acc)[2][N
 #pragma unroll
         for (int m = 0; m < NM; m++) {
             const int pos = (m0 + m) * 16 + (lane & 15);
-            if (pos < POS) pv_put4<SKIP>(act, acc[n][m], s, t, skip[n][m], ch0, pos, g, pre);
+            if (pos < POS) pv_put4<SKIP>(act, acc[n][m], s, t, skip[n][m], ch0, pos, nullptr, pre);
         }
     }
 }
@@ -267,12 +267,11 @@ __device__ __forceinline__ void f16_store_heads(const f32x4 (&acc)[2][NM], const
     }
 }
 
-// gmaps: nullptr, or the root's 4 map copies (x0, y1, x1, y2); y1, x1, y2 are stored here.
-// gpre: nullptr, or the root's 4 pre-ReLU maps (PV_PRE_FLOATS each)
+// gpre: nullptr, or the root's 4 pre-ReLU maps (PV_PRE_FLOATS each); of a root's maps
+// only x0 is kept (conv0_f16): y1, x1, y2 are relu of these
 template <int NM, int m0>
 __device__ __forceinline__ void f16_tower(ActF16x3& act, const float* __restrict__ W, int wave, int lane,
-                                          float* __restrict__ hpart, _Float16* __restrict__ gmaps,
-                                          float* __restrict__ gpre) {
+                                          float* __restrict__ hpart, float* __restrict__ gpre) {
     const int np = wave & 3;
     for (int blk = 0; blk < 2; blk++) {
         f32x4 skip[2][NM];
@@ -294,11 +293,9 @@ __device__ __forceinline__ void f16_tower(ActF16x3& act, const float* __restrict
             PV_STAMP(3);
             float* pre = gpre ? gpre + (size_t)layer * PV_PRE_FLOATS : nullptr;
             if (half == 0)
-                f16_store<NM, false>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane,
-                                     gmaps ? gmaps + (size_t)(1 + layer) * PV_MAP_HALVES : nullptr, pre);
+                f16_store<NM, false>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane, pre);
             else if (blk == 0)
-                f16_store<NM, true>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane,
-                                    gmaps ? gmaps + (size_t)2 * PV_MAP_HALVES : nullptr, pre);
+                f16_store<NM, true>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane, pre);
             else
                 f16_store_heads<NM>(acc, W, R + RES_S, R + RES_T, skip, np, m0, lane, hpart, pre);
             __syncthreads();
@@ -724,7 +721,7 @@ constexpr int PV_SPLIT = 8;  // M tiles of the older wave of each SIMD pair (it 
 constexpr int PV_YOUNG_TILES = 15 - PV_SPLIT;
 // list (optional): the boards to run, list[0 .. *list_count); ord / maps: the
 // root ordinal of every board (-1: none) and the root map area -- a board with
-// 0 <= ord < root_cap also stores its x0, y1, x1, y2 maps (gz_pvinc.hip)
+// 0 <= ord < root_cap also stores its x0 map and its pre-ReLU values (gz_pvdg.hip)
 template <bool LIST, bool DUMP>
 __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restrict__ W,
                                                          const uint32_t* __restrict__ boards, int n,
@@ -752,7 +749,7 @@ __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restri
         if (DUMP) {
             const int o = ord[b];
             if (o >= 0 && o < root_cap) {
-                gm = maps + (size_t)o * 4 * PV_MAP_HALVES;
+                gm = maps + (size_t)o * PV_MAP_HALVES;  // x0 only
                 if (pres) gp = pres + (size_t)o * 4 * PV_PRE_FLOATS;
             }
         }
@@ -770,9 +767,9 @@ __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restri
         __syncthreads();
         PV_STAMP(1);
         if (wave >> 2)
-            f16_tower<PV_YOUNG_TILES, PV_SPLIT>(act, W, wave, lane, sm.hpart, gm, gp);
+            f16_tower<PV_YOUNG_TILES, PV_SPLIT>(act, W, wave, lane, sm.hpart, gp);
         else
-            f16_tower<PV_SPLIT, 0>(act, W, wave, lane, sm.hpart, gm, gp);
+            f16_tower<PV_SPLIT, 0>(act, W, wave, lane, sm.hpart, gp);
         int tid_h = threadIdx.x;  // re-read: a pinned tid kept live across the tower is spilled
         asm volatile("" : "+v"(tid_h));
         // the 1x1 head convs' outputs go to HBM; the FC heads run batched over boards
@@ -1278,7 +1275,7 @@ static TreeWs tree_carve(void* ws, int32_t n, int32_t root_cap) {
     t.ghead = (int32_t*)(p + l.ghead);
     t.maps = (_Float16*)(p + l.maps);
     t.pres = (float*)(p + l.pres);
-    t.patches = (_Float16*)(p + l.patches);
+    t.patches = (float*)(p + l.patches);
     t.scratch = (_Float16*)(p + l.scratch);
     t.hf = (_Float16*)(p + l.hf);
     t.patch_cap = patch_cap_of(root_cap);

@@ -295,8 +295,9 @@ def pv_forward_tree(weights, leaf_rows, meta, root_cap=None, d_count=None):
     rows = np.ascontiguousarray(leaf_rows, np.uint32).reshape(-1, 16)
     n = rows.shape[0]
     meta = np.ascontiguousarray(meta, np.int32)
-    if root_cap is None:
-        root_cap = int((meta == -1).sum())
+    if root_cap is None:  # a map slot per root and a quarter more: 11.9 patch slots per map slot
+        roots = int((meta == -1).sum())
+        root_cap = roots + (roots + 3) // 4
     d_b = torch.from_numpy(rows.view(np.int32).copy()).cuda()
     d_m = torch.from_numpy(meta.copy()).cuda()
     new = torch.empty

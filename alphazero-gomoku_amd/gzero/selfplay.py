@@ -87,8 +87,8 @@ class SelfPlayEngine:
         pv_mode: "full" = one full forward per node (gz_pv_forward); "tree" = the
         incremental forward (gz_pv_forward_tree, f16x3 only): a root's children as the
         root's pre-BN accumulators plus the convolution of their input differences
-        (within 2e-5 of the full forward), its grandchildren recomputing the windows
-        around their new stone; roots and other nodes bit-identical to "full"."""
+        (within 2e-5 of the full forward), its grandchildren the same delta of their
+        parent; roots and other nodes bit-identical to "full"."""
         if search not in ("reference", "puct"):
             raise ValueError(f"search must be 'reference' or 'puct', not {search!r}")
         self.search = search
@@ -187,7 +187,10 @@ class SelfPlayEngine:
         self.d_meta = self.d_tree_ws = None
         if self.tree:
             self.d_meta = torch.empty(self.leaf_cap, dtype=torch.int32, device="cuda")
-            self.root_cap = self.n_slots * self.plies_per_step  # one root per slot per ply
+            # one root per slot per ply, and a quarter more: the patch slots (11.9 per root
+            # slot) are one pool, and a ply-step needs about 13.4 per root that moves
+            roots = self.n_slots * self.plies_per_step
+            self.root_cap = roots + (roots + 3) // 4
             self.d_tree_ws = torch.empty(self.lib.gz_pv_tree_workspace_bytes(self.leaf_cap, self.root_cap),
                                          dtype=torch.uint8, device="cuda")
         base = int(game_id_base)

@@ -264,13 +264,18 @@ int gz_pv_forward_sym(const float* d_weights, const uint32_t* d_boards, int32_t 
  * plus the convolution of their one-stone input differences (radius 1..4 per
  * layer's input): the same network in f16x3 arithmetic with fp32 accumulation in
  * another order, within 2e-5 of the full forward's logits / value (1e-4 of the
- * reference's fp32 forward).  The children of a root child (grandchildren)
- * recompute the windows around their stone from the root's maps overlaid with
- * their parent's recomputed squares (at most 16 * root_cap parents).  A tag whose
+ * reference's fp32 forward).  The children of a root child (grandchildren) are
+ * the same delta taken from their parent: the parent's pre-ReLU values (its
+ * patch, fp32, inside the squares its stone changed; the root's elsewhere) plus
+ * the convolution of the grandchild's one-stone differences -- a delta of a
+ * delta, under the same 2e-5 / 1e-4 bounds, not the full forward's values given
+ * the patch (the patches of 145,920 B share one pool of 1,736,704 B per root map
+ * slot, 11.9 patches each; the grandchildren of parents beyond it take the full
+ * forward, so give root_cap room where roots have a dozen such parents).  A tag whose
  * board does not differ from its parent's by exactly one cell is ignored (full
  * forward), so the tags only decide speed.  d_workspace:
- * gz_pv_tree_workspace_bytes(n, root_cap) bytes (~2.4 MB per root: maps 512 KB,
- * pre-BN accumulators 512 KB, 16 patches of 84 KB).  It has no precision argument:
+ * gz_pv_tree_workspace_bytes(n, root_cap) bytes (~2.4 MB per root: the x0 map
+ * 128 KB, pre-ReLU values 512 KB, the patch pool 1.7 MB).  It has no precision argument:
  * the tree forward is f16x3 only (there is no GZ_PV_F16 tree forward). */
 size_t gz_pv_tree_workspace_bytes(int32_t n, int32_t root_cap);
 int gz_pv_forward_tree(const float* d_weights, const uint32_t* d_boards, const int32_t* d_meta, int32_t n,

@@ -5,8 +5,9 @@ Plays --burn-in plies on --slots self-play slots (200 sims, no PV), then one
 step with the leaves gathered and tagged, and runs the tree forward (and, with
 --full, the full forward) --iters times on those same leaves.  Prints the list
 sizes, ms per launch and the bitwise check of the last launch against the full
-forward (--check: within 2e-5).  Used with rocprofv3 (--kernel-trace / --pmc) to
-isolate pv_dg_kernel / pv_sib_kernel.
+forward (--check: within 2e-5; per node kind too: roots, children, grandchildren).  Used
+with rocprofv3 (--kernel-trace / --pmc) to isolate pv_dg_kernel's two launches
+(pv_dg_kernel<false>: the children, pv_dg_kernel<true>: the grandchildren).
 """
 import argparse
 import os
@@ -63,11 +64,6 @@ def main():
         ms = ev[0].elapsed_time(ev[1]) / a.iters
         print(f"{label}: {ms:.3f} ms per launch, {ms * 1e3 / n:.4f} us per board", flush=True)
 
-    stamps = hasattr(lib, "gz_pvinc_stamps_read")
-    if stamps:  # -DGZ_PVINC_STAMPS build (make -C tools variant VAR=pistamps EXTRA=-DGZ_PVINC_STAMPS)
-        import ctypes
-        lib.gz_pvinc_stamps_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        st = np.zeros(34, np.uint64)
     dgst = hasattr(lib, "gz_pvdg_stamps_read")
     if dgst:  # -DGZ_PVDG_STAMPS build (make -C tools variant VAR=dgstamps EXTRA=-DGZ_PVDG_STAMPS)
         import ctypes
@@ -78,10 +74,6 @@ def main():
                 "x2 epilogue + heads", "drain + barrier (y1 -> x1, x2)", "fill issue (+ record) + wait",
                 "barrier (image landed)"]
     tiles = torch.zeros(2, dtype=torch.int32, device="cuda")
-    sib_names = ["select nodes", "window fills (not overlapped)", "conv0", "y1 k-loop", "y1 barrier + next fill",
-                 "y1 epilogue", "x1 k-loop", "x1 barrier + next fill", "x1 epilogue", "y2 k-loop",
-                 "y2 barrier + next fill", "y2 epilogue", "x2 k-loop", "x2 barrier + next fill",
-                 "x2 epilogue + heads", "record"]
     run = tree
     if hasattr(lib, "gz_pvdg_chk_read"):  # -DGZ_DG_CHK build: global accesses outside the workspace
         import ctypes
@@ -89,7 +81,8 @@ def main():
         chk = np.zeros(16, np.uint64)
         tree()
         lib.gz_pvdg_chk_read(chk.ctypes.data)
-        print("pv_dg_kernel checks (loads / stores / fills / record r / record w outside the workspace, LDS "
+        print("pv_dg_kernel checks, both launches (loads, the patch reads included / stores / fills / record r / "
+              "record w outside the workspace, LDS "
               "fragment reads, row node index, x2 partial index, tables bad at chunk start, stale past the count, bad "
               "cells, tables bad before y1/x1 passes, before y2/x2 passes):", chk.tolist(), flush=True)
     timed(run, "tree")
@@ -99,7 +92,7 @@ def main():
     _lib.check(lib.gz_pv_tree_exec_tiles(ptr(eng.d_tree_ws), eng.leaf_cap, ptr(tiles), stream()), "tiles")
     t2 = [int(x) for x in tiles.cpu()]
     print(f"  executed 16-row tile-taps: children {t2[0]} ({t2[0] / max(1, st_kids):.1f} per child), "
-          f"grandchildren {t2[1]}", flush=True)
+          f"grandchildren {t2[1]} ({t2[1] / max(1, st[4]):.1f} per grandchild)", flush=True)
     if dgst:
         lib.gz_pvdg_stamps_read(dst.ctypes.data, 1)
         run()
@@ -111,17 +104,6 @@ def main():
         print(f"  stamps, workgroup 0 children (pv_dg_kernel): {kids} nodes, {tot / kids:.0f} ticks per node")
         for i, x in enumerate(dg_names):
             print(f"    {x:36s} {vals[i] / kids:9.0f}  {vals[i] / max(1, tot) * 100:5.1f}%")
-    if stamps:
-        lib.gz_pvinc_stamps_read(st.ctypes.data, 1)
-        run()
-        torch.cuda.synchronize()
-        lib.gz_pvinc_stamps_read(st.ctypes.data, 0)
-        gk = max(1, int(st[32]))
-        vals = [int(x) for x in st[: len(sib_names)]]
-        tot = sum(vals)
-        print(f"  stamps, workgroup 0 grandchildren (pv_sib_kernel): {gk} nodes, {tot / gk:.0f} ticks per node")
-        for i, x in enumerate(sib_names):
-            print(f"    {x:30s} {vals[i] / gk:9.0f}  {vals[i] / max(1, tot) * 100:5.1f}%")
     if a.full or a.check:
         ws = w.workspace_for(eng.leaf_cap)
 
@@ -139,6 +121,17 @@ def main():
         good = err[0] < 2e-5 and err[1] < 2e-5 and err[2] < 1e-6 and err[3] < 1e-6
         print(f"tree: max |diff| vs the full forward: logits {err[0]:.2e} value {err[1]:.2e} "
               f"probs {err[2]:.2e} prior {err[3]:.2e} -> {'ok' if good else 'FAIL'}", flush=True)
+        # per node kind as tagged (meta: -1 root, a root's index: child, a child's: grandchild)
+        meta = eng.d_meta[:n].cpu().numpy()
+        par = np.where(meta >= 0, meta, 0)
+        kind = np.where(meta == -1, 0, np.where(meta < 0, 3, np.where(meta[par] == -1, 1, np.where(meta[par] >= 0, 2, 3))))
+        dl = (out[0].double() - ref[0].double()).abs().reshape(n, 225).amax(1).cpu().numpy()
+        dv = (out[1].double() - ref[1].double()).abs().reshape(n).cpu().numpy()
+        for kd, name in enumerate(("roots", "children", "grandchildren", "other")):
+            sel = kind == kd
+            if sel.any():
+                print(f"  {name}: {int(sel.sum())} nodes, max |dlogit| {dl[sel].max():.3e} max |dvalue| {dv[sel].max():.3e}",
+                      flush=True)
         if not good:
             sys.exit(1)
 
