@@ -11,6 +11,8 @@ additions is not, so the outputs are compared within tolerance, stated here:
 * against the REFERENCE (tests/golden pvnet2, weight seed 29): within the
   north star's 1e-4, as the full forward;
 * at weights x3 (larger activations and differences) within 1e-4 of torch fp32.
+These are the reference-parity and geometry tests; the precision claim of the delta rows
+(16 T of the float64 specification) is held in tests/test_gpu_pv_f16x3.py.
 """
 import base64
 

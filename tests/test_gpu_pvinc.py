@@ -12,7 +12,8 @@ logits and value within DELTA_TOL = 2e-5 of the full forward (measured ~2e-7),
 softmax and the fp64 masked prior within 1e-6.  Covered: grandchildren on every
 cell around parents at corners, edges and the centre, both capacity fallbacks and
 wrong tags; children on every cell, real searches and the reference fixtures are in
-tests/test_gpu_pvdelta.py.
+tests/test_gpu_pvdelta.py.  DELTA_TOL guards the geometry; the precision claim (16 T of the
+float64 specification) is held in tests/test_gpu_pv_f16x3.py.
 """
 import numpy as np
 import pytest

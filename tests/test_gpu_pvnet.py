@@ -1,6 +1,7 @@
 """K6 policy-value forward (fp32 MFMA) against the reference GomokuModel
 (golden, deterministic weights) and against a torch fp32 CPU forward.
-Tolerance: 1e-4 absolute on logits / value / softmax (north star)."""
+Tolerance: 1e-4 absolute on logits / value / softmax (north star).  This is reference
+parity; the precision claim (fp32-equivalent, 8 T) is held in tests/test_gpu_pv_f16x3.py."""
 import base64
 
 import numpy as np
