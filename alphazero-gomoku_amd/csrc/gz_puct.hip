@@ -55,24 +55,9 @@
 // Root noise is mixed into the rows of full roots only.  Not with leaf batching, not in
 // a match.
 //
-// Workspace (gz_puct_workspace_bytes(n, S), M = S+1 nodes per game):
-//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S, flags, alpha, eps, F, p), written
-//                       by gz_puct_begin
-//   n x game_stride     per game, game_stride = al256(128 + 2334 M):
-//        PuctHdr  128 B   root position, game id, node count, pending node, ...
-//        W        f64 [M]
-//        prior    f64 [M][225]   the evaluator's row, copied by the backup step
-//        visits   i32 [M]
-//        value    f32 [M]        the value the network returned for the node
-//        board    u32 [M][16]    black[8], white[8] of the node's position
-//        child    i16 [M][225]   -1 = none
-//        parent   i16 [M]
-//        move     u8  [M]        row-major cell (255 for the root)
-//        term     u8  [M]        0 live, 1/2 winner colour, 3 draw (as Tree.term)
-//   gz_puct_search's round buffers: leaves u32 [n][16], active i32 [n], logits f32
-//   [n][225], probs f32 [n][225], value f32 [n], prior f64 [n][225], then
-//   gz_pv_workspace_bytes(n) for the forward.
-// About 2.3 KB per node: 1.9 GB at 4096 games x 200 simulations.
+//
+// The layouts (workspace, export, self-play) are in gz_puct.h, which the PUCT units share;
+// slot compaction is gz_puct_compact.hip, the match gz_puct_match.hip.
 //
 // Tree reuse between plies (opt-in: gz_puct_reroot, gz_selfplay_puct_rounds).  A search
 // ends when visits[0] == S+1.  After the move m the next ply's tree is the subtree of
@@ -98,10 +83,6 @@
 // while its header says so (reuse == REUSE_MAGIC) and its root is the slot's game id,
 // move count and position; gz_selfplay_puct_reset clears the mark.
 //
-// Export (gz_puct_trees, gz_puct_tree_bytes(S) = al256(16 + 1884 M) per game):
-//   i32 n_nodes, n_evals, main_draws, move; then W, prior, visits, value, board,
-//   parent, move, term as above (no child table), nodes in creation order.
-//
 // Leaf batching with virtual loss (opt-in, GZ_PUCT_LEAF_BATCH; tests/puct_batch_ref.py
 // restates it).  Game g owns the rows g K .. g K + K - 1 of every round buffer.  Round 0
 // evaluates the root in row g K.  In every later round puct_select_batch_kernel descends
@@ -123,54 +104,6 @@
 // drains its stores and passes a workgroup-scope release / acquire (batch_sync).
 // The first descent of a round never collides, so a move takes between 1 + ceil(S/K) and
 // S+1 rounds; gz_puct_search reads the largest remaining count back (4 bytes) to know.
-// Batched workspace (gz_puct_batch_workspace_bytes(n, S, K)): PuctCfg and the trees as
-// above, then pend i16 [n][K] (the node of every active row), 256 bytes for the
-// remaining count, the round buffers and the forward's workspace for n K rows.
-//
-// Self-play workspace (gz_selfplay_puct_workspace_bytes(n, S); gz_selfplay_puct_layout gives
-// the offsets), every part al256: boards gz_board_state [n], game ids i64 [n], moves i32
-// [n], stats gz_search_stats [n], visits i32 [n][225], root_q f64 [n], then
-//   pend   u16 [n][200][225]   the visit rows of every slot's game in progress
-//   the PUCT block             the workspace above for n games
-// Capacity and active count (gz_selfplay_puct_run_active, gz_selfplay_puct_rounds_active):
-// n is the capacity, which places every part; a run of the first n_active <= n slots
-// launches n_active workgroups, forwards n_active (K) rows and leaves the rest alone --
-// the per-slot indexing (tree_of, pend + s 200 225, leaf row s) is the same either way.
-//
-// Slot compaction (gz_selfplay_puct_compact; in place).  With a active slots among the
-// first n_active, the holes are the idle slots below a and the fillers the active ones at
-// or above a; there are equally many, and the k-th filler goes to the k-th hole (both
-// ascending).  Sources (>= a) and destinations (< a) are disjoint, so all pairs move at
-// once without a second copy of the trees or of pend; the slot order is not preserved.
-//   1. puct_compact_plan_kernel   one workgroup: counts a, ranks holes and fillers, writes
-//                                 the pair lists, d_order and d_n_active;
-//   2. puct_compact_move_kernel   pair x part: the filler's pend rows [0, n_moves) and, for
-//                                 the reuse engine, its PuctHdr and rows [0, n_nodes) of
-//                                 each tree array to the hole's places, byte for byte
-//                                 (16-byte words between the unaligned ends of a span);
-//   3. puct_compact_swap_kernel   the two slot buffers trade places (after 2, which reads
-//                                 n_moves from the filler's slot where it was).
-// The launches are sized for the most pairs there can be, n_active / 2; a workgroup past
-// the device's pair count leaves at once.  What a hole held, and a filler's old place, are
-// dead: an idle slot is never searched, and a later filler overwrites all that is read.
-//
-// The match (gz_puct_match_run): the lock-step self-play ply with two evaluators.  Side A
-// (0) plays black in game g iff ((g ^ parity) & 1) == 0, and the side that moves at a
-// search's root evaluates every leaf of that search.  Per ply, after the boards:
-//   1. puct_match_plan_kernel     one workgroup: side[s] (-1: idle, its board marked over, so
-//                                 begin gives it no leaf and finish move -1), row_of[s] = the
-//                                 slot's rank among its side's slots in ascending slot order,
-//                                 count[0..1];
-//   2. per round (S+1), between select and backup:
-//        puct_match_gather_kernel   leaf row s -> packed leaves of side[s], row row_of[s];
-//        gz_pv_forward x 2          side i's blob and precision over count[i] rows (the count
-//                                   is read on the device; a count of 0 evaluates nothing);
-//        puct_match_scatter_kernel  packed prior row and value -> slot row s of the round
-//                                   buffers, which backup reads as ever;
-//   3. finish, stash, commit as gz_selfplay_puct_run.
-// Match workspace (gz_puct_match_workspace_bytes(n, S)): the self-play workspace of n slots,
-// then side i32 [n], row_of i32 [n], the counts (256 bytes) and per side the round buffers of
-// n rows (leaves, an unused active column, logits, probs, value, prior, the forward's scratch).
 //
 // Leaf symmetry (opt-in, GZ_PUCT_LEAF_SYM; gz_sym.h, gz_pvsym.hip, tests/puct_sym_ref.py):
 // every leaf is evaluated on its board under t = sym_of(seed, leaf row), one of the 8
@@ -179,10 +112,9 @@
 //   select / begin / round -> sym_leaves (leaf rows in place, t per row) -> gz_pv_forward
 //   -> sym_priors (the f64 prior rows in place) -> backup (the root noise as ever, on the
 //   mapped-back row);
-// the match turns the slot rows before the gather and maps the slot rows back after the
-// scatter, so both sides see the same t and a round still has two extra launches.  The
-// select, backup, re-root and compaction kernels do not know about it.  t lives behind the
-// flag-clear workspace: gz_puct_sym_bytes(rows) more bytes, touched only with the flag set.
+// the match (gz_puct_match.hip) likewise.  The select, backup, re-root and compaction kernels do
+// not know about it.  t lives behind the flag-clear workspace: gz_puct_sym_bytes(rows) more
+// bytes, touched only with the flag set.
 // The step API accepts the flag and ignores it (its caller evaluates: gz_pv_forward_sym).
 #include <hip/hip_runtime.h>
 
@@ -192,41 +124,13 @@
 #include <unordered_map>
 
 #include "gz_dirichlet.h"
-#include "gz_internal.h"
-#include "gz_search.h"
+#include "gz_puct.h"
 
 using namespace gz;
 
 namespace {
 
-__host__ __device__ constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct PuctCfg {
-    double c_puct;
-    uint64_t seed;
-    int32_t temp_plies;
-    int32_t S;
-    int32_t flags;  // GZ_PUCT_ROOT_NOISE | GZ_PUCT_PLAYOUT_CAP
-    int32_t leaves;  // K of a batched search (GZ_PUCT_LEAF_BATCH), 0: one leaf per round
-    double noise_alpha;
-    double noise_eps;
-    int32_t fast;      // F of GZ_PUCT_PLAYOUT_CAP
-    int32_t pad;
-    double full_prob;  // p
-};
-static_assert(sizeof(PuctCfg) <= 256, "the configuration block");
-
-// The root noise of a launch, by value.  on: 0 none, 1 mix with (seed, alpha, eps),
-// -1 as gz_puct_begin stored it in the workspace's PuctCfg (gz_puct_backup and
-// gz_puct_reroot take no params).
-struct PuctNoise {
-    double alpha;
-    double eps;
-    uint64_t seed;
-    int32_t on;
-    int32_t pad;
-};
-
+// the root noise of a launch: nz, or (on < 0) what gz_puct_begin stored in the PuctCfg
 __device__ inline PuctNoise noise_of(const PuctNoise& nz, const char* ws) {
     if (nz.on >= 0) return nz;
     const PuctCfg* cfg = (const PuctCfg*)ws;
@@ -239,14 +143,7 @@ __device__ inline PuctNoise noise_of(const PuctNoise& nz, const char* ws) {
     return r;
 }
 
-// The playout cap of a launch, by value.  on: 0 none (every root is full, budget S), 1 cap
-// with (fast, full_prob), -1 as gz_puct_begin stored it in the workspace's PuctCfg.
-struct PuctCap {
-    double full_prob;
-    int32_t fast;
-    int32_t on;
-};
-
+// the playout cap of a launch, as noise_of
 __device__ inline PuctCap cap_of(const PuctCap& cp, const char* ws) {
     if (cp.on >= 0) return cp;
     const PuctCfg* cfg = (const PuctCfg*)ws;
@@ -267,77 +164,6 @@ __host__ __device__ inline bool cap_is_full(uint64_t seed, int64_t game_id, int3
 // is the root of (game, ply) a full search?  Without the cap every root is.
 __device__ inline bool root_is_full(const PuctCap& cap, uint64_t seed, int64_t game_id, int32_t ply) {
     return !cap.on || cap_is_full(seed, game_id, ply, cap.full_prob);
-}
-
-struct PuctHdr {  // 128 bytes
-    uint32_t black[8];
-    uint32_t white[8];
-    int64_t game_id;
-    int32_t n_moves;
-    int32_t player;
-    int32_t over;        // the root is finished (or full): no search, move -1
-    int32_t n_nodes;
-    int32_t n_evals;     // nodes the evaluator was asked for
-    int32_t main_draws;  // draws on the (game, ply, 0) stream (0 or 1)
-    int32_t pending;     // node waiting for its prior and value, -1 = none
-    int32_t move;
-    int32_t new_evals;   // evaluations since the last move (gz_selfplay_puct_rounds' slot statistics)
-    int32_t reuse;       // REUSE_MAGIC: a tree of gz_selfplay_puct_rounds (0: gz_puct_begin, a reset)
-    int32_t rounds;      // rounds of gz_selfplay_puct_rounds since the last move
-    int32_t budget;      // B: the search is finished at B + 1 root visits (S, or F on a fast ply)
-    int32_t full;        // a full ply (always without GZ_PUCT_PLAYOUT_CAP): its root row takes the noise
-    int32_t pad[1];
-};
-constexpr int32_t REUSE_MAGIC = 0x52455553;
-static_assert(sizeof(PuctHdr) == 128, "puct header");
-
-__host__ __device__ inline size_t game_stride_for(int S) {
-    const size_t M = (size_t)S + 1;
-    return al256(sizeof(PuctHdr) + 2334 * M);
-}
-
-__host__ __device__ inline size_t export_bytes_for(int S) {
-    const size_t M = (size_t)S + 1;
-    return al256(16 + 1884 * M);
-}
-
-struct PuctTree {
-    PuctHdr* h;
-    double* W;
-    double* prior;
-    int32_t* visits;
-    float* value;
-    uint32_t* board;
-    int16_t* child;
-    int16_t* parent;
-    uint8_t* move;
-    uint8_t* term;
-};
-
-__device__ inline PuctTree tree_of(char* ws, int g, int S) {
-    const size_t M = (size_t)S + 1;
-    char* b = ws + 256 + (size_t)g * game_stride_for(S);
-    PuctTree t;
-    t.h = (PuctHdr*)b;
-    b += sizeof(PuctHdr);
-    t.W = (double*)b;
-    b += 8 * M;
-    t.prior = (double*)b;
-    b += 1800 * M;
-    t.visits = (int32_t*)b;
-    b += 4 * M;
-    t.value = (float*)b;
-    b += 4 * M;
-    t.board = (uint32_t*)b;
-    b += 64 * M;
-    t.child = (int16_t*)b;
-    b += 450 * M;
-    t.parent = (int16_t*)b;
-    b += 2 * M;
-    t.move = (uint8_t*)b;
-    b += M;
-    t.term = (uint8_t*)b;
-    return t;
 }
 
 __device__ inline void backup(const PuctTree& t, int i, double v) {
@@ -450,12 +276,14 @@ __device__ inline void begin_root(const PuctTree& t, const BB& black, const BB& 
     }
 }
 
+__device__ inline int budget_of(const PuctCap& cap, bool full, int S) { return full ? S : cap.fast; }
+
 // the budget of an inherited root, right after reroot() (every lane of one wave calls;
 // the header already holds the new ply); returns whether the ply is full
 __device__ inline bool set_budget(PuctHdr* h, const PuctCap& cap, uint64_t seed, int S) {
     const bool full = root_is_full(cap, seed, h->game_id, h->n_moves);
     if (lane_id() == 0) {
-        h->budget = full ? S : cap.fast;
+        h->budget = budget_of(cap, full, S);
         h->full = full ? 1 : 0;
     }
     return full;
@@ -492,7 +320,7 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
     load_bb(white, bs.white);
     const bool over = bs.over != 0 || !bb_any(empties(black, white));
     const bool full = root_is_full(cap, p.seed, game_ids[g], bs.n_moves);
-    begin_root(t, black, white, game_ids[g], bs.n_moves, bs.player, over, 0, full ? S : cap.fast, full);
+    begin_root(t, black, white, game_ids[g], bs.n_moves, bs.player, over, 0, budget_of(cap, full, S), full);
     write_leaf(leaves, active, g * rows, black, white, !over);
     for (int k = 1; k < rows; k++) write_leaf(leaves, active, g * rows + k, black, white, false);
     if (pend)
@@ -500,32 +328,37 @@ __global__ __launch_bounds__(WAVE) void puct_begin_kernel(const gz_board_state* 
 }
 
 // ---------------------------------------------------------------- select
-// One simulation's descent of game g's tree: the new leaf's board into row g, or an
-// empty row (a terminal node backed up, a game that is over, waits for a backup or
-// whose root already has its budget's B+1 visits -- with tree reuse, where a game can
-// reach its budget before the others, and on the fast plies of a playout cap).
-__device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, uint32_t* leaves, int32_t* active) {
+// What one descent did.  NONE: the tree is as it was (no empty cell, no node left, a
+// collision).  TERMINAL: a terminal node, found on the path or created, was backed up.
+// LEAF: node j was created under `parent` and waits for its evaluation.
+enum { DESCENT_NONE, DESCENT_TERMINAL, DESCENT_LEAF };
+
+struct Descent {
+    int what;
+    int j, parent;
+};
+
+// One descent by PUCT from the root -- position black / white, `mover` to move at ply cnt --
+// to a new child, which it creates; black / white leave as the position where it ended.
+// VL: virtual loss is in play (the header comment has both forms of the score).  vl [S+1]
+// counts the leaves of this launch that wait below a node, and a live child created in this
+// launch (index >= first) has no prior row yet: a collision.  Without VL neither is read.
+template <bool VL>
+__device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, const int16_t* vl, int first,
+                                       BB& black, BB& white, int mover, int cnt) {
     const int lane = lane_id();
     PuctHdr* h = t.h;
-    BB black, white;
-    load_bb(black, h->black);
-    load_bb(white, h->white);
-    // (pending: the caller skipped a backup; keep the tree as it is)
-    if (h->over || h->pending >= 0 || t.visits[0] > h->budget) {
-        write_leaf(leaves, active, g, black, white, false);
-        return;
-    }
-    int mover = h->player, cnt = h->n_moves;
     int i = 0;
     while (true) {
         const int tm = t.term[i];
         if (tm) {
             if (lane == 0) backup(t, i, tm == 3 ? 0.0 : -1.0);
-            write_leaf(leaves, active, g, black, white, false);
-            return;
+            return {DESCENT_TERMINAL, i, -1};
         }
         const BB E = empties(black, white);
-        const double sq = __builtin_sqrt((double)t.visits[i]);
+        int ni = t.visits[i];
+        if constexpr (VL) ni += vl[i];
+        const double sq = __builtin_sqrt((double)ni);
         const double* pr = t.prior + (size_t)i * GZ_CELLS;
         const int16_t* ch = t.child + (size_t)i * GZ_CELLS;
         double bv = -__builtin_inf();
@@ -538,8 +371,14 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
                 int nn = 0;
                 double q = 0.0;
                 if (cj >= 0) {
-                    nn = t.visits[cj];
-                    q = nn ? t.W[cj] / (double)nn : 0.0;
+                    if constexpr (VL) {
+                        const int lost = vl[cj];
+                        nn = t.visits[cj] + lost;
+                        q = nn ? (t.W[cj] - (double)lost) / (double)nn : 0.0;
+                    } else {
+                        nn = t.visits[cj];
+                        q = nn ? t.W[cj] / (double)nn : 0.0;
+                    }
                 }
                 const double u = ((c_puct * pr[c]) * sq) / (1.0 + (double)nn);
                 const double sc = q + u;
@@ -551,13 +390,12 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
         }
         wave_argmax(bv, bi);
         if (bi == INT_MAX) bi = bit_to_cell(lowest_bit(E));  // only if the evaluator gave non-finite priors
-        if (bi < 0 || bi >= GZ_CELLS) {  // (a live node always has an empty cell)
-            write_leaf(leaves, active, g, black, white, false);
-            return;
-        }
+        if (bi < 0 || bi >= GZ_CELLS) return {DESCENT_NONE, -1, -1};  // (a live node always has an empty cell)
         const int bit = cell_to_bit(bi);
         const int cj = ch[bi];
         if (cj >= 0) {
+            if constexpr (VL)
+                if (cj >= first && t.term[cj] == 0) return {DESCENT_NONE, -1, -1};  // a collision
             if (mover == 1) bb_set(black, bit);
             else bb_set(white, bit);
             mover = 3 - mover;
@@ -566,10 +404,9 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
             continue;
         }
         const int j = h->n_nodes;
-        if (j > S) {  // more select steps than the workspace was sized for: no node left
-            write_leaf(leaves, active, g, black, white, false);
-            return;
-        }
+        // more select steps than the workspace was sized for: no node left (never within the
+        // budget: every descent creates at most one node)
+        if (j > S) return {DESCENT_NONE, -1, -1};
         // make_move (gomoku_board.py:84-113): five or more wins, then the full board /
         // the 200-ply cap draws
         const bool win = bb_test(threats(mover == 1 ? black : white).win, bit);
@@ -583,11 +420,28 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
             t.child[(size_t)i * GZ_CELLS + bi] = (int16_t)j;
             h->n_nodes = j + 1;
             if (term) backup(t, j, term == 3 ? 0.0 : -1.0);
-            else h->pending = j;
         }
-        write_leaf(leaves, active, g, black, white, term == 0);
-        return;
+        return {term ? DESCENT_TERMINAL : DESCENT_LEAF, j, i};
     }
+}
+
+// One simulation's descent of game g's tree: the new leaf's board into row g, or an
+// empty row (a terminal node backed up, a game that is over, waits for a backup or
+// whose root already has its budget's B+1 visits -- with tree reuse, where a game can
+// reach its budget before the others, and on the fast plies of a playout cap).
+__device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, uint32_t* leaves, int32_t* active) {
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    bool live = false;
+    // (pending: the caller skipped a backup; keep the tree as it is)
+    if (!(h->over || h->pending >= 0 || t.visits[0] > h->budget)) {
+        const Descent d = descend_once<false>(t, c_puct, S, nullptr, 0, black, white, h->player, h->n_moves);
+        live = d.what == DESCENT_LEAF;
+        if (live && lane_id() == 0) h->pending = d.j;
+    }
+    write_leaf(leaves, active, g, black, white, live);
 }
 
 __global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int S, uint32_t* leaves, int32_t* active) {
@@ -598,32 +452,43 @@ __global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int 
 }
 
 // ---------------------------------------------------------------- backup
-// The root noise is mixed here, into the row of a root as it is stored (node 0 pending:
-// gz_puct_begin's, puct_round_kernel's and gz_puct_reroot's one-node roots), and not in
-// a kernel of its own: roots appear in any round of gz_selfplay_puct_rounds, so a
-// separate kernel would be one more launch in every round, while here a round without
-// a new root pays one uniform branch.
-__global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int S, const double* prior,
-                                                           const float* value, PuctNoise nz) {
-    const int g = blockIdx.x;
-    if (g >= n) return;
+// Node j receives row `row` of the round buffers: the prior row by the whole wave, the
+// value by lane 0, which backs it up.
+__device__ inline void store_eval(const PuctTree& t, int j, const double* prior, const float* value, size_t row) {
     const int lane = lane_id();
-    PuctTree t = tree_of(ws, g, S);
-    const int j = t.h->pending;
-    if (j < 0) return;
-    for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[(size_t)g * GZ_CELLS + c];
+    for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[row * GZ_CELLS + c];
+    if (lane == 0) {
+        const float v = value[row];
+        t.value[j] = v;
+        backup(t, j, (double)v);
+        t.h->n_evals += 1;
+        t.h->new_evals += 1;
+    }
+}
+
+// The pending node j (>= 0) receives its evaluation.  The root noise is mixed here, into
+// the row of a root as it is stored (node 0 pending: gz_puct_begin's, puct_round_kernel's
+// and gz_puct_reroot's one-node roots), and not in a kernel of its own: roots appear in any
+// round of gz_selfplay_puct_rounds, so a separate kernel would be one more launch in every
+// round, while here a round without a new root pays one uniform branch.  (nz by value: a
+// reference to the kernel's argument keeps a copy of it in scratch.)
+__device__ inline void store_pending_eval(const PuctTree& t, int j, const char* ws, PuctNoise nz, const double* prior,
+                                          const float* value, size_t row) {
+    store_eval(t, j, prior, value, row);
     if (j == 0 && t.h->full) {  // (a fast ply's root keeps the evaluator's row)
         const PuctNoise z = noise_of(nz, ws);
         if (z.on) mix_root_row(t, z);  // (each lane mixes the cells it has just stored)
     }
-    if (lane == 0) {
-        const float v = value[g];
-        t.value[j] = v;
-        backup(t, j, (double)v);
-        t.h->pending = -1;
-        t.h->n_evals += 1;
-        t.h->new_evals += 1;
-    }
+    if (lane_id() == 0) t.h->pending = -1;
+}
+
+__global__ __launch_bounds__(WAVE) void puct_backup_kernel(char* ws, int n, int S, const double* prior,
+                                                           const float* value, PuctNoise nz) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    PuctTree t = tree_of(ws, g, S);
+    const int j = t.h->pending;
+    if (j >= 0) store_pending_eval(t, j, ws, nz, prior, value, g);
 }
 
 // ---------------------------------------------------------------- leaf batching
@@ -661,89 +526,16 @@ __global__ __launch_bounds__(WAVE) void puct_select_batch_kernel(char* ws, int n
     while (go && k < K) {
         if (t.visits[0] + vl[0] > S) break;  // finished + in-flight simulations fill the budget
         BB black = rblack, white = rwhite;
-        int mover = player0, cnt = cnt0;
-        int i = 0;
-        while (true) {
-            const int tm = t.term[i];
-            if (tm) {
-                if (lane == 0) backup(t, i, tm == 3 ? 0.0 : -1.0);
-                break;
-            }
-            const BB E = empties(black, white);
-            const double sq = __builtin_sqrt((double)(t.visits[i] + vl[i]));
-            const double* pr = t.prior + (size_t)i * GZ_CELLS;
-            const int16_t* ch = t.child + (size_t)i * GZ_CELLS;
-            double bv = -__builtin_inf();
-            int bi = INT_MAX;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; q4++) {
-                const int c = lane + WAVE * q4;
-                if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) {
-                    const int cj = ch[c];
-                    int nn = 0;
-                    double q = 0.0;
-                    if (cj >= 0) {
-                        const int lost = vl[cj];
-                        nn = t.visits[cj] + lost;
-                        q = nn ? (t.W[cj] - (double)lost) / (double)nn : 0.0;
-                    }
-                    const double u = ((c_puct * pr[c]) * sq) / (1.0 + (double)nn);
-                    const double sc = q + u;
-                    if (sc > bv) {
-                        bv = sc;
-                        bi = c;
-                    }
-                }
-            }
-            wave_argmax(bv, bi);
-            if (bi == INT_MAX) bi = bit_to_cell(lowest_bit(E));  // only if the evaluator gave non-finite priors
-            if (bi < 0 || bi >= GZ_CELLS) {  // (a live node always has an empty cell)
-                go = false;
-                break;
-            }
-            const int bit = cell_to_bit(bi);
-            const int cj = ch[bi];
-            if (cj >= 0) {
-                if (cj >= first && t.term[cj] == 0) {  // a collision: the node has no prior row yet
-                    go = false;
-                    break;
-                }
-                if (mover == 1) bb_set(black, bit);
-                else bb_set(white, bit);
-                mover = 3 - mover;
-                cnt++;
-                i = cj;
-                continue;
-            }
-            const int j = h->n_nodes;
-            if (j > S) {  // (never within the budget: every descent creates at most one node)
-                go = false;
-                break;
-            }
-            // make_move's rules, as descend()
-            const bool win = bb_test(threats(mover == 1 ? black : white).win, bit);
-            const int ne = bb_count(E);
-            if (mover == 1) bb_set(black, bit);
-            else bb_set(white, bit);
-            cnt++;
-            const int term = win ? mover : ((ne == 1 || cnt >= GZ_MAX_GAME_PLIES) ? 3 : 0);
-            new_node(t, j, i, bi, term, black, white, term != 0);
+        const Descent d = descend_once<true>(t, c_puct, S, vl, first, black, white, player0, cnt0);
+        if (d.what == DESCENT_NONE) go = false;
+        if (d.what == DESCENT_LEAF) {
             if (lane == 0) {
-                t.child[(size_t)i * GZ_CELLS + bi] = (int16_t)j;
-                h->n_nodes = j + 1;
-                if (term) {
-                    backup(t, j, term == 3 ? 0.0 : -1.0);
-                } else {
-                    pd[k] = (int16_t)j;
-                    vl[j] += 1;
-                    for (int x = i; x >= 0; x = t.parent[x]) vl[x] += 1;
-                }
+                pd[k] = (int16_t)d.j;
+                vl[d.j] += 1;
+                for (int x = d.parent; x >= 0; x = t.parent[x]) vl[x] += 1;
             }
-            if (term == 0) {
-                write_leaf(leaves, active, g * K + k, black, white, true);
-                k++;
-            }
-            break;
+            write_leaf(leaves, active, g * K + k, black, white, true);
+            k++;
         }
         batch_sync();
     }
@@ -753,10 +545,9 @@ __global__ __launch_bounds__(WAVE) void puct_select_batch_kernel(char* ws, int n
     }
 }
 
-// The backup step of a batched round: the root of gz_puct_begin (header.pending, row g K,
-// with the root-noise branch of puct_backup_kernel), else the game's active rows in
-// ascending order -- the prior rows by the whole wave, values and backups by lane 0 one
-// row after the other, so every W sums in the reference's order.
+// The backup step of a batched round: the root of gz_puct_begin (header.pending, row g K),
+// else the game's active rows in ascending order -- the prior rows by the whole wave, values
+// and backups by lane 0 one row after the other, so every W sums in the reference's order.
 __global__ __launch_bounds__(WAVE) void puct_backup_batch_kernel(char* ws, int n, int S, int K, int16_t* pend,
                                                                  const double* prior, const float* value,
                                                                  PuctNoise nz) {
@@ -764,38 +555,15 @@ __global__ __launch_bounds__(WAVE) void puct_backup_batch_kernel(char* ws, int n
     if (g >= n) return;
     const int lane = lane_id();
     PuctTree t = tree_of(ws, g, S);
-    PuctHdr* h = t.h;
-    const int j0 = h->pending;
+    const int j0 = t.h->pending;
     if (j0 >= 0) {
-        const size_t row = (size_t)g * K;
-        for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j0 * GZ_CELLS + c] = prior[row * GZ_CELLS + c];
-        if (j0 == 0 && h->full) {
-            const PuctNoise z = noise_of(nz, ws);
-            if (z.on) mix_root_row(t, z);  // (each lane mixes the cells it has just stored)
-        }
-        if (lane == 0) {
-            const float v = value[row];
-            t.value[j0] = v;
-            backup(t, j0, (double)v);
-            h->pending = -1;
-            h->n_evals += 1;
-            h->new_evals += 1;
-        }
+        store_pending_eval(t, j0, ws, nz, prior, value, (size_t)g * K);
         return;
     }
     int16_t* pd = pend + (size_t)g * K;
     for (int k = 0; k < K; k++) {
         const int j = pd[k];
-        if (j < 0 || j > S) continue;
-        const size_t row = (size_t)g * K + k;
-        for (int c = lane; c < GZ_CELLS; c += WAVE) t.prior[(size_t)j * GZ_CELLS + c] = prior[row * GZ_CELLS + c];
-        if (lane == 0) {
-            const float v = value[row];
-            t.value[j] = v;
-            backup(t, j, (double)v);
-            h->n_evals += 1;
-            h->new_evals += 1;
-        }
+        if (j >= 0 && j <= S) store_eval(t, j, prior, value, (size_t)g * K + k);
     }
     // every lane has read the game's pend row before it is cleared
     batch_sync();
@@ -1085,7 +853,7 @@ __global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n
         const int64_t gid = h->game_id;
         const int32_t reuse = h->reuse;
         const bool full = root_is_full(cap, seed, gid, cnt);
-        begin_root(t, black, white, gid, cnt, 3 - mover, over, reuse, full ? S : cap.fast, full);
+        begin_root(t, black, white, gid, cnt, 3 - mover, over, reuse, budget_of(cap, full, S), full);
         live = !over;
         __threadfence_block();
     }
@@ -1094,18 +862,6 @@ __global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n
         const int r = h->over ? 0 : h->budget + 1 - t.visits[0];  // (thread 0 wrote the budget itself)
         remaining[g] = r < 0 ? 0 : r;
     }
-}
-
-// a tree of gz_selfplay_puct_rounds whose root is the slot's game and position
-__device__ inline bool tree_matches(const PuctHdr* h, const SlotHeader* sh) {
-    const int lane = lane_id();
-    bool ne = false;
-    if (lane < 16) ne = ((const uint32_t*)h)[lane] != ((const uint32_t*)sh)[lane];  // black[8], white[8] in both
-    return ballot(ne) == 0 && h->reuse == REUSE_MAGIC && h->game_id == sh->game_id && h->n_moves == sh->n_moves;
-}
-
-__device__ inline const SlotHeader* slot_of(const char* slots, int s) {
-    return (const SlotHeader*)(slots + (size_t)s * slot_stride_bytes());
 }
 
 // Round step 1: a slot whose search is at its budget (B + 1 root visits or more) picks
@@ -1199,8 +955,8 @@ __global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int
         descend(t, p.c_puct, S, s, leaves, active);
     } else {
         const bool full = root_is_full(cap, p.seed, sh->game_id, sh->n_moves);
-        begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC, full ? S : cap.fast,
-                   full);
+        begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC,
+                   budget_of(cap, full, S), full);
         write_leaf(leaves, active, s, black, white, true);
     }
     if (lane_id() == 0) h->rounds = rounds + 1;
@@ -1231,14 +987,14 @@ __global__ __launch_bounds__(256) void puct_export_kernel(const char* ws, int n,
         o[2] = h->main_draws;
         o[3] = h->move;
     }
-    // W .. board: 1880 M bytes, 4-byte words on both sides
+    // W .. board: 4-byte words on both sides
     const uint32_t* a = (const uint32_t*)(src + sizeof(PuctHdr));
     uint32_t* b = (uint32_t*)(dst + 16);
-    for (size_t w = threadIdx.x; w < 470 * M; w += 256) b[w] = a[w];
-    // parent, move, term: 4 M bytes after the child table
-    const char* c = src + sizeof(PuctHdr) + 2330 * M;
-    char* d = dst + 16 + 1880 * M;
-    for (size_t w = threadIdx.x; w < 4 * M; w += 256) d[w] = c[w];
+    for (size_t w = threadIdx.x; w < EXPORT_HEAD_BYTES / 4 * M; w += 256) b[w] = a[w];
+    // parent, move, term: after the child table
+    const char* c = src + sizeof(PuctHdr) + EXPORT_TAIL_OFFSET * M;
+    char* d = dst + 16 + EXPORT_HEAD_BYTES * M;
+    for (size_t w = threadIdx.x; w < EXPORT_TAIL_BYTES * M; w += 256) d[w] = c[w];
 }
 
 // int32 visit row of the search -> the slot's pending uint16 row of this ply
@@ -1274,294 +1030,6 @@ __global__ __launch_bounds__(256) void puct_cap_full_kernel(const gz_record* rec
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     out[i] = cap_is_full(seed, records[i].game_id, records[i].ply, full_prob) ? 1 : 0;
-}
-
-// ---------------------------------------------------------------- slot compaction
-// gz_selfplay_puct_compact (the header comment has the scheme).  The plan in the
-// workspace: int32 n_pairs (16 bytes), holes [cap], fillers [cap].
-constexpr int CP_THREADS = 256;
-constexpr int CP_PARTS = 8;  // workgroups that share the bytes of one pair
-
-// One workgroup scans the first n slots in tiles of 1024 (the ballot and prefix scheme of
-// selfplay_order_kernel): pass 0 counts the active slots, a; pass 1 ranks the holes (idle,
-// index < a) and the fillers (active, index >= a), each ascending; then the k-th filler is
-// paired with the k-th hole.  order[s] = s except at the pairs, which trade places.
-__global__ __launch_bounds__(1024) void puct_compact_plan_kernel(const char* slots, int n, int cap, int32_t* order,
-                                                                 int32_t* n_active, int32_t* plan) {
-    __shared__ int wsum[2][16];
-    __shared__ int carry[2], total;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int32_t* holes = plan + 4;
-    int32_t* fillers = holes + cap;
-    for (int pass = 0; pass < 2; pass++) {
-        if (tid == 0) carry[0] = carry[1] = 0;
-        __syncthreads();
-        for (int t0 = 0; t0 < n; t0 += 1024) {
-            const int s = t0 + tid;
-            const bool in = s < n;
-            bool act = false;
-            if (in) {
-                const SlotHeader* h = slot_of(slots, s);
-                act = h->game_id < h->game_id_end;
-            }
-            // (pass 0: x = active; pass 1: x = hole, y = filler)
-            const bool x = pass == 0 ? act : (in && !act && s < total);
-            const bool y = pass == 1 && act && s >= total;
-            const uint64_t mx = __ballot(x), my = __ballot(y);
-            if (lane == 0) {
-                wsum[0][wave] = __popcll(mx);
-                wsum[1][wave] = __popcll(my);
-            }
-            __syncthreads();
-            int bx = carry[0], by = carry[1];
-            for (int w = 0; w < wave; w++) {
-                bx += wsum[0][w];
-                by += wsum[1][w];
-            }
-            const uint64_t below = (1ull << lane) - 1;
-            if (pass == 1) {
-                if (x) holes[bx + __popcll(mx & below)] = s;
-                if (y) fillers[by + __popcll(my & below)] = s;
-                if (in && !x && !y) order[s] = s;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 0; w < 16; w++) {
-                    carry[0] += wsum[0][w];
-                    carry[1] += wsum[1][w];
-                }
-            }
-            __syncthreads();
-        }
-        if (tid == 0 && pass == 0) {
-            total = carry[0];
-            *n_active = carry[0];
-        }
-        __syncthreads();
-    }
-    // (as many fillers as holes: a minus the active slots below a, either way)
-    const int pairs = carry[0] < carry[1] ? carry[0] : carry[1];
-    if (tid == 0) plan[0] = pairs;
-    __threadfence_block();  // the lists are written before other threads of the workgroup read them
-    __syncthreads();
-    for (int k = tid; k < pairs; k += 1024) {
-        const int h = holes[k], f = fillers[k];
-        order[h] = f;
-        order[f] = h;
-    }
-}
-
-// nbytes from src to dst, which are congruent mod 16: this workgroup's share (part of
-// CP_PARTS) of the 16-byte words between the unaligned ends, and the ends by part 0
-__device__ inline void copy_span(char* dst, const char* src, size_t nbytes, int part) {
-    size_t head = (16 - ((size_t)src & 15)) & 15;
-    if (head > nbytes) head = nbytes;
-    const size_t words = (nbytes - head) / 16;
-    const uint4* a = (const uint4*)(src + head);
-    uint4* b = (uint4*)(dst + head);
-    for (size_t i = (size_t)part * CP_THREADS + threadIdx.x; i < words; i += (size_t)CP_PARTS * CP_THREADS) b[i] = a[i];
-    if (part == 0 && threadIdx.x < 16) {
-        const size_t t = head + words * 16 + threadIdx.x;
-        if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
-        if (t < nbytes) dst[t] = src[t];
-    }
-}
-
-// Pair k (blockIdx.x), part blockIdx.y: the filler's pending visit rows [0, n_moves) and,
-// with trees, its tree (the header and rows [0, n_nodes) of every array) to the hole's
-// places.  The slots are still where they were (puct_compact_swap_kernel runs afterwards).
-__global__ __launch_bounds__(CP_THREADS) void puct_compact_move_kernel(const char* slots, const int32_t* plan, int cap,
-                                                                       int S, int trees, char* ws, uint16_t* pend) {
-    const int k = blockIdx.x, part = blockIdx.y;
-    if (k >= plan[0]) return;
-    const int h = plan[4 + k], f = plan[4 + cap + k];
-    int rows = slot_of(slots, f)->n_moves;
-    rows = rows < 0 ? 0 : (rows > GZ_MAX_GAME_PLIES ? GZ_MAX_GAME_PLIES : rows);
-    const size_t per_slot = (size_t)GZ_MAX_GAME_PLIES * GZ_CELLS * 2;
-    copy_span((char*)pend + h * per_slot, (const char*)pend + f * per_slot, (size_t)rows * GZ_CELLS * 2, part);
-    if (!trees) return;
-    const size_t M = (size_t)S + 1;
-    const char* src = ws + 256 + f * game_stride_for(S);
-    char* dst = ws + 256 + h * game_stride_for(S);
-    int nn = ((const PuctHdr*)src)->n_nodes;
-    nn = nn < 0 ? 0 : (nn > S + 1 ? S + 1 : nn);
-    copy_span(dst, src, sizeof(PuctHdr), part);
-    // W, prior, visits, value, board, child, parent, move, term: bytes per node, as tree_of
-    const int width[9] = {8, 1800, 4, 4, 64, 450, 2, 1, 1};
-    size_t off = sizeof(PuctHdr);
-#pragma unroll
-    for (int a = 0; a < 9; a++) {
-        copy_span(dst + off, src + off, (size_t)width[a] * nn, part);
-        off += width[a] * M;
-    }
-}
-
-// the slot buffers of pair k trade places (16-byte words)
-__global__ __launch_bounds__(CP_THREADS) void puct_compact_swap_kernel(char* slots, const int32_t* plan, int cap) {
-    const int k = blockIdx.x, part = blockIdx.y;
-    if (k >= plan[0]) return;
-    const size_t sb = slot_stride_bytes();
-    uint4* a = (uint4*)(slots + plan[4 + k] * sb);
-    uint4* b = (uint4*)(slots + plan[4 + cap + k] * sb);
-    for (size_t i = (size_t)part * CP_THREADS + threadIdx.x; i < sb / 16; i += (size_t)CP_PARTS * CP_THREADS) {
-        const uint4 x = a[i], y = b[i];
-        a[i] = y;
-        b[i] = x;
-    }
-}
-
-// ---------------------------------------------------------------- the match (two networks)
-// gz_puct_match_run (the header comment has the scheme).  Side A is index 0, B index 1;
-// A plays black in game g iff ((g ^ parity) & 1) == 0, and the mover's side evaluates
-// every leaf of its search.
-__device__ inline int match_side(int64_t game_id, int player, int parity) {
-    const bool a_black = (((int)(game_id & 1) ^ parity) & 1) == 0;
-    return (player == 1) == a_black ? 0 : 1;
-}
-
-// Once per ply, one workgroup over the first n slots in tiles of 1024 (the ballot and
-// prefix scheme of puct_compact_plan_kernel): side[s] = the mover's side or -1 for an idle
-// slot, row_of[s] = the slot's rank among the slots of its side in ascending slot order,
-// count[0..1] = the slots per side.  An idle slot's board is marked over, so the search
-// leaves it alone (no leaf, no backup, move -1) whatever its prior and value rows hold.
-__global__ __launch_bounds__(1024) void puct_match_plan_kernel(const char* slots, int n, int parity,
-                                                               gz_board_state* boards, int32_t* side,
-                                                               int32_t* row_of, int32_t* count) {
-    __shared__ int wsum[2][16];
-    __shared__ int carry[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry[0] = carry[1] = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < n; t0 += 1024) {
-        const int s = t0 + tid;
-        int sd = -1;
-        if (s < n) {
-            const SlotHeader* h = slot_of(slots, s);
-            if (h->game_id < h->game_id_end) sd = match_side(h->game_id, h->player, parity);
-            else boards[s].over = 1;
-        }
-        const uint64_t m0 = __ballot(sd == 0), m1 = __ballot(sd == 1);
-        if (lane == 0) {
-            wsum[0][wave] = __popcll(m0);
-            wsum[1][wave] = __popcll(m1);
-        }
-        __syncthreads();
-        int b0 = carry[0], b1 = carry[1];
-        for (int w = 0; w < wave; w++) {
-            b0 += wsum[0][w];
-            b1 += wsum[1][w];
-        }
-        const uint64_t below = (1ull << lane) - 1;
-        if (s < n) {
-            side[s] = sd;
-            row_of[s] = sd == 0 ? b0 + __popcll(m0 & below) : (sd == 1 ? b1 + __popcll(m1 & below) : 0);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 0; w < 16; w++) {
-                carry[0] += wsum[0][w];
-                carry[1] += wsum[1][w];
-            }
-        }
-        __syncthreads();
-    }
-    if (tid < 2) count[tid] = carry[tid];
-}
-
-// leaf row s (64 bytes, four 16-byte words) -> row row_of[s] of its side's packed leaves
-__global__ __launch_bounds__(256) void puct_match_gather_kernel(const uint32_t* leaves, int n, const int32_t* side,
-                                                                const int32_t* row_of, uint32_t* packed0,
-                                                                uint32_t* packed1) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int s = i >> 2, q = i & 3;
-    if (s >= n) return;
-    const int sd = side[s];
-    if (sd < 0) return;
-    uint4* dst = (uint4*)(sd == 0 ? packed0 : packed1);
-    dst[(size_t)row_of[s] * 4 + q] = ((const uint4*)leaves)[(size_t)s * 4 + q];
-}
-
-// One wave per slot: row row_of[s] of its side's packed prior (225 fp64) and value -> slot
-// row s of the round buffers (rows are 1800 bytes apart: 8-byte words).
-__global__ __launch_bounds__(256) void puct_match_scatter_kernel(int n, const int32_t* side, const int32_t* row_of,
-                                                                 const double* prior0, const double* prior1,
-                                                                 const float* value0, const float* value1,
-                                                                 double* prior, float* value) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (s >= n) return;
-    const int sd = side[s];
-    if (sd < 0) return;
-    const size_t r = (size_t)row_of[s];
-    const double* src = (sd == 0 ? prior0 : prior1) + r * GZ_CELLS;
-    double* dst = prior + (size_t)s * GZ_CELLS;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        if (lane + WAVE * k < GZ_CELLS) dst[lane + WAVE * k] = src[lane + WAVE * k];
-    if (lane == 0) value[s] = (sd == 0 ? value0 : value1)[r];
-}
-
-// gz_puct_match_results: one thread per record
-__global__ __launch_bounds__(256) void puct_match_results_kernel(const gz_record* records, int n, int parity,
-                                                                 int64_t base, int n_games,
-                                                                 gz_puct_match_tally* tally, int8_t* result) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool in = i < n;
-    int first = 0, res = 0, a_black = 0;
-    if (in) {
-        const gz_record& r = records[i];
-        if (r.ply == 0) {  // the mover is black, z black's result
-            first = 1;
-            a_black = match_side(r.game_id, 1, parity) == 0;
-            res = a_black ? r.z : -r.z;
-            const int64_t k = r.game_id - base;
-            if (result && k >= 0 && k < n_games) result[k] = (int8_t)res;
-        }
-    }
-    // (one atomic per wave and field)
-    unsigned long long* t = (unsigned long long*)tally;
-    const unsigned long long c[9] = {
-        (unsigned long long)__popcll(__ballot(first)),
-        (unsigned long long)__popcll(__ballot(first && res > 0)),
-        (unsigned long long)__popcll(__ballot(first && res < 0)),
-        (unsigned long long)__popcll(__ballot(first && res == 0)),
-        (unsigned long long)__popcll(__ballot(first && res > 0 && a_black)),
-        (unsigned long long)__popcll(__ballot(first && res > 0 && !a_black)),
-        (unsigned long long)__popcll(__ballot(first && res < 0 && !a_black)),
-        (unsigned long long)__popcll(__ballot(first && res < 0 && a_black)),
-        (unsigned long long)__popcll(__ballot(in))};
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int f = 0; f < 9; f++)
-            if (c[f]) atomicAdd(t + f, c[f]);
-    }
-}
-
-inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
-
-int check_alpha(const char* who, double alpha) {
-    if (!(alpha >= 1e-3 && alpha <= 1e3))  // (a NaN fails both)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": noise alpha must be finite and in [1e-3, 1e3]");
-    return GZ_OK;
-}
-
-// The root noise p asks for.  Only with GZ_PUCT_ROOT_NOISE set is p a
-// gz_puct_noise_params; without it nothing past the 32 bytes of gz_puct_params is read.
-int read_noise(const char* who, const gz_puct_params* p, PuctNoise& nz) {
-    nz.alpha = 0.0;
-    nz.eps = 0.0;
-    nz.seed = p->seed;
-    nz.on = 0;
-    nz.pad = 0;
-    if (!(p->flags & GZ_PUCT_ROOT_NOISE)) return GZ_OK;
-    const gz_puct_noise_params* q = (const gz_puct_noise_params*)p;
-    int rc = check_alpha(who, q->noise_alpha);
-    if (rc) return rc;
-    if (!(q->noise_eps >= 0.0 && q->noise_eps <= 1.0))
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": noise eps must be in [0, 1]");
-    nz.alpha = q->noise_alpha;
-    nz.eps = q->noise_eps;
-    nz.on = 1;
-    return GZ_OK;
 }
 
 // The leaves per round p asks for: 0 without GZ_PUCT_LEAF_BATCH (nothing past the noise
@@ -1628,130 +1096,26 @@ int leaves_of(const void* ws) {
     return it == g_batch_leaves.end() ? 0 : it->second;
 }
 
-int backup_impl(void* ws, int32_t n, int32_t S, const double* d_prior, const float* d_value, const PuctNoise& nz,
-                void* stream) {
+}  // namespace
+
+// ---------------------------------------------------------------- the host steps the match borrows
+namespace gz {
+
+int gz_internal_puct_backup(void* ws, int32_t n, int32_t S, const double* d_prior, const float* d_value,
+                            const PuctNoise& nz, void* stream) {
     puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_prior, d_value, nz);
     return gz_check_launch("puct_backup_kernel");
 }
 
-// GZ_PUCT_LEAF_SYM (gz_sym.h, gz_pvsym.hip): t is the extra region behind the flag-clear
-// workspace, one byte per row of the round buffers; nullptr with the flag clear, and then
-// neither step launches anything.  sym_leaves turns the round's leaf rows in place -- the
-// select, begin and round kernels rewrite every row of every round and nothing but the
-// forward reads the buffer (the backup kernels take no leaf pointer; a node's board is in
-// its tree) -- and sym_priors maps the forward's prior rows back before the backup, which
-// reads nothing else of the 225-wide buffers.
-struct LeafSym {
-    uint8_t* t;
-    uint64_t seed;
-};
-
-LeafSym leaf_sym(const gz_puct_params* p, void* ws, size_t flag_clear_bytes) {
-    LeafSym ls;
-    ls.t = (p->flags & GZ_PUCT_LEAF_SYM) ? (uint8_t*)ws + flag_clear_bytes : nullptr;
-    ls.seed = p->seed;
-    return ls;
-}
-
-int sym_leaves(const LeafSym& ls, uint32_t* leaves, int32_t rows, void* stream) {
-    if (!ls.t) return GZ_OK;
-    return gz_internal_sym_boards(leaves, leaves, rows, nullptr, nullptr, ls.seed, ls.t, stream);
-}
-
-int sym_priors(const LeafSym& ls, double* prior, int32_t rows, void* stream) {
-    if (!ls.t) return GZ_OK;
-    return gz_internal_sym_rows(nullptr, nullptr, prior, rows, nullptr, ls.t, stream);
-}
-
-struct RoundBufs {
-    uint32_t* leaves;
-    int32_t* active;
-    float *logits, *probs, *value;
-    double* prior;
-    void* pvws;
-};
-
-// reroot()'s LDS: map and list, int16 [S+1] each
-size_t remap_bytes(int32_t S) { return (4 * ((size_t)S + 1) + 15) & ~(size_t)15; }
-
-size_t rounds_offset(int32_t n, int32_t S) { return 256 + (size_t)n * game_stride_for(S); }
-
-// the round buffers of n rows from p on
-RoundBufs carve_rows(char* p, size_t n) {
-    RoundBufs r;
-    r.leaves = (uint32_t*)p;
-    p += al256((size_t)n * 64);
-    r.active = (int32_t*)p;
-    p += al256((size_t)n * 4);
-    r.logits = (float*)p;
-    p += al256((size_t)n * 900);
-    r.probs = (float*)p;
-    p += al256((size_t)n * 900);
-    r.value = (float*)p;
-    p += al256((size_t)n * 4);
-    r.prior = (double*)p;
-    p += al256((size_t)n * 1800);
-    r.pvws = p;
-    return r;
-}
-
-// (n: the game count the workspace was sized for -- a search of fewer games on it finds
-// every buffer where the full one does)
-RoundBufs carve_rounds(void* ws, int32_t n, int32_t S) { return carve_rows((char*)ws + rounds_offset(n, S), n); }
-
-// the batched workspace after the trees: pend i16 [n][K], the remaining count, then the
-// round buffers of n K rows
-struct BatchBufs {
-    int16_t* pend;
-    int32_t* left;
-    RoundBufs r;
-};
-
-size_t batch_pend_bytes(int32_t n, int32_t K) { return al256((size_t)n * K * 2); }
-
-BatchBufs carve_batch(void* ws, int32_t n, int32_t S, int32_t K) {
-    char* p = (char*)ws + rounds_offset(n, S);
-    BatchBufs b;
-    b.pend = (int16_t*)p;
-    p += batch_pend_bytes(n, K);
-    b.left = (int32_t*)p;
-    p += 256;
-    b.r = carve_rows(p, (size_t)n * K);
-    return b;
-}
-
-int check_S(const char* who, int32_t n, int32_t S) {
-    if (S < 1 || S > GZ_MAX_SIMULATIONS)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": num_simulations out of range [1, 4095]");
-    if (n < 0) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n < 0");
-    return GZ_OK;
-}
-
-int finish_impl(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
-                gz_search_stats* d_stats, void* stream) {
+int gz_internal_puct_finish(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
+                            gz_search_stats* d_stats, void* stream) {
     puct_finish_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q, d_stats);
     return gz_check_launch("puct_finish_kernel");
 }
 
-// n_cap: the game count that carved the workspace (the place of pend), n <= n_cap games run
-int select_batch_impl(void* ws, int32_t n_cap, int32_t n, int32_t S, int32_t K, uint32_t* d_leaves, int32_t* d_active,
-                      void* stream) {
-    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n_cap, S));
-    puct_select_batch_kernel<<<n, WAVE, 2 * ((size_t)S + 1), as_stream(stream)>>>((char*)ws, n, S, K, pend, d_leaves,
-                                                                                   d_active);
-    return gz_check_launch("puct_select_batch_kernel");
-}
-
-int backup_batch_impl(void* ws, int32_t n_cap, int32_t n, int32_t S, int32_t K, const double* d_prior,
-                      const float* d_value, const PuctNoise& nz, void* stream) {
-    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n_cap, S));
-    puct_backup_batch_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, K, pend, d_prior, d_value, nz);
-    return gz_check_launch("puct_backup_batch_kernel");
-}
-
-// gz_puct_begin on a workspace carved for n_cap games, of which the first n begin
-int begin_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n_cap, int32_t n,
-               const gz_puct_params* p, void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream) {
+int gz_internal_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n_cap, int32_t n,
+                           const gz_puct_params* p, void* d_workspace, uint32_t* d_leaves, int32_t* d_active,
+                           void* stream) {
     if (!p) return gz_fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
     int rc = check_S("gz_puct_begin", n, p->num_simulations);
     if (rc) return rc;
@@ -1776,6 +1140,72 @@ int begin_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_
     return gz_check_launch("puct_begin_kernel");
 }
 
+int gz_internal_puct_stash_commit(void* d_slots, int32_t n, const SelfplayWs& w, gz_record* d_records,
+                                  int32_t record_cap, uint16_t* d_visits, gz_selfplay_counters* d_counters,
+                                  void* stream) {
+    puct_stash_kernel<<<n, WAVE, 0, as_stream(stream)>>>(w.boards, w.moves, w.visits, n, w.pend);
+    int rc = gz_check_launch("puct_stash_kernel");
+    if (rc) return rc;
+    return gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
+                                       d_visits, stream);
+}
+
+}  // namespace gz
+
+namespace {
+
+// reroot()'s LDS: map and list, int16 [S+1] each
+size_t remap_bytes(int32_t S) { return (4 * ((size_t)S + 1) + 15) & ~(size_t)15; }
+
+// the batched workspace after the trees: pend i16 [n][K], the remaining count, then the
+// round buffers of n K rows
+struct BatchBufs {
+    int16_t* pend;
+    int32_t* left;
+    RoundBufs r;
+};
+
+size_t batch_pend_bytes(int32_t n, int32_t K) { return al256((size_t)n * K * 2); }
+
+BatchBufs carve_batch(void* ws, int32_t n, int32_t S, int32_t K) {
+    char* p = (char*)ws + rounds_offset(n, S);
+    BatchBufs b;
+    b.pend = (int16_t*)p;
+    p += batch_pend_bytes(n, K);
+    b.left = (int32_t*)p;
+    p += 256;
+    b.r = carve_rows(p, (size_t)n * K);
+    return b;
+}
+
+// n_cap: the game count that carved the workspace (the place of pend), n <= n_cap games run
+int select_batch_impl(void* ws, int32_t n_cap, int32_t n, int32_t S, int32_t K, uint32_t* d_leaves, int32_t* d_active,
+                      void* stream) {
+    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n_cap, S));
+    puct_select_batch_kernel<<<n, WAVE, 2 * ((size_t)S + 1), as_stream(stream)>>>((char*)ws, n, S, K, pend, d_leaves,
+                                                                                   d_active);
+    return gz_check_launch("puct_select_batch_kernel");
+}
+
+int backup_batch_impl(void* ws, int32_t n_cap, int32_t n, int32_t S, int32_t K, const double* d_prior,
+                      const float* d_value, const PuctNoise& nz, void* stream) {
+    int16_t* pend = (int16_t*)((char*)ws + rounds_offset(n_cap, S));
+    puct_backup_batch_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, K, pend, d_prior, d_value, nz);
+    return gz_check_launch("puct_backup_batch_kernel");
+}
+
+// One evaluation of a round's rows: the leaf rows turned (GZ_PUCT_LEAF_SYM), the forward,
+// the prior rows turned back.
+int eval_rows(const LeafSym& ls, const float* d_pv_weights, const RoundBufs& r, int32_t rows, int32_t precision,
+              void* stream) {
+    int rc = sym_leaves(ls, r.leaves, rows, stream);
+    if (rc) return rc;
+    rc = gz_pv_forward(d_pv_weights, r.leaves, rows, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws, precision,
+                       stream);
+    if (rc) return rc;
+    return sym_priors(ls, r.prior, rows, stream);
+}
+
 // The batched search: the root round, ceil(S/K) rounds of n K rows, then one int32 read
 // back -- the largest remaining count -- and ceil(left/K) more rounds until it is 0.
 // Every unfinished game completes at least one simulation per round, so the count falls.
@@ -1790,7 +1220,7 @@ int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids,
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
     if (rc) return rc;
-    rc = begin_impl(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
+    rc = gz_internal_puct_begin(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
     if (rc) return rc;
     int todo = 1 + (S + K - 1) / K;
     bool root = true;
@@ -1801,12 +1231,7 @@ int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids,
                 if (rc) return rc;
             }
             root = false;
-            rc = sym_leaves(ls, r.leaves, n * K, stream);
-            if (rc) return rc;
-            rc = gz_pv_forward(d_pv_weights, r.leaves, n * K, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
-                               p->precision, stream);
-            if (rc) return rc;
-            rc = sym_priors(ls, r.prior, n * K, stream);
+            rc = eval_rows(ls, d_pv_weights, r, n * K, p->precision, stream);
             if (rc) return rc;
             rc = backup_batch_impl(ws, n_cap, n, S, K, r.prior, r.value, nz, stream);
             if (rc) return rc;
@@ -1823,7 +1248,7 @@ int search_batch_impl(const gz_board_state* d_boards, const int64_t* d_game_ids,
             return gz_fail(GZ_ERR_HIP, std::string("gz_puct_search: the remaining count: ") + hipGetErrorString(e));
         todo = (left + K - 1) / K;
     }
-    return finish_impl(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
+    return gz_internal_puct_finish(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
 }
 
 // The search of the first n games on a workspace sized and carved for n_cap (n <= n_cap):
@@ -1844,32 +1269,26 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
     if (rc) return rc;
-    rc = begin_impl(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
+    rc = gz_internal_puct_begin(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
     if (rc) return rc;
     for (int round = 0; round <= S; round++) {
         if (round > 0) {
             rc = gz_puct_select(ws, n, S, r.leaves, r.active, stream);
             if (rc) return rc;
         }
-        rc = sym_leaves(ls, r.leaves, n, stream);
+        rc = eval_rows(ls, d_pv_weights, r, n, p->precision, stream);
         if (rc) return rc;
-        rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
-                           p->precision, stream);
-        if (rc) return rc;
-        rc = sym_priors(ls, r.prior, n, stream);
-        if (rc) return rc;
-        rc = backup_impl(ws, n, S, r.prior, r.value, nz, stream);
+        rc = gz_internal_puct_backup(ws, n, S, r.prior, r.value, nz, stream);
         if (rc) return rc;
     }
-    return finish_impl(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
+    return gz_internal_puct_finish(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
 }
 
 int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     if (!p) return gz_fail(GZ_ERR_ARG, std::string(who) + ": params is NULL");
     int rc = check_S(who, n, p->num_simulations);
     if (rc) return rc;
-    if (p->precision != GZ_PV_FP32 && p->precision != GZ_PV_F16X3 && p->precision != GZ_PV_F16)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
+    if (!known_precision(p->precision)) return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
     PuctNoise nz;
     rc = read_noise(who, p, nz);
     if (rc) return rc;
@@ -1882,63 +1301,25 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     return check_rows(who, n, K);
 }
 
-struct SelfplayWs {
-    gz_board_state* boards;
-    int64_t* gids;
-    int32_t* moves;
-    gz_search_stats* stats;
-    int32_t* visits;
-    double* root_q;
-    uint16_t* pend;
-    void* puct;
-};
-
-size_t pend_bytes(int32_t n_slots) { return al256((size_t)n_slots * GZ_MAX_GAME_PLIES * GZ_CELLS * 2); }
-
-SelfplayWs carve_selfplay(void* ws, int32_t n) {
-    char* p = (char*)ws;
-    SelfplayWs w;
-    w.boards = (gz_board_state*)p;
-    p += al256((size_t)n * sizeof(gz_board_state));
-    w.gids = (int64_t*)p;
-    p += al256((size_t)n * 8);
-    w.moves = (int32_t*)p;
-    p += al256((size_t)n * 4);
-    w.stats = (gz_search_stats*)p;
-    p += al256((size_t)n * sizeof(gz_search_stats));
-    w.visits = (int32_t*)p;
-    p += al256((size_t)n * 900);
-    w.root_q = (double*)p;
-    p += al256((size_t)n * 8);
-    w.pend = (uint16_t*)p;
-    p += pend_bytes(n);
-    w.puct = p;
-    return w;
-}
-
 // gz_selfplay_puct_run(_active): n_slots sized and carved the workspace, the first n plays
 int run_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, const gz_puct_params* p,
              const float* d_pv_weights, void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
              uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
     int rc = check_search_args(who, p, n_slots);
     if (rc) return rc;
-    if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
-        !d_pv_weights || !d_visits)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": bad arguments");
-    if (n < 1 || n > n_slots) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n_active out of range [1, n_slots]");
+    rc = check_selfplay_args(who, d_slots, n_slots, n_plies, d_counters, d_records, record_cap, d_workspace,
+                             d_pv_weights != nullptr, d_visits);
+    if (rc) return rc;
+    rc = check_active(who, n, n_slots);
+    if (rc) return rc;
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
-    hipStream_t st = as_stream(stream);
     for (int it = 0; it < n_plies; it++) {
         rc = gz_selfplay_boards(d_slots, n, p->num_simulations, w.boards, w.gids, stream);
         if (rc) return rc;
         rc = search_impl(w.boards, w.gids, n_slots, n, p, d_pv_weights, w.puct, w.moves, w.visits, w.root_q, w.stats,
                          stream);
         if (rc) return rc;
-        puct_stash_kernel<<<n, WAVE, 0, st>>>(w.boards, w.moves, w.visits, n, w.pend);
-        rc = gz_check_launch("puct_stash_kernel");
-        if (rc) return rc;
-        rc = gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
-                                         d_visits, stream);
+        rc = gz_internal_puct_stash_commit(d_slots, n, w, d_records, record_cap, d_visits, d_counters, stream);
         if (rc) return rc;
     }
     return GZ_OK;
@@ -1950,15 +1331,16 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
                 int32_t record_cap, uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
     int rc = check_search_args(who, p, n_slots);
     if (rc) return rc;
-    if (!d_slots || n_slots <= 0 || n_rounds < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
-        !d_pv_weights || !d_visits)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": bad arguments");
+    rc = check_selfplay_args(who, d_slots, n_slots, n_rounds, d_counters, d_records, record_cap, d_workspace,
+                             d_pv_weights != nullptr, d_visits);
+    if (rc) return rc;
     int K;
     rc = read_leaves(who, p, K);
     if (rc) return rc;
     if (K > 1)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": tree reuse with leaves_per_round > 1 is not supported");
-    if (n < 1 || n > n_slots) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n_active out of range [1, n_slots]");
+    rc = check_active(who, n, n_slots);
+    if (rc) return rc;
     const int S = p->num_simulations;
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
     const RoundBufs r = carve_rounds(w.puct, n_slots, S);
@@ -1981,121 +1363,9 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
         puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, cap, (char*)w.puct, r.leaves, r.active);
         rc = gz_check_launch("puct_round_kernel");
         if (rc) return rc;
-        rc = sym_leaves(ls, r.leaves, n, stream);
+        rc = eval_rows(ls, d_pv_weights, r, n, p->precision, stream);
         if (rc) return rc;
-        rc = gz_pv_forward(d_pv_weights, r.leaves, n, nullptr, r.logits, r.value, r.probs, r.prior, r.pvws,
-                           p->precision, stream);
-        if (rc) return rc;
-        rc = sym_priors(ls, r.prior, n, stream);
-        if (rc) return rc;
-        rc = backup_impl(w.puct, n, S, r.prior, r.value, nz, stream);
-        if (rc) return rc;
-    }
-    return GZ_OK;
-}
-
-// the match workspace after the self-play workspace of n slots: side i32 [n], row_of i32
-// [n], the two counts (256 bytes), then per side the round buffers of n rows
-struct MatchWs {
-    int32_t *side, *row_of, *count;
-    RoundBufs pk[2];
-};
-
-size_t rows_bytes(int32_t n) {
-    const size_t m = (size_t)n;
-    return al256(m * 64) + al256(m * 4) + 2 * al256(m * 900) + al256(m * 4) + al256(m * 1800) + gz_pv_workspace_bytes(n);
-}
-
-MatchWs carve_match(void* ws, int32_t n, int32_t S) {
-    char* p = (char*)ws + gz_selfplay_puct_workspace_bytes(n, S);
-    MatchWs m;
-    m.side = (int32_t*)p;
-    p += al256((size_t)n * 4);
-    m.row_of = (int32_t*)p;
-    p += al256((size_t)n * 4);
-    m.count = (int32_t*)p;
-    p += 256;
-    m.pk[0] = carve_rows(p, n);
-    p += rows_bytes(n);
-    m.pk[1] = carve_rows(p, n);
-    return m;
-}
-
-bool known_precision(int32_t x) { return x == GZ_PV_FP32 || x == GZ_PV_F16X3 || x == GZ_PV_F16; }
-
-// gz_puct_match_run: run_impl with the routed evaluation in place of the one forward
-int match_impl(void* d_slots, int32_t n_slots, int32_t n, const gz_puct_match_params* mp, void* d_workspace,
-               int32_t n_plies, gz_record* d_records, int32_t record_cap, uint16_t* d_visits,
-               gz_selfplay_counters* d_counters, void* stream) {
-    const char* who = "gz_puct_match_run";
-    if (!mp || !mp->search) return gz_fail(GZ_ERR_ARG, std::string(who) + ": params is NULL");
-    const gz_puct_params* p = mp->search;
-    int rc = check_S(who, n_slots, p->num_simulations);
-    if (rc) return rc;
-    if (p->flags & GZ_PUCT_LEAF_BATCH)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": leaf batching is not supported in a match");
-    if (p->flags & GZ_PUCT_PLAYOUT_CAP)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the playout cap is not supported in a match");
-    PuctNoise nz;
-    rc = read_noise(who, p, nz);
-    if (rc) return rc;
-    if (!known_precision(mp->precision[0]) || !known_precision(mp->precision[1]))
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
-    if (mp->a_black_parity != 0 && mp->a_black_parity != 1)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": a_black_parity must be 0 or 1");
-    if (!d_slots || n_slots <= 0 || n_plies < 0 || !d_counters || !d_records || record_cap < 0 || !d_workspace ||
-        !mp->d_weights[0] || !mp->d_weights[1] || !d_visits)
-        return gz_fail(GZ_ERR_ARG, std::string(who) + ": bad arguments");
-    if (n < 1 || n > n_slots) return gz_fail(GZ_ERR_ARG, std::string(who) + ": n_active out of range [1, n_slots]");
-    const int S = p->num_simulations;
-    const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
-    const RoundBufs r = carve_rounds(w.puct, n_slots, S);
-    const MatchWs m = carve_match(d_workspace, n_slots, S);
-    // (both sides under the same t: the slot rows turn before the gather and back after the scatter)
-    const LeafSym ls = leaf_sym(p, d_workspace, gz_puct_match_workspace_bytes(n_slots, S));
-    hipStream_t st = as_stream(stream);
-    for (int it = 0; it < n_plies; it++) {
-        rc = gz_selfplay_boards(d_slots, n, S, w.boards, w.gids, stream);
-        if (rc) return rc;
-        puct_match_plan_kernel<<<1, 1024, 0, st>>>((const char*)d_slots, n, mp->a_black_parity, w.boards, m.side,
-                                                   m.row_of, m.count);
-        rc = gz_check_launch("puct_match_plan_kernel");
-        if (rc) return rc;
-        rc = begin_impl(w.boards, w.gids, n_slots, n, p, w.puct, r.leaves, r.active, stream);
-        if (rc) return rc;
-        for (int round = 0; round <= S; round++) {
-            if (round > 0) {
-                rc = gz_puct_select(w.puct, n, S, r.leaves, r.active, stream);
-                if (rc) return rc;
-            }
-            rc = sym_leaves(ls, r.leaves, n, stream);
-            if (rc) return rc;
-            puct_match_gather_kernel<<<(n * 4 + 255) / 256, 256, 0, st>>>(r.leaves, n, m.side, m.row_of,
-                                                                          m.pk[0].leaves, m.pk[1].leaves);
-            rc = gz_check_launch("puct_match_gather_kernel");
-            if (rc) return rc;
-            for (int sd = 0; sd < 2; sd++) {
-                const RoundBufs& k = m.pk[sd];
-                rc = gz_pv_forward(mp->d_weights[sd], k.leaves, n, m.count + sd, k.logits, k.value, k.probs,
-                                   k.prior, k.pvws, mp->precision[sd], stream);
-                if (rc) return rc;
-            }
-            puct_match_scatter_kernel<<<(n + 3) / 4, 256, 0, st>>>(n, m.side, m.row_of, m.pk[0].prior, m.pk[1].prior,
-                                                                   m.pk[0].value, m.pk[1].value, r.prior, r.value);
-            rc = gz_check_launch("puct_match_scatter_kernel");
-            if (rc) return rc;
-            rc = sym_priors(ls, r.prior, n, stream);
-            if (rc) return rc;
-            rc = backup_impl(w.puct, n, S, r.prior, r.value, nz, stream);
-            if (rc) return rc;
-        }
-        rc = finish_impl(w.puct, n, S, w.moves, w.visits, w.root_q, w.stats, stream);
-        if (rc) return rc;
-        puct_stash_kernel<<<n, WAVE, 0, st>>>(w.boards, w.moves, w.visits, n, w.pend);
-        rc = gz_check_launch("puct_stash_kernel");
-        if (rc) return rc;
-        rc = gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
-                                         d_visits, stream);
+        rc = gz_internal_puct_backup(w.puct, n, S, r.prior, r.value, nz, stream);
         if (rc) return rc;
     }
     return GZ_OK;
@@ -2110,14 +1380,12 @@ size_t gz_puct_tree_bytes(int32_t S) { return S < 0 ? 0 : export_bytes_for(S); }
 size_t gz_puct_workspace_bytes(int32_t n, int32_t S) {
     if (n < 1) n = 1;
     if (S < 0) S = 0;
-    const size_t m = (size_t)n;
-    return rounds_offset(n, S) + al256(m * 64) + al256(m * 4) + 2 * al256(m * 900) + al256(m * 4) + al256(m * 1800) +
-           gz_pv_workspace_bytes(n);
+    return rounds_offset(n, S) + rows_bytes((size_t)n);
 }
 
 int gz_puct_begin(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
                   void* d_workspace, uint32_t* d_leaves, int32_t* d_active, void* stream) {
-    return begin_impl(d_boards, d_game_ids, n, n, p, d_workspace, d_leaves, d_active, stream);
+    return gz_internal_puct_begin(d_boards, d_game_ids, n, n, p, d_workspace, d_leaves, d_active, stream);
 }
 
 int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, int32_t* d_active, void* stream) {
@@ -2141,7 +1409,7 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prio
     nz.on = -1;  // as gz_puct_begin stored it in the workspace
     const int K = leaves_of(d_workspace);
     if (K > 0) return backup_batch_impl(d_workspace, n, n, S, K, d_prior, d_value, nz, stream);
-    return backup_impl(d_workspace, n, S, d_prior, d_value, nz, stream);
+    return gz_internal_puct_backup(d_workspace, n, S, d_prior, d_value, nz, stream);
 }
 
 int gz_puct_remaining(void* d_workspace, int32_t n, int32_t S, int32_t* d_remaining, void* stream) {
@@ -2161,9 +1429,7 @@ size_t gz_puct_batch_workspace_bytes(int32_t n, int32_t S, int32_t K) {
     if (S < 0) S = 0;
     if (K < 1) K = 1;
     if (K > GZ_PUCT_MAX_LEAVES) K = GZ_PUCT_MAX_LEAVES;
-    const size_t m = (size_t)n * K;
-    return rounds_offset(n, S) + batch_pend_bytes(n, K) + 256 + al256(m * 64) + al256(m * 4) + 2 * al256(m * 900) +
-           al256(m * 4) + al256(m * 1800) + gz_pv_workspace_bytes((int32_t)m);
+    return rounds_offset(n, S) + batch_pend_bytes(n, K) + 256 + rows_bytes((size_t)n * K);
 }
 
 int gz_puct_finish(void* d_workspace, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
@@ -2172,7 +1438,7 @@ int gz_puct_finish(void* d_workspace, int32_t n, int32_t S, int32_t* d_moves, in
     if (rc) return rc;
     if (n > 0 && (!d_workspace || !d_moves)) return gz_fail(GZ_ERR_ARG, "gz_puct_finish: bad arguments");
     if (n == 0) return GZ_OK;
-    return finish_impl(d_workspace, n, S, d_moves, d_visits, d_root_q, nullptr, stream);
+    return gz_internal_puct_finish(d_workspace, n, S, d_moves, d_visits, d_root_q, nullptr, stream);
 }
 
 int gz_puct_search(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, const gz_puct_params* p,
@@ -2198,16 +1464,12 @@ int gz_puct_trees(const void* d_workspace, int32_t n, int32_t S, void* d_out, vo
 
 size_t gz_selfplay_puct_workspace_bytes(int32_t n_slots, int32_t S) {
     if (n_slots < 1) n_slots = 1;
-    const size_t m = (size_t)n_slots;
-    return al256(m * sizeof(gz_board_state)) + al256(m * 8) + al256(m * 4) + al256(m * sizeof(gz_search_stats)) +
-           al256(m * 900) + al256(m * 8) + pend_bytes(n_slots) + gz_puct_workspace_bytes(n_slots, S);
+    return selfplay_head_bytes(n_slots) + gz_puct_workspace_bytes(n_slots, S);
 }
 
 size_t gz_selfplay_puct_batch_workspace_bytes(int32_t n_slots, int32_t S, int32_t K) {
     if (n_slots < 1) n_slots = 1;
-    const size_t m = (size_t)n_slots;
-    return al256(m * sizeof(gz_board_state)) + al256(m * 8) + al256(m * 4) + al256(m * sizeof(gz_search_stats)) +
-           al256(m * 900) + al256(m * 8) + pend_bytes(n_slots) + gz_puct_batch_workspace_bytes(n_slots, S, K);
+    return selfplay_head_bytes(n_slots) + gz_puct_batch_workspace_bytes(n_slots, S, K);
 }
 
 int gz_selfplay_puct_run_active(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_params* p,
@@ -2268,71 +1530,11 @@ int gz_selfplay_puct_layout(int32_t n_slots, int32_t S, int32_t K, size_t out[4]
     if (rc) return rc;
     if (n_slots < 1 || K < 0 || K > GZ_PUCT_MAX_LEAVES || !out)
         return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_layout: bad arguments");
-    const uintptr_t base = 4096;  // (any address: only the differences are used)
-    const SelfplayWs w = carve_selfplay((void*)base, n_slots);
-    out[0] = (size_t)((uintptr_t)w.pend - base);
-    out[1] = (size_t)((uintptr_t)w.puct - base);
+    out[0] = part_offset(SELFPLAY_WIDTH, n_slots, SELFPLAY_PARTS - 1);  // pend, the last part
+    out[1] = selfplay_head_bytes(n_slots);
     out[2] = out[1] + 256;
     out[3] = game_stride_for(S);
     return GZ_OK;
-}
-
-size_t gz_selfplay_puct_compact_workspace_bytes(int32_t n_slots) {
-    return al256(16 + 2 * (size_t)(n_slots > 0 ? n_slots : 0) * 4);
-}
-
-int gz_selfplay_puct_compact(void* d_slots, int32_t n_slots, int32_t n_active, int32_t S, int32_t K,
-                             int32_t move_trees, void* d_puct_workspace, int32_t* d_order, int32_t* d_n_active,
-                             void* d_workspace, void* stream) {
-    int rc = check_S("gz_selfplay_puct_compact", n_slots, S);
-    if (rc) return rc;
-    if (!d_slots || n_slots < 1 || !d_puct_workspace || !d_order || !d_n_active || !d_workspace)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: bad arguments");
-    if (n_active < 1 || n_active > n_slots)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: n_active out of range [1, n_slots]");
-    if (K < 0 || K > GZ_PUCT_MAX_LEAVES)  // (0: the unbatched search, as PuctCfg.leaves)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: leaves_per_round out of range [0, 32]");
-    if (K > 1 && move_trees)
-        return gz_fail(GZ_ERR_ARG, "gz_selfplay_puct_compact: tree reuse with leaves_per_round > 1 is not supported");
-    const SelfplayWs w = carve_selfplay(d_puct_workspace, n_slots);
-    int32_t* plan = (int32_t*)d_workspace;
-    hipStream_t st = as_stream(stream);
-    puct_compact_plan_kernel<<<1, 1024, 0, st>>>((const char*)d_slots, n_active, n_slots, d_order, d_n_active, plan);
-    rc = gz_check_launch("puct_compact_plan_kernel");
-    if (rc) return rc;
-    const int pairs = n_active / 2;  // at most: the count itself stays on the device
-    if (pairs == 0) return GZ_OK;
-    puct_compact_move_kernel<<<dim3(pairs, CP_PARTS), CP_THREADS, 0, st>>>((const char*)d_slots, plan, n_slots, S,
-                                                                          move_trees ? 1 : 0, (char*)w.puct, w.pend);
-    rc = gz_check_launch("puct_compact_move_kernel");
-    if (rc) return rc;
-    puct_compact_swap_kernel<<<dim3(pairs, CP_PARTS), CP_THREADS, 0, st>>>((char*)d_slots, plan, n_slots);
-    return gz_check_launch("puct_compact_swap_kernel");
-}
-
-size_t gz_puct_match_workspace_bytes(int32_t n_slots, int32_t S) {
-    if (n_slots < 1) n_slots = 1;
-    return gz_selfplay_puct_workspace_bytes(n_slots, S) + 2 * al256((size_t)n_slots * 4) + 256 + 2 * rows_bytes(n_slots);
-}
-
-int gz_puct_match_run(void* d_slots, int32_t n_slots, int32_t n_active, const gz_puct_match_params* mp,
-                      void* d_workspace, int32_t n_plies, gz_record* d_records, int32_t record_cap,
-                      uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
-    return match_impl(d_slots, n_slots, n_active, mp, d_workspace, n_plies, d_records, record_cap, d_visits,
-                      d_counters, stream);
-}
-
-int gz_puct_match_results(const gz_record* d_records, int32_t n_records, int32_t a_black_parity,
-                          int64_t game_id_base, int32_t n_games, gz_puct_match_tally* d_tally, int8_t* d_result,
-                          void* stream) {
-    if (n_records < 0 || n_games < 0 || !d_tally || (n_records > 0 && !d_records))
-        return gz_fail(GZ_ERR_ARG, "gz_puct_match_results: bad arguments");
-    if (a_black_parity != 0 && a_black_parity != 1)
-        return gz_fail(GZ_ERR_ARG, "gz_puct_match_results: a_black_parity must be 0 or 1");
-    if (n_records == 0) return GZ_OK;
-    puct_match_results_kernel<<<(n_records + 255) / 256, 256, 0, as_stream(stream)>>>(
-        d_records, n_records, a_black_parity, game_id_base, n_games, d_tally, d_result);
-    return gz_check_launch("puct_match_results_kernel");
 }
 
 int gz_puct_root_noise(const gz_board_state* d_boards, const int64_t* d_game_ids, int32_t n, uint64_t seed,

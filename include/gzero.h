@@ -354,7 +354,7 @@ int gz_plan_gn_stats(void* d_workspace, int32_t n, int32_t num_simulations, int6
 int gz_selfplay_plan_gn_stats(void* d_workspace, int32_t n_slots, int32_t num_simulations, int64_t* out,
                               int32_t reset, void* stream);
 
-/* ---- network-guided PUCT search (opt-in mode; csrc/gz_puct.hip) ----
+/* ---- network-guided PUCT search (opt-in mode; csrc/gz_puct.hip, gz_puct.h) ----
  * The default search reproduces the reference, which never reads the network's
  * outputs.  In this mode the priors steer selection and the value head replaces
  * the rollout: per simulation the tree is descended by
@@ -374,7 +374,7 @@ int gz_selfplay_plan_gn_stats(void* d_workspace, int32_t n_slots, int32_t num_si
  * d_visits (optional) int32 [n][225] root-child visits; d_root_q (optional) the
  * root's mean value for its side to move, -W[0] / visits[0].
  * Workspace layout, node record (~2.3 KB: 1.9 GB at 4096 games x 200 simulations)
- * and the export layout of gz_puct_trees are documented in csrc/gz_puct.hip. */
+ * and the export layout of gz_puct_trees are documented in csrc/gz_puct.h. */
 typedef struct gz_puct_params {
     int32_t num_simulations; /* S, 1..GZ_MAX_SIMULATIONS */
     int32_t temp_plies;      /* plies (move counts below this) that sample the move from the visits */

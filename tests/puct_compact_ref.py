@@ -1,7 +1,7 @@
-"""Plain-numpy restatement of gz_selfplay_puct_compact (csrc/gz_puct.hip): the
+"""Plain-numpy restatement of gz_selfplay_puct_compact (csrc/gz_puct_compact.hip): the
 hole-filling plan and what it moves, on host copies of the slot buffer and of the
 self-play workspace.  Layouts: SlotHeader (csrc/gz_search.h), PuctHdr and the tree
-arrays (the head of csrc/gz_puct.hip), offsets from gz_selfplay_puct_layout."""
+arrays (csrc/gz_puct.h), offsets from gz_selfplay_puct_layout."""
 import numpy as np
 
 PEND_SLOT_BYTES = 200 * 225 * 2  # uint16 [200][225] per slot

@@ -153,6 +153,40 @@ def test_step_api_trees_equal_the_reference(S, K):
         assert max(r.t.count[k] - r.t.count[0] for r in live for k in range(len(r.t.parent))) >= 2  # depth > 1
 
 
+@pytest.mark.parametrize("K", [0, 3])
+def test_a_select_without_the_backup_before_it_changes_nothing(K):
+    """A node still waits for its evaluation (header.pending): the select step leaves every
+    row inactive and empty and every tree byte as it was.  K = 0 is the flag-clear search
+    (puct_select_kernel), where the root and every later leaf wait that way; with leaf
+    batching only the root does."""
+    S = 4
+    states = np.concatenate([_state(_thinned(41, 1)), _state(_thinned(30, 2))])
+    evals = [make_synth(), make_synth()]
+    st = device.PuctStepper(states, [11, 12], _flagged(S, K) if K else device.puct_params(S, C_PUCT, 0, SEED))
+    per = max(K, 1)
+
+    def select_again():
+        before = [_tree_bytes(t) for t in st.trees()]
+        st.select()
+        rows, active = st.leaves()
+        assert not active.any() and not rows.any()
+        assert [_tree_bytes(t) for t in st.trees()] == before
+
+    rows, active = st.leaves()
+    assert list(np.flatnonzero(active)) == [0, per]  # the two roots
+    select_again()
+    if K:
+        return
+    prior = np.zeros((2, 225), np.float64)
+    value = np.zeros(2, np.float32)
+    for g in range(2):
+        prior[g], value[g] = evals[g](_cells_of(rows)[g], None)
+    st.backup(prior, value)
+    st.select()
+    assert st.leaves()[1].all() and [t["n_nodes"] for t in st.trees()] == [2, 2]
+    select_again()  # the new leaves wait
+
+
 # ---------------------------------------------------------------- 2. K = 1 leaves today's path alone
 def _five_states():
     tcells, tplayer, tmoves = R.tactical_position()

@@ -1,4 +1,4 @@
-"""Slot compaction of a PUCT engine on the GPU (csrc/gz_puct.hip: gz_selfplay_puct_compact,
+"""Slot compaction of a PUCT engine on the GPU (csrc/gz_puct_compact.hip: gz_selfplay_puct_compact,
 gz_selfplay_puct_run_active, gz_selfplay_puct_rounds_active): the games do not depend on
 it, the move itself against the numpy restatement in tests/puct_compact_ref.py, its
 edges, a workspace carved for its capacity and run for fewer slots, and the training

@@ -1,4 +1,4 @@
-"""The PUCT arena on the GPU (csrc/gz_puct.hip: gz_puct_match_run, gz_puct_match_results;
+"""The PUCT arena on the GPU (csrc/gz_puct_match.hip: gz_puct_match_run, gz_puct_match_results;
 gzero/arena.py) against the self-play engine where both sides are one network, and against
 the plain-Python driver of tests/puct_match_ref.py where they are two.  Every comparison
 is ==."""
