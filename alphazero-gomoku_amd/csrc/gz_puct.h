@@ -4,8 +4,8 @@
 // few host steps of the search that the match borrows.  Only those units include it.
 //
 // Workspace (gz_puct_workspace_bytes(n, S), M = S+1 nodes per game):
-//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S, flags, alpha, eps, F, p), written
-//                       by gz_puct_begin
+//   [0, 256)            PuctCfg (c_puct, seed, temp_plies, S, flags, alpha, eps, F, p, forced_k), written
+//                       by gz_puct_begin (forced_k only with forced playouts, and only then read)
 //   n x game_stride     per game, game_stride = al256(128 + 2334 M):
 //        PuctHdr  128 B   root position, game id, node count, pending node, ...
 //        W        f64 [M]
@@ -49,6 +49,7 @@
 
 #include <string>
 
+#include "gz_forced.h"
 #include "gz_internal.h"
 #include "gz_search.h"
 
@@ -70,6 +71,7 @@ struct PuctCfg {
     int32_t fast;      // F of GZ_PUCT_PLAYOUT_CAP
     int32_t pad;
     double full_prob;  // p
+    double forced_k;   // k > 0 of GZ_PUCT_FORCED_PLAYOUTS: written and read by the forced kernels only
 };
 static_assert(sizeof(PuctCfg) <= 256, "the configuration block");
 
@@ -335,6 +337,20 @@ inline int read_noise(const char* who, const gz_puct_params* p, PuctNoise& nz) {
     nz.alpha = q->noise_alpha;
     nz.eps = q->noise_eps;
     nz.on = 1;
+    return GZ_OK;
+}
+
+// The forced playouts p asks for: k = 0 without GZ_PUCT_FORCED_PLAYOUTS (nothing past the cap
+// struct is read then), else gz_puct_forced_params.forced_k, finite and in [0, 16].  k = 0
+// with the flag forces and prunes nothing: every path treats it as the flag clear.
+inline int read_forced(const char* who, const gz_puct_params* p, double& k) {
+    k = 0.0;
+    if (!(p->flags & GZ_PUCT_FORCED_PLAYOUTS)) return GZ_OK;
+    if (p->flags & GZ_PUCT_LEAF_BATCH)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": forced playouts with leaf batching are not supported");
+    const double x = ((const gz_puct_forced_params*)p)->forced_k;
+    if (!forced_k_ok(x)) return gz_fail(GZ_ERR_ARG, std::string(who) + ": forced_k must be finite and in [0, 16]");
+    k = x > 0.0 ? x : 0.0;  // (-0.0: 0.0)
     return GZ_OK;
 }
 

@@ -55,6 +55,17 @@
 // Root noise is mixed into the rows of full roots only.  Not with leaf batching, not in
 // a match.
 //
+// Forced playouts and policy-target pruning (opt-in, GZ_PUCT_FORCED_PLAYOUTS; gz_forced.h,
+// tests/puct_forced_ref.py restates it).  At a root whose budget is S a child with n >= 1
+// visits scores +infinity while n < sqrt((k * prior[0][c]) * (visits[0] - 1))
+// (descend_once<false, true>, reached for i == 0 only), and the visit row that leaves the
+// search -- puct_finish_kernel's d_visits, the row puct_advance_kernel stashes -- gives back
+// the forced playouts a child would not hold by PUCT (prune_row, between pick_move and the
+// row stores; the move and the exported tree keep the raw counts).  The flag-clear kernels
+// are untouched: the forced paths are kernels of their own (puct_select_forced_kernel,
+// puct_round_forced_kernel, puct_finish_forced_kernel, puct_advance_forced_kernel), chosen
+// on the host from the params or, in the step API, from what gz_puct_begin noted for the
+// workspace.  k = 0 is the flag clear.  Not with leaf batching, not in a match.
 //
 // The layouts (workspace, export, self-play) are in gz_puct.h, which the PUCT units share;
 // slot compaction is gz_puct_compact.hip, the match gz_puct_match.hip.
@@ -343,9 +354,14 @@ struct Descent {
 // VL: virtual loss is in play (the header comment has both forms of the score).  vl [S+1]
 // counts the leaves of this launch that wait below a node, and a live child created in this
 // launch (index >= first) has no prior row yet: a collision.  Without VL neither is read.
-template <bool VL>
+// FORCED (GZ_PUCT_FORCED_PLAYOUTS, gz_forced.h; never with VL): at the root a visited child
+// that is short of forced_min(forced_k, prior, visits[0] - 1) visits scores +infinity; the
+// first-maximum rule picks among several.  forced_k = 0 (a fast ply's root) forces nothing.
+// Without FORCED forced_k is not read.
+template <bool VL, bool FORCED = false>
 __device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, const int16_t* vl, int first,
-                                       BB& black, BB& white, int mover, int cnt) {
+                                       BB& black, BB& white, int mover, int cnt, double forced_k = 0.0) {
+    static_assert(!(VL && FORCED), "forced playouts are not defined with virtual loss");
     const int lane = lane_id();
     PuctHdr* h = t.h;
     int i = 0;
@@ -381,7 +397,9 @@ __device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, 
                     }
                 }
                 const double u = ((c_puct * pr[c]) * sq) / (1.0 + (double)nn);
-                const double sc = q + u;
+                double sc = q + u;
+                if constexpr (FORCED)
+                    if (i == 0 && nn >= 1 && (double)nn < forced_min(forced_k, pr[c], ni - 1)) sc = __builtin_inf();
                 if (sc > bv) {
                     bv = sc;
                     bi = c;
@@ -429,7 +447,10 @@ __device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, 
 // empty row (a terminal node backed up, a game that is over, waits for a backup or
 // whose root already has its budget's B+1 visits -- with tree reuse, where a game can
 // reach its budget before the others, and on the fast plies of a playout cap).
-__device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, uint32_t* leaves, int32_t* active) {
+// FORCED: playouts are forced with forced_k at a root whose budget is the full one.
+template <bool FORCED = false>
+__device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, uint32_t* leaves, int32_t* active,
+                               double forced_k = 0.0) {
     PuctHdr* h = t.h;
     BB black, white;
     load_bb(black, h->black);
@@ -437,7 +458,8 @@ __device__ inline void descend(const PuctTree& t, double c_puct, int S, int g, u
     bool live = false;
     // (pending: the caller skipped a backup; keep the tree as it is)
     if (!(h->over || h->pending >= 0 || t.visits[0] > h->budget)) {
-        const Descent d = descend_once<false>(t, c_puct, S, nullptr, 0, black, white, h->player, h->n_moves);
+        const Descent d = descend_once<false, FORCED>(t, c_puct, S, nullptr, 0, black, white, h->player, h->n_moves,
+                                                      h->budget == S ? forced_k : 0.0);
         live = d.what == DESCENT_LEAF;
         if (live && lane_id() == 0) h->pending = d.j;
     }
@@ -449,6 +471,22 @@ __global__ __launch_bounds__(WAVE) void puct_select_kernel(char* ws, int n, int 
     if (g >= n) return;
     const PuctCfg cfg = *(const PuctCfg*)ws;
     descend(tree_of(ws, g, S), cfg.c_puct, S, g, leaves, active);
+}
+
+// gz_puct_begin with GZ_PUCT_FORCED_PLAYOUTS (k > 0): k beside the configuration the begin
+// kernel has just written (stream order), for the forced select and finish kernels -- the
+// only ones that read it
+__global__ void puct_forced_cfg_kernel(char* ws, double forced_k) {
+    ((PuctCfg*)ws)->forced_k = forced_k;
+}
+
+// puct_select_kernel of a workspace whose search forces playouts
+__global__ __launch_bounds__(WAVE) void puct_select_forced_kernel(char* ws, int n, int S, uint32_t* leaves,
+                                                                  int32_t* active) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const PuctCfg cfg = *(const PuctCfg*)ws;
+    descend<true>(tree_of(ws, g, S), cfg.c_puct, S, g, leaves, active, cfg.forced_k);
 }
 
 // ---------------------------------------------------------------- backup
@@ -654,8 +692,48 @@ __device__ inline gz_search_stats search_stats(int n_nodes, int predicts, int dr
     return st;
 }
 
-__global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int S, int32_t* moves, int32_t* visits,
-                                                           double* root_q, gz_search_stats* stats) {
+// The visit row that leaves the search (GZ_PUCT_FORCED_PLAYOUTS, gz_forced.h): out = v, and at
+// a live root with the full budget every child but the most-visited one (first maximum: c*)
+// gives back the forced playouts it would not hold by PUCT against c*'s score.  cfg: c_puct,
+// forced_k, S.  The move choice and the tree keep the raw counts.  Every lane of the wave calls.
+__device__ inline void prune_row(const PuctTree& t, const PuctHdr* h, const PuctCfg& cfg, const int v[4], int out[4]) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[k] = v[k];
+    if (!(cfg.forced_k > 0.0) || h->budget != cfg.S) return;
+    // (only an empty cell has a child, and only a child has visits)
+    int bv = 0, bi = INT_MAX;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (v[k] > bv) {
+            bv = v[k];
+            bi = lane + WAVE * k;
+        }
+    wave_argmax_int(bv, bi);
+    if (bv <= 0 || bi >= GZ_CELLS) return;
+    const int N = t.visits[0];
+    const double sq = __builtin_sqrt((double)N);
+    double best = 0.0;
+    if ((bi & (WAVE - 1)) == lane) best = forced_score(cfg.c_puct, t.prior[bi], sq, t.W[t.child[bi]] / (double)bv, bv);
+    best = __shfl(best, bi & (WAVE - 1));
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {  // (one copy of the loop; the result goes to out[k] by select)
+        const int c = lane + WAVE * k;
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) n = j == k ? v[j] : n;
+        int kept = n;
+        if (c < GZ_CELLS && c != bi && n >= 1)
+            kept = forced_kept(n, forced_prune_count(cfg.c_puct, cfg.forced_k, t.prior[c], sq, N - 1, t.W[t.child[c]], n, best));
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[j] = j == k ? kept : out[j];
+    }
+}
+
+// FORCED: the row stored is the pruned one
+template <bool FORCED>
+__device__ inline void finish_game(char* ws, int n, int S, int32_t* moves, int32_t* visits, double* root_q,
+                                   gz_search_stats* stats) {
     const int g = blockIdx.x;
     if (g >= n) return;
     const int lane = lane_id();
@@ -670,9 +748,17 @@ __global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int 
     int v[4];
     const long long total = root_visits(t, over, v);
     if (visits) {
+        if constexpr (FORCED) {
+            int out[4];
+            prune_row(t, h, cfg, v, out);  // (a root that is over: v is 0 everywhere and stays)
 #pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (lane + WAVE * k < GZ_CELLS) visits[(size_t)g * GZ_CELLS + lane + WAVE * k] = v[k];
+            for (int k = 0; k < 4; k++)
+                if (lane + WAVE * k < GZ_CELLS) visits[(size_t)g * GZ_CELLS + lane + WAVE * k] = out[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (lane + WAVE * k < GZ_CELLS) visits[(size_t)g * GZ_CELLS + lane + WAVE * k] = v[k];
+        }
     }
     int mv = -1, draws = 0;
     if (!over) mv = pick_move(h, cfg, E, v, total, draws);
@@ -684,6 +770,18 @@ __global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int 
         h->main_draws = draws;
         if (stats) stats[g] = search_stats(over ? 0 : h->n_nodes, h->n_evals, draws, 0);
     }
+}
+
+__global__ __launch_bounds__(WAVE) void puct_finish_kernel(char* ws, int n, int S, int32_t* moves, int32_t* visits,
+                                                           double* root_q, gz_search_stats* stats) {
+    finish_game<false>(ws, n, S, moves, visits, root_q, stats);
+}
+
+// puct_finish_kernel of a workspace whose search forces playouts
+__global__ __launch_bounds__(WAVE) void puct_finish_forced_kernel(char* ws, int n, int S, int32_t* moves,
+                                                                  int32_t* visits, double* root_q,
+                                                                  gz_search_stats* stats) {
+    finish_game<true>(ws, n, S, moves, visits, root_q, stats);
 }
 
 // ---------------------------------------------------------------- tree reuse
@@ -870,9 +968,10 @@ __global__ __launch_bounds__(RR_THREADS) void puct_reroot_kernel(char* ws, int n
 // (move -1 leaves the slot alone); then the workgroup re-roots the tree under the move,
 // unless the move ends the game -- the tree of a move that ends it no longer matches
 // its slot after the commit, and puct_round_kernel begins a fresh one.
-__global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* slots, int n, gz_puct_params p,
-                                                                  PuctNoise nz, PuctCap cap, char* ws, int32_t* moves,
-                                                                  gz_search_stats* stats, uint16_t* pend) {
+// FORCED: the row stashed is the pruned one (prune_row with forced_k).
+template <bool FORCED>
+__device__ inline void advance_slot(const char* slots, int n, gz_puct_params p, PuctNoise nz, PuctCap cap, char* ws,
+                                    int32_t* moves, gz_search_stats* stats, uint16_t* pend, double forced_k) {
     extern __shared__ __attribute__((aligned(16))) int16_t remap[];
     __shared__ int next_root;
     const int s = blockIdx.x;
@@ -899,9 +998,18 @@ __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* sl
             const long long total = root_visits(t, false, v);
             mv = pick_move(h, cfg, empties(black, white), v, total, draws);
             uint16_t* row = pend + ((size_t)s * GZ_MAX_GAME_PLIES + h->n_moves) * GZ_CELLS;
+            if constexpr (FORCED) {
+                cfg.forced_k = forced_k;
+                int out[4];
+                prune_row(t, h, cfg, v, out);
 #pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (lane + WAVE * k < GZ_CELLS) row[lane + WAVE * k] = (uint16_t)v[k];
+                for (int k = 0; k < 4; k++)
+                    if (lane + WAVE * k < GZ_CELLS) row[lane + WAVE * k] = (uint16_t)out[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (lane + WAVE * k < GZ_CELLS) row[lane + WAVE * k] = (uint16_t)v[k];
+            }
             if (mv >= 0 && mv < GZ_CELLS) {
                 c = t.child[mv];
                 if (c <= 0 || c >= h->n_nodes || c > S || t.term[c]) c = -1;
@@ -932,9 +1040,24 @@ __global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* sl
     }
 }
 
+__global__ __launch_bounds__(RR_THREADS) void puct_advance_kernel(const char* slots, int n, gz_puct_params p,
+                                                                  PuctNoise nz, PuctCap cap, char* ws, int32_t* moves,
+                                                                  gz_search_stats* stats, uint16_t* pend) {
+    advance_slot<false>(slots, n, p, nz, cap, ws, moves, stats, pend, 0.0);
+}
+
+// puct_advance_kernel of a run that forces playouts
+__global__ __launch_bounds__(RR_THREADS) void puct_advance_forced_kernel(const char* slots, int n, gz_puct_params p,
+                                                                         PuctNoise nz, PuctCap cap, char* ws,
+                                                                         int32_t* moves, gz_search_stats* stats,
+                                                                         uint16_t* pend, double forced_k) {
+    advance_slot<true>(slots, n, p, nz, cap, ws, moves, stats, pend, forced_k);
+}
+
 // Round step 3: a tree that is not the slot's (a new game, a reset, a move that ended
 // the game) gives way to a fresh root, whose board is its leaf of this round; every
-// other slot descends once.
+// other slot descends once.  (puct_round_forced_kernel below is this kernel with
+// descend<true>: a change here belongs there too.)
 __global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int n, gz_puct_params p, PuctCap cap,
                                                           char* ws, uint32_t* leaves, int32_t* active) {
     const int s = blockIdx.x;
@@ -953,6 +1076,37 @@ __global__ __launch_bounds__(WAVE) void puct_round_kernel(const char* slots, int
     const int rounds = h->reuse == REUSE_MAGIC ? h->rounds : 0;
     if (tree_matches(h, sh)) {
         descend(t, p.c_puct, S, s, leaves, active);
+    } else {
+        const bool full = root_is_full(cap, p.seed, sh->game_id, sh->n_moves);
+        begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC,
+                   budget_of(cap, full, S), full);
+        write_leaf(leaves, active, s, black, white, true);
+    }
+    if (lane_id() == 0) h->rounds = rounds + 1;
+}
+
+// puct_round_kernel of a run that forces playouts: the same step with descend<true>.  (A
+// kernel of its own text, not a shared body: routed through a common inline function the
+// flag-clear kernel above allocates its registers differently.)
+__global__ __launch_bounds__(WAVE) void puct_round_forced_kernel(const char* slots, int n, gz_puct_params p,
+                                                                 PuctCap cap, char* ws, uint32_t* leaves,
+                                                                 int32_t* active, double forced_k) {
+    const int s = blockIdx.x;
+    if (s >= n) return;
+    const int S = p.num_simulations;
+    const SlotHeader* sh = slot_of(slots, s);
+    PuctTree t = tree_of(ws, s, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, sh->black);
+    load_bb(white, sh->white);
+    if (sh->game_id >= sh->game_id_end) {
+        write_leaf(leaves, active, s, black, white, false);
+        return;
+    }
+    const int rounds = h->reuse == REUSE_MAGIC ? h->rounds : 0;
+    if (tree_matches(h, sh)) {
+        descend<true>(t, p.c_puct, S, s, leaves, active, forced_k);
     } else {
         const bool full = root_is_full(cap, p.seed, sh->game_id, sh->n_moves);
         begin_root(t, black, white, sh->game_id, sh->n_moves, sh->player, false, REUSE_MAGIC,
@@ -1075,26 +1229,32 @@ int check_rows(const char* who, int32_t n, int32_t K) {
     return GZ_OK;
 }
 
-// Which workspaces hold a batched search.  gz_puct_select, gz_puct_backup and
-// gz_puct_reroot take no params, and the kernel to launch (and its grid of rows) cannot
-// be chosen from the PuctCfg in device memory without reading it back, which would
-// synchronise the unbatched step API too.  So gz_puct_begin notes K on the host as well,
-// by workspace address; a later unbatched begin on the same address removes the note.
-std::mutex g_batch_mutex;
-std::unordered_map<const void*, int> g_batch_leaves;
+// Which workspaces hold a batched search, and which a search that forces playouts.
+// gz_puct_select, gz_puct_backup, gz_puct_finish and gz_puct_reroot take no params, and the
+// kernel to launch (and its grid of rows) cannot be chosen from the PuctCfg in device memory
+// without reading it back, which would synchronise the plain step API too.  So gz_puct_begin
+// notes K and the forcing on the host as well, by workspace address; a later plain begin on
+// the same address removes the note.
+constexpr int NOTE_FORCED = 1 << 16;  // (K <= GZ_PUCT_MAX_LEAVES lies below)
+std::mutex g_note_mutex;
+std::unordered_map<const void*, int> g_notes;
 
-void note_leaves(const void* ws, int K) {
-    std::lock_guard<std::mutex> lock(g_batch_mutex);
-    if (K > 0) g_batch_leaves[ws] = K;
-    else if (!g_batch_leaves.empty()) g_batch_leaves.erase(ws);
+void note_search(const void* ws, int K, bool forced) {
+    std::lock_guard<std::mutex> lock(g_note_mutex);
+    if (K > 0 || forced) g_notes[ws] = K | (forced ? NOTE_FORCED : 0);
+    else if (!g_notes.empty()) g_notes.erase(ws);
 }
 
-int leaves_of(const void* ws) {
-    std::lock_guard<std::mutex> lock(g_batch_mutex);
-    if (g_batch_leaves.empty()) return 0;
-    const auto it = g_batch_leaves.find(ws);
-    return it == g_batch_leaves.end() ? 0 : it->second;
+int note_of(const void* ws) {
+    std::lock_guard<std::mutex> lock(g_note_mutex);
+    if (g_notes.empty()) return 0;
+    const auto it = g_notes.find(ws);
+    return it == g_notes.end() ? 0 : it->second;
 }
+
+int leaves_of(const void* ws) { return note_of(ws) & (NOTE_FORCED - 1); }
+
+bool forced_of(const void* ws) { return (note_of(ws) & NOTE_FORCED) != 0; }
 
 }  // namespace
 
@@ -1109,6 +1269,11 @@ int gz_internal_puct_backup(void* ws, int32_t n, int32_t S, const double* d_prio
 
 int gz_internal_puct_finish(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
                             gz_search_stats* d_stats, void* stream) {
+    if (forced_of(ws)) {
+        puct_finish_forced_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q,
+                                                                     d_stats);
+        return gz_check_launch("puct_finish_forced_kernel");
+    }
     puct_finish_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q, d_stats);
     return gz_check_launch("puct_finish_kernel");
 }
@@ -1130,14 +1295,20 @@ int gz_internal_puct_begin(const gz_board_state* d_boards, const int64_t* d_game
     PuctCap cap;
     rc = read_cap("gz_puct_begin", p, cap);
     if (rc) return rc;
+    double forced_k;
+    rc = read_forced("gz_puct_begin", p, forced_k);
+    if (rc) return rc;
     if (n > 0 && (!d_boards || !d_game_ids || !d_workspace || !d_leaves || !d_active))
         return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
     if (n == 0) return GZ_OK;
-    note_leaves(d_workspace, K);
+    note_search(d_workspace, K, forced_k > 0.0);
     int16_t* pend = K > 0 ? (int16_t*)((char*)d_workspace + rounds_offset(n_cap, p->num_simulations)) : nullptr;
     puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, cap, K, pend,
                                                          (char*)d_workspace, d_leaves, d_active);
-    return gz_check_launch("puct_begin_kernel");
+    rc = gz_check_launch("puct_begin_kernel");
+    if (rc || !(forced_k > 0.0)) return rc;
+    puct_forced_cfg_kernel<<<1, 1, 0, as_stream(stream)>>>((char*)d_workspace, forced_k);
+    return gz_check_launch("puct_forced_cfg_kernel");
 }
 
 int gz_internal_puct_stash_commit(void* d_slots, int32_t n, const SelfplayWs& w, gz_record* d_records,
@@ -1298,6 +1469,9 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     PuctCap cap;
     rc = read_cap(who, p, cap);
     if (rc) return rc;
+    double forced_k;
+    rc = read_forced(who, p, forced_k);
+    if (rc) return rc;
     return check_rows(who, n, K);
 }
 
@@ -1352,16 +1526,28 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
     PuctCap cap;
     rc = read_cap(who, p, cap);
     if (rc) return rc;
+    double forced_k;
+    rc = read_forced(who, p, forced_k);
+    if (rc) return rc;
+    const bool forced = forced_k > 0.0;
     for (int it = 0; it < n_rounds; it++) {
-        puct_advance_kernel<<<n, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n, *p, nz, cap,
-                                                                   (char*)w.puct, w.moves, w.stats, w.pend);
-        rc = gz_check_launch("puct_advance_kernel");
+        if (forced)
+            puct_advance_forced_kernel<<<n, RR_THREADS, remap_bytes(S), st>>>(
+                (const char*)d_slots, n, *p, nz, cap, (char*)w.puct, w.moves, w.stats, w.pend, forced_k);
+        else
+            puct_advance_kernel<<<n, RR_THREADS, remap_bytes(S), st>>>((const char*)d_slots, n, *p, nz, cap,
+                                                                       (char*)w.puct, w.moves, w.stats, w.pend);
+        rc = gz_check_launch(forced ? "puct_advance_forced_kernel" : "puct_advance_kernel");
         if (rc) return rc;
         rc = gz_internal_selfplay_commit(d_slots, n, w.moves, w.stats, d_records, record_cap, d_counters, w.pend,
                                          d_visits, stream);
         if (rc) return rc;
-        puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, cap, (char*)w.puct, r.leaves, r.active);
-        rc = gz_check_launch("puct_round_kernel");
+        if (forced)
+            puct_round_forced_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, cap, (char*)w.puct, r.leaves,
+                                                         r.active, forced_k);
+        else
+            puct_round_kernel<<<n, WAVE, 0, st>>>((const char*)d_slots, n, *p, cap, (char*)w.puct, r.leaves, r.active);
+        rc = gz_check_launch(forced ? "puct_round_forced_kernel" : "puct_round_kernel");
         if (rc) return rc;
         rc = eval_rows(ls, d_pv_weights, r, n, p->precision, stream);
         if (rc) return rc;
@@ -1395,6 +1581,10 @@ int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, 
     if (n == 0) return GZ_OK;
     const int K = leaves_of(d_workspace);
     if (K > 0) return select_batch_impl(d_workspace, n, n, S, K, d_leaves, d_active, stream);
+    if (forced_of(d_workspace)) {
+        puct_select_forced_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
+        return gz_check_launch("puct_select_forced_kernel");
+    }
     puct_select_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
     return gz_check_launch("puct_select_kernel");
 }
@@ -1560,6 +1750,17 @@ int gz_puct_cap_full(const gz_record* d_records, int32_t n, uint64_t seed, doubl
 
 int gz_puct_cap_full_host(uint64_t seed, int64_t game_id, int32_t ply, double full_prob) {
     return cap_is_full(seed, game_id, ply, full_prob) ? 1 : 0;
+}
+
+int gz_puct_forced_prune_host(double c_puct, double forced_k, int32_t root_visits, const double prior[225],
+                              const double W[225], const int32_t visits[225], int32_t out[225]) {
+    if (!forced_k_ok(forced_k)) return gz_fail(GZ_ERR_ARG, "gz_puct_forced_prune_host: forced_k must be finite and in [0, 16]");
+    if (root_visits < 1 || !prior || !W || !visits || !out || out == visits)
+        return gz_fail(GZ_ERR_ARG, "gz_puct_forced_prune_host: bad arguments");
+    for (int c = 0; c < GZ_CELLS; c++)
+        if (visits[c] < 0) return gz_fail(GZ_ERR_ARG, "gz_puct_forced_prune_host: a negative visit count");
+    forced_prune_row(c_puct, forced_k, root_visits, prior, W, visits, out, GZ_CELLS);
+    return GZ_OK;
 }
 
 int gz_puct_root_noise_host(uint64_t seed, int64_t game_id, int32_t ply, const uint8_t* empty225, double alpha,

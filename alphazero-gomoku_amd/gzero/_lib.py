@@ -24,6 +24,7 @@ GZ_PUCT_ROOT_NOISE = 1  # gz_puct_params.flags: the params are a gz_puct_noise_p
 GZ_PUCT_LEAF_BATCH = 2  # gz_puct_params.flags: the params are a gz_puct_batch_params
 GZ_PUCT_PLAYOUT_CAP = 4  # gz_puct_params.flags: the params are a gz_puct_cap_params
 GZ_PUCT_LEAF_SYM = 8  # gz_puct_params.flags: every leaf is evaluated under a board symmetry (no struct of its own)
+GZ_PUCT_FORCED_PLAYOUTS = 16  # gz_puct_params.flags: the params are a gz_puct_forced_params
 GZ_PUCT_MAX_LEAVES = 32
 
 
@@ -80,6 +81,10 @@ class PuctCapParams(PuctBatchParams):  # gz_puct_cap_params: the batch struct, t
     _fields_ = [("fast_simulations", ctypes.c_int32), ("cap_pad", ctypes.c_int32), ("full_prob", ctypes.c_double)]
 
 
+class PuctForcedParams(PuctCapParams):  # gz_puct_forced_params: the cap struct, then k (80 bytes)
+    _fields_ = [("forced_k", ctypes.c_double)]
+
+
 class Record(ctypes.Structure):  # gz_record, 80 bytes
     _fields_ = [("black", ctypes.c_uint32 * 8), ("white", ctypes.c_uint32 * 8),
                 ("game_id", ctypes.c_int64), ("ply", ctypes.c_int16), ("move", ctypes.c_int16),
@@ -111,6 +116,7 @@ assert ctypes.sizeof(BoardState) == 80 and ctypes.sizeof(Record) == 80
 assert ctypes.sizeof(PuctMatchParams) == 40 and ctypes.sizeof(PuctMatchTally) == 72
 assert ctypes.sizeof(PuctParams) == 32 and ctypes.sizeof(PuctNoiseParams) == 48
 assert ctypes.sizeof(PuctBatchParams) == 56 and ctypes.sizeof(PuctCapParams) == 72
+assert ctypes.sizeof(PuctForcedParams) == 80
 assert ctypes.sizeof(SearchStats) == 24 and ctypes.sizeof(SelfplayCounters) == 40
 
 class SgdNet(ctypes.Structure):  # gz_sgd_net
@@ -229,6 +235,7 @@ SIGNATURES = {
     "gz_puct_root_noise": (ctypes.c_int, [_P, _P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
     "gz_puct_cap_full": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
     "gz_puct_cap_full_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, ctypes.c_double]),
+    "gz_puct_forced_prune_host": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, _I32, _P, _P, _P, _P]),
     "gz_puct_root_noise_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, ctypes.c_double, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),

@@ -397,7 +397,8 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 
 # ---------------------------------------------------------------- PUCT search
 def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
-                noise_eps=0.25, leaves_per_round=1, fast_simulations=None, full_prob=0.25, leaf_symmetry=False):
+                noise_eps=0.25, leaves_per_round=1, fast_simulations=None, full_prob=0.25, leaf_symmetry=False,
+                forced_playouts=None):
     """gz_puct_params; precision ("fp32" / "f16x3" / "f16") is the forward gz_puct_search runs.
     dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
     noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
@@ -413,7 +414,15 @@ def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision
     leaves_per_round > 1.
     leaf_symmetry: every leaf is evaluated under one of the 8 board symmetries, picked by
     (seed, position), and its prior mapped back (GZ_PUCT_LEAF_SYM; the struct is the one
-    the other options give).  False (the default): the flag is clear."""
+    the other options give).  False (the default): the flag is clear.
+    forced_playouts k: forced playouts at full-budget roots and pruning of the visit rows
+    that leave the search (a gz_puct_forced_params with GZ_PUCT_FORCED_PLAYOUTS set;
+    include/gzero.h), k finite and in [0, 16] (KataGo: 2; 0 forces and prunes nothing).
+    None (the default): the flag is clear.  Not with leaves_per_round > 1."""
+    if forced_playouts is not None:
+        return _with_forced(puct_params(num_simulations, c_puct, temp_plies, seed, precision, dirichlet_alpha,
+                                        noise_eps, leaves_per_round, fast_simulations, full_prob, leaf_symmetry),
+                            forced_playouts)
     if leaf_symmetry:
         p = puct_params(num_simulations, c_puct, temp_plies, seed, precision, dirichlet_alpha, noise_eps,
                         leaves_per_round, fast_simulations, full_prob)
@@ -458,6 +467,39 @@ def _with_cap(params, fast_simulations, full_prob):
                               noise | sym | _lib.GZ_PUCT_PLAYOUT_CAP, alpha, eps, 1, 0, F, 0, prob)
 
 
+def _with_forced(params, forced_playouts):
+    """The gz_puct_forced_params of unbatched params; the inner fields of the options that
+    are off are zero and not read."""
+    k = float(forced_playouts)
+    if params.flags & _lib.GZ_PUCT_LEAF_BATCH:
+        raise ValueError("forced_playouts is not supported with leaves_per_round > 1")
+    if not 0.0 <= k <= 16.0:  # (a NaN fails both)
+        raise ValueError(f"forced_playouts must be in [0, 16], not {forced_playouts!r}")
+    noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
+    cap = params.flags & _lib.GZ_PUCT_PLAYOUT_CAP
+    alpha, eps = (params.noise_alpha, params.noise_eps) if noise else (0.0, 0.0)
+    F, prob = (params.fast_simulations, params.full_prob) if cap else (0, 0.0)
+    return _lib.PuctForcedParams(params.num_simulations, params.temp_plies, params.c_puct, params.seed,
+                                 params.precision, params.flags | _lib.GZ_PUCT_FORCED_PLAYOUTS, alpha, eps, 1, 0, F, 0,
+                                 prob, k)
+
+
+def forced_prune_host(c_puct, forced_k, root_visits, prior, W, visits):
+    """The pruned visit row int32 [225] of gz_puct_forced_prune_host (no GPU): prior and W
+    float64 [225], visits int32 [225] with 0 where the root has no child."""
+    lib = _lib.load()
+    pr = np.ascontiguousarray(prior, np.float64)
+    w = np.ascontiguousarray(W, np.float64)
+    v = np.ascontiguousarray(visits, np.int32)
+    if pr.shape != (225,) or w.shape != (225,) or v.shape != (225,):
+        raise ValueError("prior, W and visits must have 225 entries")
+    out = np.empty(225, np.int32)
+    _lib.check(lib.gz_puct_forced_prune_host(float(c_puct), float(forced_k), int(root_visits), pr.ctypes.data,
+                                             w.ctypes.data, v.ctypes.data, out.ctypes.data),
+               "gz_puct_forced_prune_host")
+    return out
+
+
 def cap_full(records_dev, seed, full_prob):
     """Which records are full plies of a capped run with this seed and full_prob
     (gz_puct_cap_full): records_dev a device uint8 tensor of gz_record (80 bytes each),
@@ -490,6 +532,8 @@ def with_leaves(params, leaves_per_round):
         return params
     if params.flags & _lib.GZ_PUCT_PLAYOUT_CAP:
         raise ValueError("leaves_per_round > 1 is not supported with fast_simulations (the playout cap)")
+    if params.flags & _lib.GZ_PUCT_FORCED_PLAYOUTS:
+        raise ValueError("leaves_per_round > 1 is not supported with forced_playouts")
     noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
     sym = params.flags & _lib.GZ_PUCT_LEAF_SYM
     flags = noise | sym | (_lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0)
@@ -607,6 +651,10 @@ class PuctStepper:
     With a playout cap (puct_params(fast_simulations=...)) a search has no fixed number of
     rounds either: ``remaining()`` (and ``reroot()``'s result) count against each game's own
     budget, and a game at or past it has an inactive row.
+
+    With forced playouts (puct_params(forced_playouts=k)) nothing changes for the caller:
+    ``select()`` forces at full-budget roots, ``finish()`` returns the pruned visit rows and
+    picks the moves from the raw counts, ``trees()`` shows the raw counts.
 
     With leaves_per_round K > 1 (here or in params) every buffer has n K rows, game g at
     rows g K .. g K + K - 1, and a search is no fixed number of rounds: after the root's

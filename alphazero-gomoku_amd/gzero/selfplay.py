@@ -30,7 +30,8 @@ class SelfPlayEngine:
                  game_id_stride=None, planner_steps=0, planner_difficulty="medium", gn_weights=None,
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
                  rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1,
-                 compact_slots=False, fast_simulations=None, full_prob=0.25, leaf_symmetry=False):
+                 compact_slots=False, fast_simulations=None, full_prob=0.25, leaf_symmetry=False,
+                 forced_playouts=None):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -72,6 +73,14 @@ class SelfPlayEngine:
         (GZ_PUCT_LEAF_SYM, include/gzero.h), so the network's orientation bias averages out
         over a search.  Lock-step and tree_reuse alike, with every other option; the burn-in
         of :meth:`advance` keeps it.
+        forced_playouts k (search="puct" only; default None = the flag clear): forced playouts
+        and policy-target pruning (GZ_PUCT_FORCED_PLAYOUTS, include/gzero.h; KataGo's k = 2):
+        at a full-budget root a visited child gets at least sqrt(k prior visits) playouts, so
+        a noised move is examined and not just tried once, and the visit row that becomes the
+        policy target gives back the forced playouts the move did not earn by PUCT.  The move
+        played comes from the raw counts; rows no longer sum to num_simulations.  Lock-step
+        and tree_reuse alike; fast plies of a playout cap neither force nor prune; the
+        burn-in of :meth:`advance` does not force.  Not with leaves_per_round > 1.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -110,6 +119,11 @@ class SelfPlayEngine:
         self.leaf_symmetry = bool(leaf_symmetry)
         if self.leaf_symmetry and search != "puct":
             raise ValueError("leaf_symmetry needs search='puct'")
+        if forced_playouts is not None:
+            if search != "puct":
+                raise ValueError("forced_playouts needs search='puct'")
+            if self.leaves_per_round > 1:
+                raise ValueError("forced_playouts is not supported with leaves_per_round > 1")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -162,7 +176,7 @@ class SelfPlayEngine:
         if search == "puct":
             self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision, dirichlet_alpha,
                                     noise_eps, self.leaves_per_round, fast_simulations, full_prob,
-                                    self.leaf_symmetry)
+                                    self.leaf_symmetry, forced_playouts)
             K = puct_leaves(self.puct)
             nbytes = self.lib.gz_selfplay_puct_batch_workspace_bytes(self.n_slots, S, K) if K else \
                 self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S)
@@ -318,7 +332,8 @@ class SelfPlayEngine:
             # one leaf per round, so the flags that would make the library read past the copy are
             # cleared; leaf_symmetry has no struct of its own and stays: the burn-in is a search too)
             p = _lib.PuctParams.from_buffer_copy(self.puct)
-            p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH | _lib.GZ_PUCT_PLAYOUT_CAP)
+            p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH | _lib.GZ_PUCT_PLAYOUT_CAP |
+                         _lib.GZ_PUCT_FORCED_PLAYOUTS)
             p.num_simulations = min(8, p.num_simulations)
             for _ in range(int(n_plies) if self.n_active > 0 else 0):
                 self.d_counters.zero_()

@@ -251,7 +251,7 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                          noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True,
                          pv_weights=None, fast_simulations: Optional[int] = None, full_prob: float = 0.25,
-                         leaf_symmetry: bool = False):
+                         leaf_symmetry: bool = False, forced_playouts: Optional[float] = None):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -282,6 +282,9 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     cap, all of them), the ones run_iteration trains on.
     leaf_symmetry: every leaf is evaluated under a board symmetry picked by (seed, position)
     (SelfPlayEngine(leaf_symmetry=True)); off by default.
+    forced_playouts k: forced playouts at full-budget roots, and visit rows pruned of the
+    playouts a move did not earn (SelfPlayEngine(forced_playouts=k); KataGo uses 2): the rows
+    returned are the pruned ones and sum to at most num_simulations.  None (default): off.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -294,7 +297,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          rounds_per_step=plies_per_step * (num_simulations + 1) if tree_reuse else None,
                          dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round,
                          game_id_end=game_id_base + n_games if compact else None, compact_slots=bool(compact),
-                         fast_simulations=fast_simulations, full_prob=full_prob, leaf_symmetry=leaf_symmetry)
+                         fast_simulations=fast_simulations, full_prob=full_prob, leaf_symmetry=leaf_symmetry,
+                         forced_playouts=forced_playouts)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -644,7 +648,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                   noise_eps: float = 0.25, leaves_per_round: int = 1,
                   selfplay_precision: Optional[str] = None, fast_simulations: Optional[int] = None,
-                  full_prob: float = 0.25, leaf_symmetry: bool = False) -> dict:
+                  full_prob: float = 0.25, leaf_symmetry: bool = False,
+                  forced_playouts: Optional[float] = None) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -670,7 +675,12 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     then the count kept and ``records_played`` the count of all plies.
     ``leaf_symmetry`` (search="puct"): self-play evaluates every leaf under a random board
     symmetry (selfplay_puct_device), which averages the network's orientation bias out of the
-    visit distributions it then trains on."""
+    visit distributions it then trains on.
+    ``forced_playouts`` k (search="puct"; KataGo's 2): self-play forces playouts at its
+    full-budget roots and the dataset is built from the pruned visit rows
+    (selfplay_puct_device); gz_dataset_pi normalises every row by its own sum, so the rows
+    train as they are.  With ``dirichlet_alpha`` the noise then explores without being
+    imitated."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     from gzero.weights import PRECISIONS
@@ -689,6 +699,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError("fast_simulations needs search='puct'")
     if leaf_symmetry and search != "puct":
         raise ValueError("leaf_symmetry needs search='puct'")
+    if forced_playouts is not None and search != "puct":
+        raise ValueError("forced_playouts needs search='puct'")
     if selfplay_precision is not None:
         if search != "puct":
             raise ValueError("selfplay_precision needs search='puct'")
@@ -706,7 +718,7 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                                                    leaves_per_round=leaves_per_round,
                                                    pv_weights=model.device_weights(selfplay_precision),
                                                    fast_simulations=fast_simulations, full_prob=full_prob,
-                                                   leaf_symmetry=leaf_symmetry)
+                                                   leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -793,7 +805,7 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
          temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
          leaves_per_round: int = 1, selfplay_precision: Optional[str] = None, arena_search: str = "reference",
          tree_reuse: bool = False, fast_simulations: Optional[int] = None, full_prob: float = 0.25,
-         leaf_symmetry: bool = False):
+         leaf_symmetry: bool = False, forced_playouts: Optional[float] = None):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -809,6 +821,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     with ``tree_reuse=True``, the own-clock engine, where a fast ply costs fewer rounds.
     ``leaf_symmetry=True``: self-play and the PUCT arena evaluate every leaf under a random
     board symmetry (run_iteration, evaluate_model(puct={"leaf_symmetry": True})).
+    ``forced_playouts=k``: forced playouts and pruned policy targets in self-play
+    (run_iteration); the arena does not force.
     ``arena_search="puct"``: rank 0's per-iteration arena is a device-side match of the
     network-guided search between the model and the best snapshot
     (evaluate_model(search="puct"), colours alternating), so the win rate printed depends
@@ -824,6 +838,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
         raise ValueError("tree_reuse and fast_simulations need search='puct'")
     if leaf_symmetry and search != "puct":
         raise ValueError("leaf_symmetry needs search='puct'")
+    if forced_playouts is not None and search != "puct":
+        raise ValueError("forced_playouts needs search='puct'")
     if arena_search not in ("reference", "puct"):
         raise ValueError(f"arena_search must be 'reference' or 'puct', not {arena_search!r}")
     rank, ws = gdist.init_from_env()
@@ -845,7 +861,7 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
                             temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
                             leaves_per_round=leaves_per_round, selfplay_precision=selfplay_precision,
                             tree_reuse=tree_reuse, fast_simulations=fast_simulations, full_prob=full_prob,
-                            leaf_symmetry=leaf_symmetry)
+                            leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

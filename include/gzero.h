@@ -381,7 +381,8 @@ typedef struct gz_puct_params {
     double c_puct;
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
     int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3 / GZ_PV_F16: the forward of every search and self-play entry */
-    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP | GZ_PUCT_LEAF_SYM */
+    int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP | GZ_PUCT_LEAF_SYM |
+                                GZ_PUCT_FORCED_PLAYOUTS */
 } gz_puct_params;
 /* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).
  * With GZ_PUCT_ROOT_NOISE in flags the p given to gz_puct_begin, gz_puct_search,
@@ -496,6 +497,55 @@ typedef struct gz_puct_cap_params {
 int gz_puct_cap_full(const gz_record* d_records, int32_t n, uint64_t seed, double full_prob, uint8_t* d_full,
                      void* stream);
 int gz_puct_cap_full_host(uint64_t seed, int64_t game_id, int32_t ply, double full_prob);
+/* Forced playouts and policy-target pruning (opt-in; KataGo's paper, section 3.2, the
+ * companion of root noise and the playout cap).  With GZ_PUCT_FORCED_PLAYOUTS in flags p
+ * points at a gz_puct_forced_params (its inner fields are read only with their own flags);
+ * without it nothing past the 32 / 48 / 56 / 72 bytes is read and every entry point computes
+ * what it did before.  Everything is fp64 in exactly the order written (csrc/gz_forced.h;
+ * tests/puct_forced_ref.py restates it), sqrt and / correctly rounded.
+ * Forcing, at the root only and only at a root whose budget is the full one (budget == S:
+ * every root without the playout cap, the full plies with it; fast plies neither force nor
+ * prune).  T = visits[0] - 1.  For an empty cell c whose child j has n = visits[j] >= 1:
+ *   forced(c) = sqrt((forced_k * prior[0][c]) * (double)T)
+ *   if ((double)n < forced(c))  score(c) = +infinity      (else the score as it is)
+ * prior[0] is the root's stored row (the noised one with GZ_PUCT_ROOT_NOISE); several
+ * infinite scores resolve by the first-maximum rule (lowest cell); a terminal child is forced
+ * like any other.  Nodes below the root, the backup, the move choice and the budget are
+ * unchanged.
+ * Pruning, where a root's visit row leaves the search: gz_puct_finish's d_visits (so the row
+ * of a lock-step self-play ply) and the row an own-clock ply stashes.  The move is picked
+ * from the raw counts and gz_puct_trees exports the raw visits.  With N = visits[0],
+ * sq = sqrt((double)N) and the raw counts v[c] of a full-budget root:
+ *   c* = the empty cell with the most visits, first maximum; n* = v[c*]  (n* == 0: row unchanged)
+ *   best = W[child c*] / n* + ((c_puct * prior[0][c*]) * sq) / (1.0 + (double)n*)
+ *   every other cell c with n = v[c] >= 1, q = W[child c] / (double)n held fixed:
+ *     m = min(n, (int)forced(c))                   (forced(c) with T = N - 1; truncation)
+ *     r = 0;  while r < m:  s = q + ((c_puct * prior[0][c]) * sq) / (1.0 + (double)(n - (r + 1)));
+ *                           if s >= best: break;  r += 1
+ *     out[c] = n - r;  if r > 0 and out[c] == 1: out[c] = 0
+ *   out[c*] = n*
+ * A pruned row sums to at most the raw sum and never to 0 while n* > 0 (gz_dataset_pi
+ * normalises a row by its own sum).  forced_k = 0 forces nothing and prunes nothing: the flag
+ * with k = 0 gives the flag-clear bytes.  A root that is over gives the zero row as before.
+ * Accepted by gz_puct_begin (which keeps forced_k with the workspace for gz_puct_select and
+ * gz_puct_finish), gz_puct_search, gz_selfplay_puct_run(_active) and
+ * gz_selfplay_puct_rounds(_active).  gz_puct_reroot takes no params and reads nothing of
+ * this: the workspace stays what gz_puct_begin made it, so the searches after a re-root force
+ * and prune as the one before.  Combines with GZ_PUCT_ROOT_NOISE, GZ_PUCT_PLAYOUT_CAP and
+ * GZ_PUCT_LEAF_SYM.  GZ_ERR_ARG before any launch: forced_k not finite or outside [0, 16],
+ * the flag together with GZ_PUCT_LEAF_BATCH (virtual loss and forcing are not defined
+ * together), the flag in gz_puct_match_run's search params (an arena plays, it collects no
+ * targets).  Workspace sizes, the tree stride, the record format and the pend / d_visits
+ * layouts are unchanged. */
+#define GZ_PUCT_FORCED_PLAYOUTS 16
+typedef struct gz_puct_forced_params {
+    gz_puct_cap_params cap;  /* base; its fields are read only with their own flags */
+    double forced_k;         /* KataGo's k (2), finite, in [0, 16] */
+} gz_puct_forced_params;     /* 80 bytes */
+/* The pruning of one row by the same code on the host, no GPU: visits[c] == 0 means no child
+ * at c (W[c] and prior[c] are then not read), root_visits = N >= 1, out != visits. */
+int gz_puct_forced_prune_host(double c_puct, double forced_k, int32_t root_visits, const double prior[225],
+                              const double W[225], const int32_t visits[225], int32_t out[225]);
 /* Leaf symmetry (opt-in; AlphaGo Zero's random board symmetry per leaf evaluation): with
  * GZ_PUCT_LEAF_SYM in flags every leaf x is evaluated as
  *   t = gz_pv_sym(seed, x);  (prior_y, value) = gz_pv_forward(T_t(x));  prior[c] mapped back

@@ -41,6 +41,20 @@ noise on and off.
     python tools/puct_bench.py --noise 0.3,0.25 --reuse --precisions f16x3 --steps 5 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/noise_bench.json
 
+--forced K measures forced playouts and policy-target pruning
+(SelfPlayEngine(forced_playouts=K)) the way --noise measures the noise, with the root noise
+of --forced-noise on in all three engines: the parent build (--lockstep-library), this build
+with the flag clear and with it set take turns as child processes, lock-step and (--reuse)
+own-clock.  Then what the feature does, from gz_puct_search on --forced-positions mid-game
+positions with that noise, flag clear and set under the same seed: the share of a full
+search's visits the forcing threshold covers and the share it displaced, the share pruned
+from the rows, and the target mass on the cells whose noised prior exceeds twice the clean
+one -- at the init weights and with the policy FC scaled by --policy-scale (synthetic nets with
+a favourite move).
+
+    python tools/puct_bench.py --forced 2 --reuse --precisions f16x3 --steps 5 \\
+        --lockstep-library parent/libgzero.so --out profiles/puct/forced_bench.json
+
 --sym measures the leaf symmetry (SelfPlayEngine(leaf_symmetry=True)) the way --noise
 measures the noise: three child processes -- the parent build, this build with the flag
 clear, this build with the flag set -- take turns at one timed step each, lock-step and
@@ -124,7 +138,7 @@ ap.add_argument("--forward-only", action="store_true", help="(child) time gz_pv_
 ap.add_argument("--note", default=None, help="free text stored in the result's config (e.g. which build --forward-library is)")
 ap.add_argument("--reuse", action="store_true", help="measure tree reuse between plies (see above)")
 ap.add_argument("--policy-scale", default="32,128",
-                help="--reuse: the policy FC's weight and bias times this in the synthetic runs (comma-separated)")
+                help="--reuse, --cap, --forced: the policy FC's weight and bias times this in the synthetic runs (comma-separated)")
 ap.add_argument("--lockstep-library", default=None, help="--reuse: libgzero.so the lock-step child loads")
 ap.add_argument("--lockstep-child", type=float, default=None, metavar="SCALE",
                 help="(child) time lock-step steps on request, policy FC scaled by SCALE")
@@ -136,6 +150,11 @@ ap.add_argument("--sym", action="store_true", help="measure the leaf symmetry (s
 ap.add_argument("--sym-child", default=None, metavar="MODE:on|off",
                 help="(child) one engine of --sym: lockstep or reuse, with or without leaf_symmetry")
 ap.add_argument("--sym-positions", type=int, default=64, help="--sym: positions of the orientation measurement")
+ap.add_argument("--forced", type=float, default=None, metavar="K", help="measure forced playouts (see above)")
+ap.add_argument("--forced-noise", default="0.3,0.25", metavar="ALPHA,EPS", help="--forced: the root noise of every engine")
+ap.add_argument("--forced-positions", type=int, default=512, help="--forced: positions of the share measurement")
+ap.add_argument("--forced-child", default=None, metavar="MODE:off|K",
+                help="(child) one engine of --forced: lockstep or reuse, the flag clear or forced_playouts=K")
 ap.add_argument("--leaves", default=None, metavar="K,K,...",
                 help="measure leaf batching (SelfPlayEngine(leaves_per_round=K)) over --sweep-slots (see above)")
 ap.add_argument("--sweep-slots", default="1,8,64,256", help="--leaves: the slot counts (comma-separated)")
@@ -435,6 +454,14 @@ def sym_child():
     step_child(mode, {"leaf_symmetry": True} if spec == "on" else {})
 
 
+def forced_child():
+    mode, spec = a.forced_child.split(":")
+    kw = noise_args(a.forced_noise)
+    if spec != "off":
+        kw["forced_playouts"] = float(spec)
+    step_child(mode, kw)
+
+
 def step_child(mode, engine_kw):
     """Per line on stdin: one lock-step step (or one window of 2 x (S+1) rounds of a
     tree-reuse engine) timed with device events; its ms and moves on stdout."""
@@ -473,7 +500,78 @@ def sym_mode_run(prec, mode):
     return three_way_run(prec, mode, "--sym-child", kinds, "sym")
 
 
-def three_way_run(prec, mode, child_flag, kinds, what):
+def forced_mode_run(prec, mode):
+    kinds = [("parent", "off", a.lockstep_library), ("forced_off", "off", None), ("forced_on", repr(a.forced), None)]
+    return three_way_run(prec, mode, "--forced-child", kinds, "forcing", ("--forced-noise", a.forced_noise))
+
+
+def forced_shares(prec, scale):
+    """What forcing and pruning do to a full search's visit row: --forced-positions mid-game
+    positions (one per slot of a lock-step engine after --burn plies), each searched by
+    gz_puct_search with the root noise, once with the flag clear and once set (same seed, so
+    the same noise).  Raw counts come from the exported trees, the rows handed out from
+    d_visits, the clean prior from a forward of the root boards.  scale: the policy FC's weight
+    and bias times this (1.0: the init weights, whose prior is nearly flat; more: a synthetic
+    net with a favourite move, as --reuse and --cap use)."""
+    import math
+    import numpy as np
+    from gzero import device
+    from gzero.selfplay import SelfPlayEngine
+    n, S, k = a.forced_positions, a.sims, a.forced
+    alpha, eps = (float(x) for x in a.forced_noise.split(","))
+    w = bench_weights(prec, scale)
+    eng = SelfPlayEngine(n_slots=n, num_simulations=S, seed=1, pv_weights=w, search="puct", temp_plies=a.temp_plies)
+    eng.advance(a.burn)
+    st, _ = eng.boards()
+    del eng
+    gids = list(range(n))
+    live = np.flatnonzero(st["over"] == 0)
+    got = {}
+    for name, kk in (("flag_clear", None), ("flag_set", k)):
+        p = device.puct_params(S, 1.6, 0, 1, prec, dirichlet_alpha=alpha, noise_eps=eps, forced_playouts=kk)
+        _, rows, _, trees = device.puct_search(st, gids, p, w, want_trees=True)
+        raw = np.zeros((n, 225), np.int64)
+        noised = np.zeros((n, 225))
+        for g in live:
+            t = trees[g]
+            kids = np.flatnonzero(np.asarray(t["parent"]) == 0)
+            raw[g, np.asarray(t["move_of"])[kids]] = np.asarray(t["visits"])[kids]
+            noised[g] = t["prior"][0]
+        got[name] = (rows.astype(np.int64), raw, noised)
+    _, _, _, clean = device.pv_forward(w, np.stack([trees[g]["board"][0] for g in range(n)]), want_prior=True)
+    rows0, raw0, noised = got["flag_clear"]
+    rows1, raw1, noised1 = got["flag_set"]
+    assert np.array_equal(rows0, raw0) and np.array_equal(noised[live], noised1[live])
+    boosted = (noised > 2.0 * clean) & (clean > 0)
+    owed = np.zeros(n)
+    for g in live:
+        T = int(raw1[g].sum())
+        for c in np.flatnonzero(raw1[g]):
+            owed[g] += min(int(raw1[g, c]), math.ceil(math.sqrt((k * noised[g, c]) * T)))
+
+    def mass(rows):
+        tot = rows.sum(axis=1)
+        return float(((rows * boosted).sum(axis=1)[live] / tot[live]).mean())
+
+    out = {"positions": int(len(live)), "simulations": S, "forced_k": k, "noise": {"alpha": alpha, "eps": eps},
+           "what": "shares of the S visits of a full search, means over the positions: owed = sum over root "
+                   "children of min(n, ceil(forced(c))), the visits the forcing threshold covers (an upper bound "
+                   "of the forced selections); displaced = sum of max(0, raw visits with the flag - raw visits "
+                   "without) / S; pruned = 1 - sum(row handed out) / S; noise mass = the normalised row's mass "
+                   "on cells whose noised prior exceeds twice the clean prior",
+           "owed_share": float((owed[live] / S).mean()),
+           "displaced_share": float((np.maximum(raw1 - raw0, 0).sum(axis=1)[live] / S).mean()),
+           "pruned_share": float((1.0 - rows1.sum(axis=1)[live] / S).mean()),
+           "boosted_cells_mean": float(boosted.sum(axis=1)[live].mean()),
+           "noise_mass_flag_clear": mass(rows0), "noise_mass_flag_set_raw": mass(raw1),
+           "noise_mass_flag_set": mass(rows1)}
+    print(f"{prec} policy x{scale:g}: of {S} visits owed {out['owed_share']:.4f}, displaced {out['displaced_share']:.4f}, pruned "
+          f"{out['pruned_share']:.4f}; mass on noised cells {out['noise_mass_flag_clear']:.4f} flag clear, "
+          f"{out['noise_mass_flag_set_raw']:.4f} set (raw), {out['noise_mass_flag_set']:.4f} set (pruned)")
+    return out
+
+
+def three_way_run(prec, mode, child_flag, kinds, what, extra=()):
     """The three engines of one mode, taking turns: {name: per-step ms, moves, medians}."""
     S = a.sims
     rounds = 2 * (S + 1) if mode == "reuse" else S + 1
@@ -486,7 +584,7 @@ def three_way_run(prec, mode, child_flag, kinds, what):
                 env["GZ_LIBRARY"] = os.path.abspath(library)
             kids[name] = subprocess.Popen(
                 [sys.executable, os.path.abspath(__file__), child_flag, f"{mode}:{spec}", "--slots", str(a.slots),
-                 "--sims", str(S), "--burn", str(a.burn), "--precisions", prec, "--temp-plies", str(a.temp_plies)],
+                 "--sims", str(S), "--burn", str(a.burn), "--precisions", prec, "--temp-plies", str(a.temp_plies), *extra],
                 env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
         for name, kid in kids.items():
             if kid.stdout.readline().strip() != "READY":
@@ -876,6 +974,37 @@ if a.noise_child is not None:
     sys.exit(0)
 if a.sym_child is not None:
     sym_child()
+    sys.exit(0)
+if a.forced_child is not None:
+    forced_child()
+    sys.exit(0)
+if a.forced is not None:
+    prec = precisions[0]
+    res = {"config": {"slots": a.slots, "simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies,
+                      "precision": prec, "forced_k": a.forced, "noise": noise_args(a.forced_noise), "steps": a.steps,
+                      "timing": "device events around one lock-step step (S+1 rounds) or one window of 2 x (S+1) "
+                                "rounds with tree reuse; three child processes (parent build, this build with the "
+                                "flag clear and with forced_playouts), all with the root noise, take turns",
+                      "parent_library": "another build (--lockstep-library)" if a.lockstep_library else "this build",
+                      "claims": "cost per round and what the rows show; nothing about playing strength or learning"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    for mode in ("lockstep", "reuse") if a.reuse else ("lockstep",):
+        res["results"][mode] = forced_mode_run(prec, mode)
+    res["results"]["shares"] = None
+    if a.forced_positions > 0:
+        res["results"]["shares"] = {"init_weights": forced_shares(prec, 1.0)}
+        for scale in (float(x) for x in a.policy_scale.split(",") if x):
+            res["results"]["shares"][f"policy_fc_x{scale:g}_synthetic"] = forced_shares(prec, scale)
+    import torch
+    res["device"] = torch.cuda.get_device_name(0)
+    print("PUCT_FORCED_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.sym:
     prec = precisions[0]
