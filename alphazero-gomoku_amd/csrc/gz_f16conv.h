@@ -290,7 +290,8 @@ __device__ __forceinline__ float dot_col(const float* __restrict__ wp, int strid
 // B operand is one 16-byte load from the packed weights
 //   Wp[kb][n-tile][lane 64][t 4] = W^T[16kb + 4(lane/16) + t][16 n-tile + lane%16]
 // (zero past K and N; gzero/weights.py pack_mfma_b).  n-tiles nt[0..ntn) of the wave.
-// Used by the batched FC heads of the PV and planner nets.
+// Used by the batched FC heads of the planner nets (gz_gnet.hip); the PV heads cut their
+// fp16 fragments from the same packed layout (pv_heads_pack_kernel, gz_pvnet.hip).
 __device__ __forceinline__ void heads_gemm_block(const float* __restrict__ Wp, int ntiles, int kb, int lane,
                                                  const int (&nt)[4], int ntn, f32x4 (&acc)[4][4],
                                                  const float* __restrict__ arow[4]) {

@@ -24,6 +24,12 @@
 //    maps stored as fp16(y) in one plane, weights fp16(w), one MFMA per product,
 //    the same fp32 BN / skip / ReLU epilogues, conv0 and heads (pv_kernel_f16).
 //    Opt-in, for the PUCT search; not within 1e-4 of the fp32 forward.
+//
+// f16x3 and f16 are one piece of code: the tower helpers and the board loop
+// (pv_boards_f16) are templates on the map type, ActF16x3 or ActF16, which differ in
+// their f16_get4 / pv_put4 overloads and in f16_conv's TERMS alone; the two __global__
+// kernels are shells that lay out LDS.  Both feed the batched FC heads (pv_heads_kernel);
+// fp32 runs its heads inside pv_kernel_f32.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -141,9 +147,17 @@ struct ActF32 {
     }
 };
 
-// ============================================================ fp16x3 policy (gz_f16conv.h)
-template <int NM>
-__device__ __forceinline__ void f16_load(const ActF16x3& act, f32x4 (&out)[2][NM], int np, int m0, int lane) {
+// ============================================================ f16x3 / f16 policy (gz_f16conv.h)
+// One tower for both: Act = ActF16x3 (hi + lo planes, 3 MFMAs per product) or ActF16
+// (GZ_PV_F16: maps stored as fp16(y) in the hi plane alone, one MFMA per product).  The
+// types differ in f16_get4, pv_put4 and f16_conv's TERMS, nowhere else.
+template <class Act>
+constexpr int F16_TERMS = 3;
+template <>
+constexpr int F16_TERMS<ActF16> = 1;
+
+template <int NM, class Act>
+__device__ __forceinline__ void f16_load(const Act& act, f32x4 (&out)[2][NM], int np, int m0, int lane) {
     asm volatile("" : "+v"(lane));  // addresses are recomputed per layer, not hoisted (and spilled)
     lane &= 63;
 #pragma unroll
@@ -187,11 +201,17 @@ __device__ __forceinline__ void pv_put4(ActF16x3& act, const f32x4& acc, const f
     if (pre) *(f32x4*)(pre + pos * CH + ch0) = z;
 }
 
+// one term: the value stored as fp16(y); no global copies (the tree forward stays f16x3)
+template <bool SKIP>
+__device__ __forceinline__ void pv_put4(ActF16& act, const f32x4& acc, const f32x4& s, const f32x4& t,
+                                        const f32x4& skip, int ch0, int pos, _Float16*, float*) {
+    f16_put4<SKIP>(act, acc, s, t, skip, ch0, pos);
+}
+
 // pre (root boards of the delta tree forward, else nullptr): the layer's pre-ReLU
 // values z = BN(acc) (+ the skip input), [pos][128] fp32
-
-template <int NM, bool SKIP>
-__device__ __forceinline__ void f16_store(ActF16x3& act, const f32x4 (&acc)[2][NM], const float* __restrict__ S,
+template <int NM, bool SKIP, class Act>
+__device__ __forceinline__ void f16_store(Act& act, const f32x4 (&acc)[2][NM], const float* __restrict__ S,
                                           const float* __restrict__ T, const f32x4 (&skip)[2][NM], int np, int m0,
                                           int lane, float* __restrict__ pre) {
     asm volatile("" : "+v"(lane));  // addresses are recomputed per layer, not hoisted (and spilled)
@@ -268,9 +288,11 @@ __device__ __forceinline__ void f16_store_heads(const f32x4 (&acc)[2][NM], const
 }
 
 // gpre: nullptr, or the root's 4 pre-ReLU maps (PV_PRE_FLOATS each); of a root's maps
-// only x0 is kept (conv0_f16): y1, x1, y2 are relu of these
-template <int NM, int m0>
-__device__ __forceinline__ void f16_tower(ActF16x3& act, const float* __restrict__ W, int wave, int lane,
+// only x0 is kept (conv0_f16): y1, x1, y2 are relu of these.  The skip input is the
+// block input as stored (ActF16: fp16); the last epilogue reads its fp32 y in both,
+// x2 is never rounded.
+template <int NM, int m0, class Act>
+__device__ __forceinline__ void f16_tower(Act& act, const float* __restrict__ W, int wave, int lane,
                                           float* __restrict__ hpart, float* __restrict__ gpre) {
     const int np = wave & 3;
     for (int blk = 0; blk < 2; blk++) {
@@ -284,7 +306,8 @@ __device__ __forceinline__ void f16_tower(ActF16x3& act, const float* __restrict
 #pragma unroll
                 for (int m = 0; m < NM; m++) acc[n][m] = zero4();
             PV_WAVE_T0();
-            f16_conv<NM, 4, 8, 9>(act, (const _Float16*)(W + F16_RES0 + layer * F16_STRIDE), np, m0, lane, acc);
+            f16_conv<NM, 4, 8, 9, F16_TERMS<Act>>(act, (const _Float16*)(W + F16_RES0 + layer * F16_STRIDE), np, m0,
+                                                  lane, acc);
             PV_STAMP(2);
             PV_WAVE_STAMP(8);
             if (half == 0) f16_load<NM>(act, skip, np, m0, lane);  // block input, for the skip connection
@@ -304,84 +327,6 @@ __device__ __forceinline__ void f16_tower(ActF16x3& act, const float* __restrict
     }
 }
 
-// ============================================================ one-term f16 policy (GZ_PV_F16)
-// The f16x3 tower with the lo terms dropped: maps stored as fp16(y) in the hi plane
-// alone, one MFMA per product (f16_conv TERMS = 1), the same fp32 epilogues.  Siblings
-// of the f16x3 helpers above, not shared with them: the f16x3 instantiations (and the
-// tree forward's, which stay f16x3) compile as they did.
-template <int NM>
-__device__ __forceinline__ void f16_load(const ActF16& act, f32x4 (&out)[2][NM], int np, int m0, int lane) {
-    asm volatile("" : "+v"(lane));  // addresses are recomputed per layer, not hoisted (and spilled)
-    lane &= 63;
-#pragma unroll
-    for (int n = 0; n < 2; n++) {
-        const int ch0 = (2 * np + n) * 16 + 4 * (lane >> 4);
-#pragma unroll
-        for (int m = 0; m < NM; m++) {
-            const int pos = (m0 + m) * 16 + (lane & 15);
-            if (pos < POS) f16_get4(act, ch0, pos, out[n][m]);
-            else out[n][m] = zero4();
-        }
-    }
-}
-
-template <int NM, bool SKIP>
-__device__ __forceinline__ void f16_store(ActF16& act, const f32x4 (&acc)[2][NM], const float* __restrict__ S,
-                                          const float* __restrict__ T, const f32x4 (&skip)[2][NM], int np, int m0,
-                                          int lane) {
-    asm volatile("" : "+v"(lane));
-    lane &= 63;
-#pragma unroll
-    for (int n = 0; n < 2; n++) {
-        const int ch0 = (2 * np + n) * 16 + 4 * (lane >> 4);
-        const f32x4 s = *(const f32x4*)(S + ch0), t = *(const f32x4*)(T + ch0);
-#pragma unroll
-        for (int m = 0; m < NM; m++) {
-            const int pos = (m0 + m) * 16 + (lane & 15);
-            if (pos < POS) f16_put4<SKIP>(act, acc[n][m], s, t, skip[n][m], ch0, pos);
-        }
-    }
-}
-
-// the skip input is the block input as stored (fp16); the last epilogue is the f16x3
-// one: the 1x1 head convs read its fp32 y, x2 is never rounded
-template <int NM, int m0>
-__device__ __forceinline__ void f16_tower(ActF16& act, const float* __restrict__ W, int wave, int lane,
-                                          float* __restrict__ hpart) {
-    const int np = wave & 3;
-    for (int blk = 0; blk < 2; blk++) {
-        f32x4 skip[2][NM];
-        for (int half = 0; half < 2; half++) {
-            const int layer = 2 * blk + half;
-            const float* R = W + RES0 + layer * RES_STRIDE;
-            f32x4 acc[2][NM];
-#pragma unroll
-            for (int n = 0; n < 2; n++)
-#pragma unroll
-                for (int m = 0; m < NM; m++) acc[n][m] = zero4();
-            PV_WAVE_T0();
-            f16_conv<NM, 4, 8, 9, 1>(act, (const _Float16*)(W + F16_RES0 + layer * F16_STRIDE), np, m0, lane, acc);
-            PV_STAMP(2);
-            PV_WAVE_STAMP(8);
-            if (half == 0) f16_load<NM>(act, skip, np, m0, lane);
-            __syncthreads();
-            PV_WAVE_STAMP(16);
-            PV_STAMP(3);
-            if (half == 0)
-                f16_store<NM, false>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane);
-            else if (blk == 0)
-                f16_store<NM, true>(act, acc, R + RES_S, R + RES_T, skip, np, m0, lane);
-            else
-                f16_store_heads<NM>(acc, W, R + RES_S, R + RES_T, skip, np, m0, lane, hpart, nullptr);
-            __syncthreads();
-            PV_STAMP(4);
-        }
-    }
-}
-
-// conv0 3->128 + BN + ReLU in f16 (C^T form): the input planes are 0/1, exact in
-// fp16, so a*w = a*w_hi + a*w_lo (2 MFMAs, no a_lo term); K = 27 (k = tap*3 + cin)
-// padded to one 32-deep k-step.  Wave w: N tile w, all 15 M tiles.
 // im2col of conv0 for the board in `planes`: col[row][k] (fp16, 0/1 exactly),
 // k = tap*3 + cin (27 -> 32 zero-padded), row = position (rows >= 225 zero).
 // One thread per (row, k-half); built once per board for all 8 waves.
@@ -406,8 +351,10 @@ __device__ __forceinline__ void build_im2col(_Float16* __restrict__ col, const f
 
 // conv0 3->128 + BN + ReLU in f16 (C^T form): the input planes are 0/1, exact in
 // fp16, so a*w = a*w_hi + a*w_lo (2 MFMAs, no a_lo term); K = 27 (k = tap*3 + cin)
-// padded to one 32-deep k-step.  Wave w: N tile w, all 15 M tiles.
-__device__ __forceinline__ void conv0_f16(ActF16x3& act, const float* __restrict__ W, const _Float16* col, int nt,
+// padded to one 32-deep k-step.  Wave w: N tile w, all 15 M tiles.  The same two
+// MFMAs for ActF16, which stores x0 as fp16(x0).
+template <class Act>
+__device__ __forceinline__ void conv0_f16(Act& act, const float* __restrict__ W, const _Float16* col, int nt,
                                           int lane, _Float16* __restrict__ g) {
     const int li = lane & 15, q = lane >> 4;
     const _Float16* wf = (const _Float16*)(W + F16_C0) + ((size_t)nt * 64 + lane) * 8;
@@ -425,28 +372,6 @@ __device__ __forceinline__ void conv0_f16(ActF16x3& act, const float* __restrict
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, a[m], acc, 0, 0, 0);
         const int pos = m * 16 + li;
         if (pos < POS) pv_put4<false>(act, acc, s, t, none, ch0, pos, g, nullptr);
-    }
-}
-
-// GZ_PV_F16: the same two MFMAs (w_hi + w_lo on the 0/1 input), x0 stored as fp16(x0)
-__device__ __forceinline__ void conv0_f16(ActF16& act, const float* __restrict__ W, const _Float16* col, int nt,
-                                          int lane) {
-    const int li = lane & 15, q = lane >> 4;
-    const _Float16* wf = (const _Float16*)(W + F16_C0) + ((size_t)nt * 64 + lane) * 8;
-    const h8 bh = *(const h8*)wf, bl = *(const h8*)(wf + 8 * 64 * 8);
-    const int ch0 = nt * 16 + 4 * q;
-    const f32x4 s = *(const f32x4*)(W + C0_S + ch0), t = *(const f32x4*)(W + C0_T + ch0);
-    const f32x4 none = zero4();
-    h8 a[MT];
-#pragma unroll
-    for (int m = 0; m < MT; m++) a[m] = *(const h8*)(col + (m * 16 + li) * 32 + 8 * q);
-#pragma unroll
-    for (int m = 0; m < MT; m++) {
-        f32x4 acc = zero4();
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, a[m], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, a[m], acc, 0, 0, 0);
-        const int pos = m * 16 + li;
-        if (pos < POS) f16_put4<false>(act, acc, s, t, none, ch0, pos);
     }
 }
 
@@ -519,6 +444,13 @@ __device__ inline Smem smem_layout(char* lds, int act_bytes = ACT_BYTES) {
     m.vq = m.part + 512;
     m.hpart = m.vq + 192;
     return m;
+}
+
+// rows POS..ROWS-1 of the input planes are zero (conv0's off-board slot); written
+// once per workgroup, load_planes leaves them alone
+template <int NTH>
+__device__ __forceinline__ void zero_plane_pads(float* planes, int tid) {
+    for (int i = tid; i < 3 * (ROWS - POS); i += NTH) planes[(i / (ROWS - POS)) * ROWS + POS + i % (ROWS - POS)] = 0.f;
 }
 
 // input planes [black, white, empty] (gomoku_board.py:239-260, absolute colours)
@@ -675,8 +607,7 @@ __global__ __launch_bounds__(NT32, 1) void pv_kernel_f32(const float* __restrict
     const int count = board_count(n, d_count);
     float* slab = scratch + ((size_t)blockIdx.x * (NT32 / 64) + (threadIdx.x >> 6)) * SLAB_F;
     act.zero_slots(threadIdx.x, NT32);
-    for (int i = threadIdx.x; i < 3 * (ROWS - POS); i += NT32)
-        sm.planes[(i / (ROWS - POS)) * ROWS + POS + i % (ROWS - POS)] = 0.f;
+    zero_plane_pads<NT32>(sm.planes, threadIdx.x);
 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         // re-derive the lane ids per board: nothing lane-dependent is hoisted out
@@ -713,33 +644,25 @@ __global__ __launch_bounds__(NT32, 1) void pv_kernel_f32(const float* __restrict
     }
 }
 
-// ============================================================ f16x3 kernel: 8 waves (two per SIMD)
+// ============================================================ f16x3 / f16 kernels: 8 waves (two per SIMD)
 // (one wave per SIMD with 512 registers and all 15 M tiles per wave measured 37%
 // slower: the compiler serialises the A-fragment reads of a single stream)
 constexpr int NT16 = 512;
 constexpr int PV_SPLIT = 8;  // M tiles of the older wave of each SIMD pair (it wins MFMA arbitration)
 constexpr int PV_YOUNG_TILES = 15 - PV_SPLIT;
-// list (optional): the boards to run, list[0 .. *list_count); ord / maps: the
-// root ordinal of every board (-1: none) and the root map area -- a board with
+
+// The board loop of pv_kernel_f16x3<LIST, DUMP> (Act = ActF16x3) and pv_kernel_f16
+// (ActF16, no LIST / DUMP): the workgroup's boards li = blockIdx.x, + gridDim.x, ... of
+// count, each through conv0, the tower and the tower -> heads record in hbuf.
+// list (LIST): the boards to run, list[0 .. count); ord / maps (DUMP): the root
+// ordinal of every board (-1: none) and the root map area -- a board with
 // 0 <= ord < root_cap also stores its x0 map and its pre-ReLU values (gz_pvdg.hip)
-template <bool LIST, bool DUMP>
-__global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restrict__ W,
-                                                         const uint32_t* __restrict__ boards, int n,
-                                                         const int32_t* d_count, float* __restrict__ hbuf,
-                                                         const int32_t* __restrict__ list,
-                                                         const int32_t* __restrict__ list_count,
-                                                         const int32_t* __restrict__ ord,
-                                                         _Float16* __restrict__ maps, int root_cap,
-                                                         float* __restrict__ pres = nullptr) {
-    __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
-    const Smem sm = smem_layout(lds);
-    ActF16x3 act;
-    act.hi = (_Float16*)lds;
-    act.lo = act.hi + CH * ROWS16;
-    const int count = LIST ? *list_count : board_count(n, d_count);
+template <class Act, bool LIST, bool DUMP>
+__device__ __forceinline__ void pv_boards_f16(Act& act, const Smem& sm, const float* W, const uint32_t* boards,
+                                              int count, float* hbuf, const int32_t* list, const int32_t* ord,
+                                              _Float16* maps, int root_cap, float* pres) {
     act.zero_slots(threadIdx.x, NT16, CH);
-    for (int i = threadIdx.x; i < 3 * (ROWS - POS); i += NT16)
-        sm.planes[(i / (ROWS - POS)) * ROWS + POS + i % (ROWS - POS)] = 0.f;
+    zero_plane_pads<NT16>(sm.planes, threadIdx.x);
 
     PV_STAMP(30);  // start of the clock (slot 30 is not a phase)
     for (int li_ = blockIdx.x; li_ < count; li_ += gridDim.x) {
@@ -795,11 +718,26 @@ __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restri
     }
 }
 
-// ============================================================ one-term f16 kernel (GZ_PV_F16)
-// pv_kernel_f16x3 with the hi plane alone: the same 8 waves, 8/7 M-tile split and
-// n-tile pairs, a third of the MFMAs and half the LDS (no lo plane is allocated or
-// zeroed).  It writes the same tower -> heads records; no LIST / DUMP (the tree
-// forward stays f16x3).
+template <bool LIST, bool DUMP>
+__global__ __launch_bounds__(NT16, 1) void pv_kernel_f16x3(const float* __restrict__ W,
+                                                         const uint32_t* __restrict__ boards, int n,
+                                                         const int32_t* d_count, float* __restrict__ hbuf,
+                                                         const int32_t* __restrict__ list,
+                                                         const int32_t* __restrict__ list_count,
+                                                         const int32_t* __restrict__ ord,
+                                                         _Float16* __restrict__ maps, int root_cap,
+                                                         float* __restrict__ pres = nullptr) {
+    __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
+    const Smem sm = smem_layout(lds);
+    ActF16x3 act;
+    act.hi = (_Float16*)lds;
+    act.lo = act.hi + CH * ROWS16;
+    const int count = LIST ? *list_count : board_count(n, d_count);
+    pv_boards_f16<ActF16x3, LIST, DUMP>(act, sm, W, boards, count, hbuf, list, ord, maps, root_cap, pres);
+}
+
+// GZ_PV_F16: the hi plane alone -- a third of the MFMAs and half the LDS (no lo plane
+// is allocated or zeroed).  It writes the same tower -> heads records.
 constexpr int ACT_BYTES_F16H = CH * 256 * 2;  // 65536: the hi plane of 256 rows
 constexpr int LDS_BYTES_F16H = ACT_BYTES_F16H + SMALL_F * 4;
 __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16(const float* __restrict__ W,
@@ -809,74 +747,31 @@ __global__ __launch_bounds__(NT16, 1) void pv_kernel_f16(const float* __restrict
     const Smem sm = smem_layout(lds, ACT_BYTES_F16H);
     ActF16 act;
     act.hi = (_Float16*)lds;
-    const int count = board_count(n, d_count);
-    act.zero_slots(threadIdx.x, NT16, CH);
-    for (int i = threadIdx.x; i < 3 * (ROWS - POS); i += NT16)
-        sm.planes[(i / (ROWS - POS)) * ROWS + POS + i % (ROWS - POS)] = 0.f;
-
-    PV_STAMP(30);
-    for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        load_planes<NT16>(sm.planes, boards + (size_t)b * 16, tid);
-        __syncthreads();
-        PV_STAMP(0);
-        _Float16* col = (_Float16*)sm.hp;  // im2col in the heads' scratch area, as in pv_kernel_f16x3
-        build_im2col<NT16>(col, sm.planes, tid);
-        __syncthreads();
-        conv0_f16(act, W, col, wave, lane);
-        __syncthreads();
-        PV_STAMP(1);
-        if (wave >> 2)
-            f16_tower<PV_YOUNG_TILES, PV_SPLIT>(act, W, wave, lane, sm.hpart);
-        else
-            f16_tower<PV_SPLIT, 0>(act, W, wave, lane, sm.hpart);
-        int tid_h = threadIdx.x;
-        asm volatile("" : "+v"(tid_h));
-        // the record of pv_kernel_f16x3, same order of the sums
-        if (tid_h < POS) {
-            float p0 = W[P_B], p1 = W[P_B + 1], v = W[V_B];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                p0 += sm.hpart[(q * 3 + 0) * 256 + tid_h];
-                p1 += sm.hpart[(q * 3 + 1) * 256 + tid_h];
-                v += sm.hpart[(q * 3 + 2) * 256 + tid_h];
-            }
-            float* h = hbuf + (size_t)b * HSTRIDE;
-            h[tid_h] = p0;
-            h[POS + tid_h] = p1;
-            h[HV_OFF + tid_h] = v;
-        } else if (tid_h < POS + (HV_OFF - 2 * POS)) {
-            hbuf[(size_t)b * HSTRIDE + 2 * POS + (tid_h - POS)] = 0.f;  // hp k-padding
-        } else if (tid_h < POS + (HV_OFF - 2 * POS) + (HSTRIDE - HV_OFF - POS)) {
-            hbuf[(size_t)b * HSTRIDE + HV_OFF + POS + (tid_h - POS - (HV_OFF - 2 * POS))] = 0.f;  // hv padding
-        }
-    }
+    pv_boards_f16<ActF16, false, false>(act, sm, W, boards, board_count(n, d_count), hbuf, nullptr, nullptr, nullptr, 0,
+                                        nullptr);
 }
 
-// ============================================================ batched FC heads (f16x3 path)
-// policy_fc 450->225 and value_fc1 225->64 for HB = 64 boards per workgroup as fp32
-// MFMA GEMMs (v_mfma_f32_16x16x4_f32: exact f32 products, f32 accumulation) over
-// the 1x1-conv outputs the tower kernel left in hbuf, then value_fc2 + tanh and the
-// softmax (neural_network.py:146-159, 240-247).  K is taken in blocks of 16: in the
-// t-th k-step of block j, lane group g multiplies k = 16j + 4g + t, so a lane's A
-// operand for 4 k-steps is one 16-byte load.  Wave w: policy n-tiles {w, w+4, w+8,
-// w+12} (< 15) and value n-tile w, all 4 board tiles.
+// ============================================================ batched FC heads (f16x3 / f16 paths)
+// policy_fc 450->225 and value_fc1 225->64 for HB = 64 boards per workgroup as GEMMs
+// over the 1x1-conv outputs the tower kernel left in hbuf, then value_fc2 + tanh and
+// the softmax (neural_network.py:146-159, 240-247).  Wave w: policy n-tiles {w, w+4,
+// w+8, w+12} (< 15) and value n-tile w, all 4 board tiles.  (GZ_PV_FP32 runs its heads
+// inside pv_kernel_f32.)
 constexpr int HB = 64;
 constexpr int NTH_H = 256;
 constexpr int LG_STRIDE = 228;
-static_assert(HP_K == 16 * PF_KB && HV_K == 16 * V1_KB && HP_K % 16 == 0 && HV_K % 16 == 0 && HV_OFF % 4 == 0 && HSTRIDE % 4 == 0, "16-B A loads");
+// a thread's 8 k of a k-block are two 16-byte loads inside the record's padded row
+static_assert(HP_K % 8 == 0 && HV_K % 8 == 0 && HV_OFF % 4 == 0 && HSTRIDE % 4 == 0, "16-B A loads");
 
-// The f16x3 tower's heads run the same two GEMMs on v_mfma_f32_16x16x32_f16 with the
-// 3-product split (a_hi w_hi + a_hi w_lo + a_lo w_hi): 32-deep k-blocks, lane group g
-// multiplying k = 32 kb + 8 g + j (j < 8) of its board row (A) and its output column (B).
+// The GEMMs run on v_mfma_f32_16x16x32_f16 with the 3-product split (a_hi w_hi +
+// a_hi w_lo + a_lo w_hi): 32-deep k-blocks, lane group g multiplying k = 32 kb + 8 g + j
+// (j < 8) of its board row (A) and its output column (B).
 // The B fragments -- policy_fc / value_fc1 x 2^8 (exact; it keeps the small weights' lo
-// halves out of fp16's subnormals), split into fp16 hi / lo -- are cut from the fp32
-// fragments once per forward (pv_heads_pack_kernel) into the workspace: [kb][n-tile][lane]
-// [8] hi plane, then the lo plane.  The exact-fp32 path keeps the fp32-MFMA heads.
+// halves out of fp16's subnormals), split into fp16 hi / lo -- are cut from the blob's
+// fp32 fragments (PF_P / V1_P) once per forward (pv_heads_pack_kernel) into the
+// workspace: [kb][n-tile][lane][8] hi plane, then the lo plane.
 constexpr float HF_SCALE = 256.f, HF_UNSCALE = 1.f / 256.f;
-static_assert(HF_PKB * 32 >= HP_K - 8 && HF_VKB * 32 >= HV_K, "k-blocks");
+static_assert(HF_PKB * 32 >= HP_K && HF_VKB * 32 >= HV_K, "k-blocks");
 
 __global__ __launch_bounds__(256) void pv_heads_pack_kernel(const float* __restrict__ W, _Float16* __restrict__ hf) {
     constexpr int NPF = HF_PKB * PF_NT * 64, NV = HF_VKB * V1_NT * 64;
@@ -962,7 +857,7 @@ __device__ __forceinline__ void heads_gemm_f16x3(const _Float16* __restrict__ hf
             if (q < ntn) acc[m][q] = acc[m][q] * HF_UNSCALE;
 }
 
-// hf == nullptr: the fp32-MFMA GEMMs (exact f32 products); else the f16x3 ones
+// hf: the heads' fp16 fragments (pv_heads_pack_kernel)
 __global__ __launch_bounds__(NTH_H, 2) void pv_heads_kernel(const float* __restrict__ W, const float* __restrict__ hbuf,
                                                            int n, const int32_t* d_count, float* __restrict__ logits,
                                                            float* __restrict__ value, float* __restrict__ probs,
@@ -975,14 +870,10 @@ __global__ __launch_bounds__(NTH_H, 2) void pv_heads_kernel(const float* __restr
     if (b0 >= count) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
-    // board rows of the lane (row li of each of the 4 board tiles); rows past count
-    // re-read the last board and their outputs are dropped
-    const float* arow[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const int b = b0 + 16 * m + li;
-        arow[m] = hbuf + (size_t)(b < count ? b : count - 1) * HSTRIDE;
-    }
+    // the board row this thread splits (board tid / 4 of the workgroup's 64); rows past
+    // count re-read the last board and their outputs are dropped
+    const int sb = b0 + (tid >> 2);
+    const float* srow = hbuf + (size_t)(sb < count ? sb : count - 1) * HSTRIDE;
     {  // policy_fc
         int nt[4];
         int ntn = 0;
@@ -996,13 +887,7 @@ __global__ __launch_bounds__(NTH_H, 2) void pv_heads_kernel(const float* __restr
         for (int m = 0; m < 4; m++)
 #pragma unroll
             for (int q = 0; q < 4; q++) acc[m][q] = zero4();
-        if (hf) {
-            const int sb = b0 + (tid >> 2);
-            heads_gemm_f16x3<HF_PKB>(hf, PF_NT, HP_K, hbuf + (size_t)(sb < count ? sb : count - 1) * HSTRIDE,
-                                     (h8*)lg, tid, lane, nt, ntn, acc);
-        } else
-            for (int kb = 0; kb < HP_K / 16; kb++)
-                heads_gemm_block(W + PF_P, PF_NT, kb, lane, nt, ntn, acc, arow);
+        heads_gemm_f16x3<HF_PKB>(hf, PF_NT, HP_K, srow, (h8*)lg, tid, lane, nt, ntn, acc);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             if (q >= ntn) continue;
@@ -1016,21 +901,11 @@ __global__ __launch_bounds__(NTH_H, 2) void pv_heads_kernel(const float* __restr
         }
     }
     {  // value_fc1 (+ bias, ReLU)
-        const float* arv[4];
-#pragma unroll
-        for (int m = 0; m < 4; m++) arv[m] = arow[m] + HV_OFF;
         int nt[4] = {wave, 0, 0, 0};
         f32x4 acc[4][4];
 #pragma unroll
         for (int m = 0; m < 4; m++) acc[m][0] = zero4();
-        if (hf) {
-            const int sb = b0 + (tid >> 2);
-            heads_gemm_f16x3<HF_VKB>(hf + HF_VAL, V1_NT, HV_K,
-                                     hbuf + (size_t)(sb < count ? sb : count - 1) * HSTRIDE + HV_OFF, (h8*)h1, tid,
-                                     lane, nt, 1, acc);
-        } else
-            for (int kb = 0; kb < HV_K / 16; kb++)
-                heads_gemm_block(W + V1_P, V1_NT, kb, lane, nt, 1, acc, arv);
+        heads_gemm_f16x3<HF_VKB>(hf + HF_VAL, V1_NT, HV_K, srow + HV_OFF, (h8*)h1, tid, lane, nt, 1, acc);
         const int j = 16 * wave + li;
         const float bias = W[V1_B + j];
 #pragma unroll
@@ -1204,10 +1079,8 @@ extern "C" size_t gz_pv_workspace_bytes(int32_t n) {
 
 static void pv_heads_launch(const float* d_weights, const float* hbuf, int32_t n, const int32_t* d_count,
                             float* d_logits, float* d_value, float* d_probs, _Float16* hf, hipStream_t s) {
-    if (hf) {
-        constexpr int NF = HF_PKB * PF_NT * 64 + HF_VKB * V1_NT * 64;
-        pv_heads_pack_kernel<<<(NF + 255) / 256, 256, 0, s>>>(d_weights, hf);
-    }
+    constexpr int NF = HF_PKB * PF_NT * 64 + HF_VKB * V1_NT * 64;
+    pv_heads_pack_kernel<<<(NF + 255) / 256, 256, 0, s>>>(d_weights, hf);
     pv_heads_kernel<<<(n + HB - 1) / HB, NTH_H, 0, s>>>(d_weights, hbuf, n, d_count, d_logits, d_value, d_probs, hf);
 }
 

@@ -10,8 +10,8 @@ parent's recomputed squares: the same network in the same f16x3 arithmetic, the
 additions in another order, so they are compared within the tolerance stated here:
 logits and value within DELTA_TOL = 2e-5 of the full forward (measured ~2e-7),
 softmax and the fp64 masked prior within 1e-6.  Covered: grandchildren on every
-cell around parents at corners, edges and the centre, both capacity fallbacks and
-wrong tags; children on every cell, real searches and the reference fixtures are in
+cell around parents at corners, edges and the centre, both capacity fallbacks, more
+roots than the root kernel has workgroups and wrong tags; children on every cell, real searches and the reference fixtures are in
 tests/test_gpu_pvdelta.py.  DELTA_TOL guards the geometry; the precision claim (16 T of the
 float64 specification) is held in tests/test_gpu_pv_f16x3.py.
 """
@@ -169,6 +169,27 @@ def test_tree_root_capacity_fallback(pvw):
     assert st[0] == 3 and st[1] == 1 and st[2] > 0 and st[3] > 0, st
     _close(full, tree, len(cells))
     assert _bitwise_rows(full, tree, len(cells)) >= st[1] + st[3]
+
+
+def test_tree_more_roots_than_workgroups(pvw):
+    """More roots than the root kernel has workgroups (one per CU), so some workgroups
+    run a second root and store its x0 and pre-ReLU maps too: every root bitwise the
+    full forward, and one child per root -- computed from its root's stored maps, so a
+    map in the wrong slot or left from the workgroup's first board shows -- within
+    DELTA_TOL."""
+    from gzero import device
+    rng = np.random.default_rng(SEED + 5)
+    n_roots = torch.cuda.get_device_properties(0).multi_processor_count + 44
+    cells, meta = [], []
+    for i in range(n_roots):
+        root, kids = _root_family(rng, 8 + i % 50)
+        meta += [-1, len(cells)]
+        cells += [root, kids[(7 * i) % len(kids)]]
+    rows = _rows(cells)
+    full = device.pv_forward(pvw, rows, want_prior=True)
+    tree = device.pv_forward_tree(pvw, rows, meta)
+    assert tree[4][:5] == [n_roots, n_roots, n_roots, 0, 0], tree[4]
+    _close(full, tree, len(cells), range(0, len(cells), 2))
 
 
 def test_tree_wrong_tags_take_the_full_forward(pvw):
