@@ -41,6 +41,11 @@
 // launches n_active workgroups, forwards n_active (K) rows and leaves the rest alone --
 // the per-slot indexing (tree_of, pend + s 200 225, leaf row s) is the same either way.
 //
+// Gumbel root (GZ_PUCT_GUMBEL, gz_gumbel.h): behind the flag-clear size (and behind the leaf
+// symmetry's bytes, rounded up to 256, when that flag is set too), gz_puct_gumbel_bytes(n, S,
+// max_considered): gs f64 [n][225], every part al256, then the tables seq(m', S), m' = 1 ..
+// max_considered, int16 [max_considered][S], written by gz_puct_begin.
+//
 // Match workspace (gz_puct_match_workspace_bytes(n, S)): the self-play workspace of n slots,
 // then side i32 [n], row_of i32 [n], the counts (256 bytes) and per side the round buffers of
 // n rows (leaves, an unused active column, logits, probs, value, prior, the forward's scratch).
@@ -50,6 +55,7 @@
 #include <string>
 
 #include "gz_forced.h"
+#include "gz_gumbel.h"
 #include "gz_internal.h"
 #include "gz_search.h"
 
@@ -352,6 +358,53 @@ inline int read_forced(const char* who, const gz_puct_params* p, double& k) {
     if (!forced_k_ok(x)) return gz_fail(GZ_ERR_ARG, std::string(who) + ": forced_k must be finite and in [0, 16]");
     k = x > 0.0 ? x : 0.0;  // (-0.0: 0.0)
     return GZ_OK;
+}
+
+// The Gumbel root of a search, by value (on: 0 none).  gs and seq: the extra region of the
+// workspace (gumbel_region).
+struct PuctGumbel {
+    double c_visit, c_scale, gumbel_scale;
+    uint64_t seed;
+    double* gs;      // [n][225]
+    int16_t* seq;    // [max_considered][S]
+    int32_t max_considered;
+    int32_t on;
+};
+
+// The Gumbel root p asks for.  Only with GZ_PUCT_GUMBEL set is p a gz_puct_gumbel_params;
+// without it nothing past the forced struct is read.  gs and seq are left null.
+inline int read_gumbel(const char* who, const gz_puct_params* p, PuctGumbel& gm) {
+    gm = PuctGumbel{};
+    gm.seed = p->seed;
+    if (!(p->flags & GZ_PUCT_GUMBEL)) return GZ_OK;
+    if (p->flags & (GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP | GZ_PUCT_FORCED_PLAYOUTS))
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the Gumbel root with root noise, leaf batching, the playout "
+                                                      "cap or forced playouts is not supported");
+    const gz_puct_gumbel_params* q = (const gz_puct_gumbel_params*)p;
+    if (!gumbel_args_ok(q->max_considered, q->c_visit, q->c_scale, q->gumbel_scale))
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the Gumbel root needs max_considered in [1, 32], c_visit in "
+                                                      "[0, 1e4], c_scale in [0, 1e3] and gumbel_scale in [0, 8]");
+    gm.c_visit = q->c_visit;
+    gm.c_scale = q->c_scale;
+    gm.gumbel_scale = q->gumbel_scale;
+    gm.max_considered = q->max_considered;
+    gm.on = 1;
+    return GZ_OK;
+}
+
+static_assert(GZ_GUMBEL_MAX_CONSIDERED == GZ_PUCT_GUMBEL_MAX_CONSIDERED && GZ_GUMBEL_ROW_SCALE == GZ_PUCT_GUMBEL_ROW_SCALE,
+              "gz_gumbel.h and gzero.h name the same limits");
+
+inline size_t gumbel_gs_bytes(int32_t n) { return al256((size_t)n * GZ_CELLS * sizeof(double)); }
+
+// gs and seq of a workspace carved for n_cap games: behind the flag-clear size, and behind the
+// leaf symmetry's bytes when p sets that flag too
+inline void gumbel_region(PuctGumbel& gm, const gz_puct_params* p, void* ws, int32_t n_cap) {
+    size_t off = gz_puct_workspace_bytes(n_cap, p->num_simulations);
+    if (p->flags & GZ_PUCT_LEAF_SYM) off += gz_puct_sym_bytes(n_cap);
+    off = al256(off);
+    gm.gs = (double*)((char*)ws + off);
+    gm.seq = (int16_t*)((char*)ws + off + gumbel_gs_bytes(n_cap));
 }
 
 inline bool known_precision(int32_t x) { return x == GZ_PV_FP32 || x == GZ_PV_F16X3 || x == GZ_PV_F16; }

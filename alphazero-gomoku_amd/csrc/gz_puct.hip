@@ -67,6 +67,20 @@
 // on the host from the params or, in the step API, from what gz_puct_begin noted for the
 // workspace.  k = 0 is the flag clear.  Not with leaf batching, not in a match.
 //
+// Gumbel root with sequential halving (opt-in, GZ_PUCT_GUMBEL; gz_gumbel.h,
+// tests/puct_gumbel_ref.py restates it).  When node 0's evaluation is stored
+// (puct_backup_gumbel_kernel) the root's considered cells are drawn without replacement by
+// the Gumbel-top-k trick -- m rounds of wave_argmax over g(c) + logit(c) -- and their scores
+// kept in gs f64 [225], -infinity elsewhere.  puct_select_gumbel_kernel picks the root's cell
+// by the halving schedule (the considered child with seq(m, S)[visits[0] - 1] visits and the
+// best gs + sigma(q)) and descends by PUCT below it (descend_once<false, false, true>);
+// puct_finish_gumbel_kernel picks the move among the most-visited considered cells and hands
+// out softmax(logits + sigma(completed q)) scaled to 32767 as the row.  A search is still S+1
+// rounds.  The flag-clear and forced kernels are untouched: the host chooses these three from
+// the params or, in the step API, from what gz_puct_begin noted for the workspace.  gs and the
+// schedule tables lie behind the flag-clear workspace.  Not with root noise, leaf batching, the
+// playout cap, forced playouts or tree reuse, not in a match.
+//
 // The layouts (workspace, export, self-play) are in gz_puct.h, which the PUCT units share;
 // slot compaction is gz_puct_compact.hip, the match gz_puct_match.hip.
 //
@@ -358,10 +372,14 @@ struct Descent {
 // that is short of forced_min(forced_k, prior, visits[0] - 1) visits scores +infinity; the
 // first-maximum rule picks among several.  forced_k = 0 (a fast ply's root) forces nothing.
 // Without FORCED forced_k is not read.
-template <bool VL, bool FORCED = false>
+// GUMBEL (GZ_PUCT_GUMBEL; never with VL or FORCED): the root's cell is root_cell, chosen by the
+// caller (gumbel_root_cell); below the root the descent is the one above.
+template <bool VL, bool FORCED = false, bool GUMBEL = false>
 __device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, const int16_t* vl, int first,
-                                       BB& black, BB& white, int mover, int cnt, double forced_k = 0.0) {
+                                       BB& black, BB& white, int mover, int cnt, double forced_k = 0.0,
+                                       int root_cell = -1) {
     static_assert(!(VL && FORCED), "forced playouts are not defined with virtual loss");
+    static_assert(!(GUMBEL && (VL || FORCED)), "the Gumbel root stands alone");
     const int lane = lane_id();
     PuctHdr* h = t.h;
     int i = 0;
@@ -379,10 +397,17 @@ __device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, 
         const int16_t* ch = t.child + (size_t)i * GZ_CELLS;
         double bv = -__builtin_inf();
         int bi = INT_MAX;
+        bool chosen = false;
+        if constexpr (GUMBEL) {
+            if (i == 0) {
+                bi = root_cell;
+                chosen = true;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int c = lane + WAVE * k;
-            if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) {
+            if (!chosen && c < GZ_CELLS && bb_test(E, cell_to_bit(c))) {
                 const int cj = ch[c];
                 int nn = 0;
                 double q = 0.0;
@@ -406,7 +431,7 @@ __device__ inline Descent descend_once(const PuctTree& t, double c_puct, int S, 
                 }
             }
         }
-        wave_argmax(bv, bi);
+        if (!chosen) wave_argmax(bv, bi);
         if (bi == INT_MAX) bi = bit_to_cell(lowest_bit(E));  // only if the evaluator gave non-finite priors
         if (bi < 0 || bi >= GZ_CELLS) return {DESCENT_NONE, -1, -1};  // (a live node always has an empty cell)
         const int bit = cell_to_bit(bi);
@@ -782,6 +807,271 @@ __global__ __launch_bounds__(WAVE) void puct_finish_forced_kernel(char* ws, int 
                                                                   int32_t* visits, double* root_q,
                                                                   gz_search_stats* stats) {
     finish_game<true>(ws, n, S, moves, visits, root_q, stats);
+}
+
+// ---------------------------------------------------------------- Gumbel root (GZ_PUCT_GUMBEL, gz_gumbel.h)
+// The ok cells of this lane (bit k: cell lane + 64 k) of a root with the empty cells E and the
+// stored row `prior`: the empty cells whose prior has a logarithm, or, when the row has none
+// (any_ok false), every empty cell.  Every lane of the wave calls.
+__device__ inline int gumbel_ok_cells(const BB& E, const double* prior, bool& any_ok) {
+    const int lane = lane_id();
+    int emp = 0, okm = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int c = lane + WAVE * k;
+        if (c < GZ_CELLS && bb_test(E, cell_to_bit(c))) {
+            emp |= 1 << k;
+            if (gumbel_prior_ok(prior[c])) okm |= 1 << k;
+        }
+    }
+    any_ok = ballot(okm != 0) != 0;
+    return any_ok ? okm : emp;
+}
+
+__device__ inline int wave_max_int(int v) {
+    int id = 0;
+    wave_argmax_int(v, id);
+    return v;
+}
+
+// sum of x over the lanes of `mask` in ascending lane order, on top of acc (one running fp64
+// sum, as the restatement's); mask is uniform
+__device__ inline double wave_running_sum(double acc, double x, uint64_t mask) {
+    while (mask) {
+        const int l = (int)__builtin_ctzll(mask);
+        mask &= mask - 1;
+        acc += __shfl(x, l);
+    }
+    return acc;
+}
+
+// Root preparation, once per root, right after node 0's row is stored (each lane reads the
+// cells it has just written): the considered cells by m rounds of wave_argmax over
+// base = g + logit, gs[c] = base at them and -infinity at every other cell.
+__device__ inline void gumbel_root(const PuctTree& t, uint64_t seed, int max_considered, double gumbel_scale,
+                                   double* gs) {
+    const PuctHdr* h = t.h;
+    const int lane = lane_id();
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    bool any_ok;
+    const int okm = gumbel_ok_cells(empties(black, white), t.prior, any_ok);
+    const uint64_t key = stream_key(seed, h->game_id, h->n_moves, GZ_GUMBEL_SIM);
+    double base[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int c = lane + WAVE * k;
+        base[k] = 0.0;
+        if ((okm >> k) & 1) base[k] = gumbel_noise(key, c, gumbel_scale) + gumbel_logit(t.prior[c], any_ok);
+        if (c < GZ_CELLS) gs[c] = -__builtin_inf();
+    }
+    const int n_ok = (int)wave_sum_ll(__builtin_popcount(okm));
+    const int m = max_considered < n_ok ? max_considered : n_ok;
+    int left = okm;
+    for (int r = 0; r < m; r++) {
+        double bv = -__builtin_inf();
+        int bi = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (((left >> k) & 1) && base[k] > bv) {
+                bv = base[k];
+                bi = lane + WAVE * k;
+            }
+        wave_argmax(bv, bi);
+        if (bi >= GZ_CELLS) break;  // (base is finite: never)
+        if ((bi & (WAVE - 1)) == lane) {
+            left &= ~(1 << (bi / WAVE));
+            gs[bi] = bv;
+        }
+    }
+}
+
+// The root's cell of simulation t = visits[0] - 1 by the halving schedule: the considered cell
+// whose child has seq(m, S)[t] visits and the best gs + sigma(q); -1 without a candidate.
+__device__ inline int gumbel_root_cell(const PuctTree& t, const double* gs, const int16_t* seq, int max_considered,
+                                       double c_visit, double c_scale, int S) {
+    const int lane = lane_id();
+    double g[4], w[4];
+    int v[4], cons = 0, maxN = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int c = lane + WAVE * k;
+        g[k] = -__builtin_inf();
+        w[k] = 0.0;
+        v[k] = 0;
+        if (c < GZ_CELLS) {
+            g[k] = gs[c];
+            const int cj = t.child[c];
+            if (cj >= 0) {
+                v[k] = t.visits[cj];
+                w[k] = t.W[cj];
+            }
+        }
+        if (g[k] > -__builtin_inf()) cons |= 1 << k;
+        if (v[k] > maxN) maxN = v[k];
+    }
+    const int m = (int)wave_sum_ll(__builtin_popcount(cons));
+    maxN = wave_max_int(maxN);
+    const int tt = t.visits[0] - 1;
+    if (m < 1 || m > max_considered || tt < 0 || tt >= S) return -1;
+    const int want = seq[(size_t)(m - 1) * S + tt];
+    double bv = -__builtin_inf();
+    int bi = INT_MAX;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (((cons >> k) & 1) && v[k] == want) {
+            const double sc = gumbel_score(g[k], c_visit, c_scale, maxN, want, w[k], v[k]);
+            if (sc > bv) {
+                bv = sc;
+                bi = lane + WAVE * k;
+            }
+        }
+    wave_argmax(bv, bi);
+    return bi < GZ_CELLS ? bi : -1;
+}
+
+// gz_puct_begin with GZ_PUCT_GUMBEL: the tables seq(m', S), m' = 1 .. max_considered
+__global__ void puct_gumbel_tables_kernel(int16_t* seq, int max_considered, int S) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    if (m > max_considered) return;
+    gumbel_sequence(m, S, seq + (size_t)(m - 1) * S);
+}
+
+// puct_select_kernel of a workspace whose search has the Gumbel root
+__global__ __launch_bounds__(WAVE) void puct_select_gumbel_kernel(char* ws, int n, int S, uint32_t* leaves,
+                                                                  int32_t* active, PuctGumbel gm) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const double c_puct = ((const PuctCfg*)ws)->c_puct;
+    const PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    bool live = false;
+    if (!(h->over || h->pending >= 0 || t.visits[0] > h->budget)) {
+        const int cell = gumbel_root_cell(t, gm.gs + (size_t)g * GZ_CELLS, gm.seq, gm.max_considered, gm.c_visit,
+                                          gm.c_scale, S);
+        if (cell >= 0) {
+            const Descent d = descend_once<false, false, true>(t, c_puct, S, nullptr, 0, black, white, h->player,
+                                                               h->n_moves, 0.0, cell);
+            live = d.what == DESCENT_LEAF;
+            if (live && lane_id() == 0) h->pending = d.j;
+        }
+    }
+    write_leaf(leaves, active, g, black, white, live);
+}
+
+// puct_backup_kernel of such a workspace: the root preparation when node 0 is the pending one
+__global__ __launch_bounds__(WAVE) void puct_backup_gumbel_kernel(char* ws, int n, int S, const double* prior,
+                                                                  const float* value, PuctGumbel gm) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    PuctTree t = tree_of(ws, g, S);
+    const int j = t.h->pending;
+    if (j < 0) return;
+    store_eval(t, j, prior, value, g);
+    if (j == 0) gumbel_root(t, gm.seed, gm.max_considered, gm.gumbel_scale, gm.gs + (size_t)g * GZ_CELLS);
+    if (lane_id() == 0) t.h->pending = -1;
+}
+
+// puct_finish_kernel of such a workspace: the move among the most-visited considered cells by
+// gs + sigma(q), no draw; the row is the improved policy softmax(logit + sigma(completed q))
+// over the ok cells, scaled to GZ_GUMBEL_ROW_SCALE.  A root that is over: move -1, the zero row.
+__global__ __launch_bounds__(WAVE) void puct_finish_gumbel_kernel(char* ws, int n, int S, int32_t* moves,
+                                                                  int32_t* visits, double* root_q,
+                                                                  gz_search_stats* stats, PuctGumbel gm) {
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int lane = lane_id();
+    PuctTree t = tree_of(ws, g, S);
+    PuctHdr* h = t.h;
+    BB black, white;
+    load_bb(black, h->black);
+    load_bb(white, h->white);
+    const bool over = h->over != 0;
+    int v[4], out[4] = {0, 0, 0, 0};
+    const int sumN = (int)root_visits(t, over, v);
+    int mv = -1;
+    // (a live root that was never backed up has no row and no gs yet: move -1, the zero row)
+    if (!over && t.visits[0] > 0) {
+        const double* gs = gm.gs + (size_t)g * GZ_CELLS;
+        double w[4], q[4], gv[4], pr[4];
+        int maxN = 0, cmax = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = lane + WAVE * k;
+            w[k] = v[k] > 0 ? t.W[t.child[c]] : 0.0;
+            q[k] = v[k] > 0 ? w[k] / (double)v[k] : 0.0;
+            gv[k] = c < GZ_CELLS ? gs[c] : -__builtin_inf();
+            pr[k] = c < GZ_CELLS ? t.prior[c] : 0.0;
+            if (v[k] > maxN) maxN = v[k];
+            if (gv[k] > -__builtin_inf() && v[k] > cmax) cmax = v[k];
+        }
+        maxN = wave_max_int(maxN);
+        cmax = wave_max_int(cmax);
+        double bv = -__builtin_inf();
+        int bi = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (gv[k] > -__builtin_inf() && v[k] == cmax) {
+                const double sc = gumbel_score(gv[k], gm.c_visit, gm.c_scale, maxN, cmax, w[k], v[k]);
+                if (sc > bv) {
+                    bv = sc;
+                    bi = lane + WAVE * k;
+                }
+            }
+        wave_argmax(bv, bi);
+        mv = bi < GZ_CELLS ? bi : -1;
+        if (visits) {
+            bool any_ok;
+            const int okm = gumbel_ok_cells(empties(black, white), t.prior, any_ok);
+            double P = 0.0, A = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint64_t vis = ballot(v[k] > 0);
+                P = wave_running_sum(P, pr[k], vis);
+                A = wave_running_sum(A, pr[k] * q[k], vis);
+            }
+            const double v_mix = gumbel_vmix((double)t.value[0], sumN, P, A);
+            double x[4], mx = -__builtin_inf();
+            int mi = INT_MAX;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                x[k] = 0.0;
+                if ((okm >> k) & 1) {
+                    x[k] = gumbel_logit(pr[k], any_ok) + gumbel_sigma(gm.c_visit, gm.c_scale, maxN, v[k] > 0 ? q[k] : v_mix);
+                    if (x[k] > mx) {
+                        mx = x[k];
+                        mi = lane + WAVE * k;
+                    }
+                }
+            }
+            wave_argmax(mx, mi);
+            double Z = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                x[k] = ((okm >> k) & 1) ? gz_exp(x[k] - mx) : 0.0;
+                Z = wave_running_sum(Z, x[k], ballot((okm >> k) & 1));
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if ((okm >> k) & 1) out[k] = gumbel_row_entry(x[k] / Z);
+        }
+    }
+    if (visits) {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (lane + WAVE * k < GZ_CELLS) visits[(size_t)g * GZ_CELLS + lane + WAVE * k] = out[k];
+    }
+    if (lane == 0) {
+        moves[g] = mv;
+        if (root_q) root_q[g] = (over || t.visits[0] == 0) ? 0.0 : -t.W[0] / (double)t.visits[0];
+        h->move = mv;
+        h->main_draws = 0;
+        if (stats) stats[g] = search_stats(over ? 0 : h->n_nodes, h->n_evals, 0, 0);
+    }
 }
 
 // ---------------------------------------------------------------- tree reuse
@@ -1254,6 +1544,24 @@ int note_of(const void* ws) {
 
 int leaves_of(const void* ws) { return note_of(ws) & (NOTE_FORCED - 1); }
 
+// the workspaces begun with GZ_PUCT_GUMBEL, and their parameters and region (as the notes above)
+std::unordered_map<const void*, PuctGumbel> g_gumbel;
+
+void note_gumbel(const void* ws, const PuctGumbel& gm) {
+    std::lock_guard<std::mutex> lock(g_note_mutex);
+    if (gm.on) g_gumbel[ws] = gm;
+    else if (!g_gumbel.empty()) g_gumbel.erase(ws);
+}
+
+bool gumbel_of(const void* ws, PuctGumbel& gm) {
+    std::lock_guard<std::mutex> lock(g_note_mutex);
+    if (g_gumbel.empty()) return false;
+    const auto it = g_gumbel.find(ws);
+    if (it == g_gumbel.end()) return false;
+    gm = it->second;
+    return true;
+}
+
 bool forced_of(const void* ws) { return (note_of(ws) & NOTE_FORCED) != 0; }
 
 }  // namespace
@@ -1263,12 +1571,20 @@ namespace gz {
 
 int gz_internal_puct_backup(void* ws, int32_t n, int32_t S, const double* d_prior, const float* d_value,
                             const PuctNoise& nz, void* stream) {
+    // (no note is read here: the own-clock rounds and the match come this way without a
+    // gz_puct_begin of their own, and a note left by an earlier search on the address is not theirs)
     puct_backup_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_prior, d_value, nz);
     return gz_check_launch("puct_backup_kernel");
 }
 
 int gz_internal_puct_finish(void* ws, int32_t n, int32_t S, int32_t* d_moves, int32_t* d_visits, double* d_root_q,
                             gz_search_stats* d_stats, void* stream) {
+    PuctGumbel gm;
+    if (gumbel_of(ws, gm)) {
+        puct_finish_gumbel_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q,
+                                                                     d_stats, gm);
+        return gz_check_launch("puct_finish_gumbel_kernel");
+    }
     if (forced_of(ws)) {
         puct_finish_forced_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_moves, d_visits, d_root_q,
                                                                      d_stats);
@@ -1283,6 +1599,9 @@ int gz_internal_puct_begin(const gz_board_state* d_boards, const int64_t* d_game
                            void* stream) {
     if (!p) return gz_fail(GZ_ERR_ARG, "gz_puct_begin: params is NULL");
     int rc = check_S("gz_puct_begin", n, p->num_simulations);
+    if (rc) return rc;
+    PuctGumbel gm;
+    rc = read_gumbel("gz_puct_begin", p, gm);
     if (rc) return rc;
     PuctNoise nz;
     rc = read_noise("gz_puct_begin", p, nz);
@@ -1302,11 +1621,20 @@ int gz_internal_puct_begin(const gz_board_state* d_boards, const int64_t* d_game
         return gz_fail(GZ_ERR_ARG, "gz_puct_begin: bad arguments");
     if (n == 0) return GZ_OK;
     note_search(d_workspace, K, forced_k > 0.0);
+    if (gm.on) gumbel_region(gm, p, d_workspace, n_cap);
+    note_gumbel(d_workspace, gm);
     int16_t* pend = K > 0 ? (int16_t*)((char*)d_workspace + rounds_offset(n_cap, p->num_simulations)) : nullptr;
     puct_begin_kernel<<<n, WAVE, 0, as_stream(stream)>>>(d_boards, d_game_ids, n, *p, nz, cap, K, pend,
                                                          (char*)d_workspace, d_leaves, d_active);
     rc = gz_check_launch("puct_begin_kernel");
-    if (rc || !(forced_k > 0.0)) return rc;
+    if (rc) return rc;
+    if (gm.on) {
+        // (every begin, so every lock-step ply, writes the tables again: one small launch beside
+        // the S+1 forwards, and no state to keep about what a workspace already holds)
+        puct_gumbel_tables_kernel<<<1, WAVE, 0, as_stream(stream)>>>(gm.seq, gm.max_considered, p->num_simulations);
+        return gz_check_launch("puct_gumbel_tables_kernel");
+    }
+    if (!(forced_k > 0.0)) return rc;
     puct_forced_cfg_kernel<<<1, 1, 0, as_stream(stream)>>>((char*)d_workspace, forced_k);
     return gz_check_launch("puct_forced_cfg_kernel");
 }
@@ -1324,6 +1652,15 @@ int gz_internal_puct_stash_commit(void* d_slots, int32_t n, const SelfplayWs& w,
 }  // namespace gz
 
 namespace {
+
+// The backup step of a search whose Gumbel root, if any, the caller names: gm.on with gs set
+// (search_impl from its params, gz_puct_backup from the note of its gz_puct_begin).
+int backup_step(void* ws, int32_t n, int32_t S, const double* d_prior, const float* d_value, const PuctNoise& nz,
+                const PuctGumbel& gm, void* stream) {
+    if (!gm.on) return gz_internal_puct_backup(ws, n, S, d_prior, d_value, nz, stream);
+    puct_backup_gumbel_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)ws, n, S, d_prior, d_value, gm);
+    return gz_check_launch("puct_backup_gumbel_kernel");
+}
 
 // reroot()'s LDS: map and list, int16 [S+1] each
 size_t remap_bytes(int32_t S) { return (4 * ((size_t)S + 1) + 15) & ~(size_t)15; }
@@ -1440,6 +1777,10 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
     PuctNoise nz;
     int rc = read_noise("gz_puct_search", p, nz);
     if (rc) return rc;
+    PuctGumbel gm;
+    rc = read_gumbel("gz_puct_search", p, gm);
+    if (rc) return rc;
+    if (gm.on) gumbel_region(gm, p, ws, n_cap);
     rc = gz_internal_puct_begin(d_boards, d_game_ids, n_cap, n, p, ws, r.leaves, r.active, stream);
     if (rc) return rc;
     for (int round = 0; round <= S; round++) {
@@ -1449,7 +1790,7 @@ int search_impl(const gz_board_state* d_boards, const int64_t* d_game_ids, int32
         }
         rc = eval_rows(ls, d_pv_weights, r, n, p->precision, stream);
         if (rc) return rc;
-        rc = gz_internal_puct_backup(ws, n, S, r.prior, r.value, nz, stream);
+        rc = backup_step(ws, n, S, r.prior, r.value, nz, gm, stream);
         if (rc) return rc;
     }
     return gz_internal_puct_finish(ws, n, S, d_moves, d_visits, d_root_q, d_stats, stream);
@@ -1460,6 +1801,9 @@ int check_search_args(const char* who, const gz_puct_params* p, int32_t n) {
     int rc = check_S(who, n, p->num_simulations);
     if (rc) return rc;
     if (!known_precision(p->precision)) return gz_fail(GZ_ERR_ARG, std::string(who) + ": unknown precision");
+    PuctGumbel gm;
+    rc = read_gumbel(who, p, gm);
+    if (rc) return rc;
     PuctNoise nz;
     rc = read_noise(who, p, nz);
     if (rc) return rc;
@@ -1505,6 +1849,8 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
                 int32_t record_cap, uint16_t* d_visits, gz_selfplay_counters* d_counters, void* stream) {
     int rc = check_search_args(who, p, n_slots);
     if (rc) return rc;
+    if (p->flags & GZ_PUCT_GUMBEL)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the Gumbel root with tree reuse is not supported");
     rc = check_selfplay_args(who, d_slots, n_slots, n_rounds, d_counters, d_records, record_cap, d_workspace,
                              d_pv_weights != nullptr, d_visits);
     if (rc) return rc;
@@ -1517,6 +1863,9 @@ int rounds_impl(const char* who, void* d_slots, int32_t n_slots, int32_t n, cons
     if (rc) return rc;
     const int S = p->num_simulations;
     const SelfplayWs w = carve_selfplay(d_workspace, n_slots);
+    // (the trees of these rounds are begun by puct_round_kernel, not by gz_puct_begin: whatever an
+    // earlier search noted for this address is over)
+    note_gumbel(w.puct, PuctGumbel{});
     const RoundBufs r = carve_rounds(w.puct, n_slots, S);
     const LeafSym ls = leaf_sym(p, w.puct, gz_puct_workspace_bytes(n_slots, S));
     hipStream_t st = as_stream(stream);
@@ -1581,6 +1930,11 @@ int gz_puct_select(void* d_workspace, int32_t n, int32_t S, uint32_t* d_leaves, 
     if (n == 0) return GZ_OK;
     const int K = leaves_of(d_workspace);
     if (K > 0) return select_batch_impl(d_workspace, n, n, S, K, d_leaves, d_active, stream);
+    PuctGumbel gm;
+    if (gumbel_of(d_workspace, gm)) {
+        puct_select_gumbel_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active, gm);
+        return gz_check_launch("puct_select_gumbel_kernel");
+    }
     if (forced_of(d_workspace)) {
         puct_select_forced_kernel<<<n, WAVE, 0, as_stream(stream)>>>((char*)d_workspace, n, S, d_leaves, d_active);
         return gz_check_launch("puct_select_forced_kernel");
@@ -1599,7 +1953,9 @@ int gz_puct_backup(void* d_workspace, int32_t n, int32_t S, const double* d_prio
     nz.on = -1;  // as gz_puct_begin stored it in the workspace
     const int K = leaves_of(d_workspace);
     if (K > 0) return backup_batch_impl(d_workspace, n, n, S, K, d_prior, d_value, nz, stream);
-    return gz_internal_puct_backup(d_workspace, n, S, d_prior, d_value, nz, stream);
+    PuctGumbel gm;
+    if (!gumbel_of(d_workspace, gm)) gm = PuctGumbel{};
+    return backup_step(d_workspace, n, S, d_prior, d_value, nz, gm, stream);
 }
 
 int gz_puct_remaining(void* d_workspace, int32_t n, int32_t S, int32_t* d_remaining, void* stream) {
@@ -1686,6 +2042,9 @@ int gz_puct_reroot(void* d_workspace, int32_t n, int32_t S, const int32_t* d_mov
     if (n == 0) return GZ_OK;
     if (leaves_of(d_workspace) > 1)
         return gz_fail(GZ_ERR_ARG, "gz_puct_reroot: tree reuse with leaves_per_round > 1 is not supported");
+    PuctGumbel gm;
+    if (gumbel_of(d_workspace, gm))
+        return gz_fail(GZ_ERR_ARG, "gz_puct_reroot: tree reuse with the Gumbel root is not supported");
     puct_reroot_kernel<<<n, RR_THREADS, remap_bytes(S), as_stream(stream)>>>((char*)d_workspace, n, S, d_moves, d_leaves,
                                                                       d_active, d_remaining);
     return gz_check_launch("puct_reroot_kernel");
@@ -1760,6 +2119,43 @@ int gz_puct_forced_prune_host(double c_puct, double forced_k, int32_t root_visit
     for (int c = 0; c < GZ_CELLS; c++)
         if (visits[c] < 0) return gz_fail(GZ_ERR_ARG, "gz_puct_forced_prune_host: a negative visit count");
     forced_prune_row(c_puct, forced_k, root_visits, prior, W, visits, out, GZ_CELLS);
+    return GZ_OK;
+}
+
+size_t gz_puct_gumbel_bytes(int32_t n, int32_t S, int32_t max_considered) {
+    if (n < 1) n = 1;
+    if (S < 1) S = 1;
+    if (max_considered < 1) max_considered = 1;
+    if (max_considered > GZ_GUMBEL_MAX_CONSIDERED) max_considered = GZ_GUMBEL_MAX_CONSIDERED;
+    return gumbel_gs_bytes(n) + al256((size_t)max_considered * S * sizeof(int16_t));
+}
+
+int gz_puct_gumbel_sequence_host(int32_t m, int32_t S, int16_t* out) {
+    if (m < 1 || m > GZ_GUMBEL_MAX_CONSIDERED || S < 1 || S > GZ_MAX_SIMULATIONS || !out)
+        return gz_fail(GZ_ERR_ARG, "gz_puct_gumbel_sequence_host: bad arguments");
+    gumbel_sequence(m, S, out);
+    return GZ_OK;
+}
+
+int gz_puct_gumbel_root_host(uint64_t seed, int64_t game_id, int32_t ply, const double prior[225],
+                             const uint8_t* empty225, int32_t max_considered, double gumbel_scale,
+                             double gs_out[225]) {
+    if (!gumbel_args_ok(max_considered, 0.0, 0.0, gumbel_scale))
+        return gz_fail(GZ_ERR_ARG, "gz_puct_gumbel_root_host: max_considered must be in [1, 32], gumbel_scale in [0, 8]");
+    if (!prior || !empty225 || !gs_out) return gz_fail(GZ_ERR_ARG, "gz_puct_gumbel_root_host: bad arguments");
+    gumbel_root_row(stream_key(seed, game_id, ply, GZ_GUMBEL_SIM), prior, empty225, max_considered, gumbel_scale,
+                    gs_out);
+    return GZ_OK;
+}
+
+int gz_puct_gumbel_policy_host(const double prior[225], const double W[225], const int32_t visits[225], double v0,
+                               double c_visit, double c_scale, double pi_out[225], int32_t row_out[225]) {
+    if (!gumbel_args_ok(1, c_visit, c_scale, 0.0))
+        return gz_fail(GZ_ERR_ARG, "gz_puct_gumbel_policy_host: c_visit must be in [0, 1e4], c_scale in [0, 1e3]");
+    if (!prior || !W || !visits) return gz_fail(GZ_ERR_ARG, "gz_puct_gumbel_policy_host: bad arguments");
+    for (int c = 0; c < GZ_CELLS; c++)
+        if (visits[c] < 0) return gz_fail(GZ_ERR_ARG, "gz_puct_gumbel_policy_host: a negative visit count");
+    gumbel_policy_row(prior, nullptr, W, visits, v0, c_visit, c_scale, pi_out, row_out);
     return GZ_OK;
 }
 

@@ -173,6 +173,8 @@ int gz_puct_match_run(void* d_slots, int32_t n_slots, int32_t n, const gz_puct_m
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": the playout cap is not supported in a match");
     if (p->flags & GZ_PUCT_FORCED_PLAYOUTS)
         return gz_fail(GZ_ERR_ARG, std::string(who) + ": forced playouts are not supported in a match");
+    if (p->flags & GZ_PUCT_GUMBEL)
+        return gz_fail(GZ_ERR_ARG, std::string(who) + ": the Gumbel root is not supported in a match");
     PuctNoise nz;
     rc = read_noise(who, p, nz);
     if (rc) return rc;

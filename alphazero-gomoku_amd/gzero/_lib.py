@@ -25,6 +25,9 @@ GZ_PUCT_LEAF_BATCH = 2  # gz_puct_params.flags: the params are a gz_puct_batch_p
 GZ_PUCT_PLAYOUT_CAP = 4  # gz_puct_params.flags: the params are a gz_puct_cap_params
 GZ_PUCT_LEAF_SYM = 8  # gz_puct_params.flags: every leaf is evaluated under a board symmetry (no struct of its own)
 GZ_PUCT_FORCED_PLAYOUTS = 16  # gz_puct_params.flags: the params are a gz_puct_forced_params
+GZ_PUCT_GUMBEL = 32  # gz_puct_params.flags: the params are a gz_puct_gumbel_params
+GZ_PUCT_GUMBEL_MAX_CONSIDERED = 32
+GZ_PUCT_GUMBEL_ROW_SCALE = 32767
 GZ_PUCT_MAX_LEAVES = 32
 
 
@@ -85,6 +88,11 @@ class PuctForcedParams(PuctCapParams):  # gz_puct_forced_params: the cap struct,
     _fields_ = [("forced_k", ctypes.c_double)]
 
 
+class PuctGumbelParams(PuctForcedParams):  # gz_puct_gumbel_params: the forced struct, then the Gumbel root (112 bytes)
+    _fields_ = [("max_considered", ctypes.c_int32), ("gumbel_pad", ctypes.c_int32), ("c_visit", ctypes.c_double),
+                ("c_scale", ctypes.c_double), ("gumbel_scale", ctypes.c_double)]
+
+
 class Record(ctypes.Structure):  # gz_record, 80 bytes
     _fields_ = [("black", ctypes.c_uint32 * 8), ("white", ctypes.c_uint32 * 8),
                 ("game_id", ctypes.c_int64), ("ply", ctypes.c_int16), ("move", ctypes.c_int16),
@@ -117,6 +125,8 @@ assert ctypes.sizeof(PuctMatchParams) == 40 and ctypes.sizeof(PuctMatchTally) ==
 assert ctypes.sizeof(PuctParams) == 32 and ctypes.sizeof(PuctNoiseParams) == 48
 assert ctypes.sizeof(PuctBatchParams) == 56 and ctypes.sizeof(PuctCapParams) == 72
 assert ctypes.sizeof(PuctForcedParams) == 80
+assert ctypes.sizeof(PuctGumbelParams) == 112 and PuctGumbelParams.max_considered.offset == 80
+assert PuctGumbelParams.c_visit.offset == 88 and PuctGumbelParams.gumbel_scale.offset == 104
 assert ctypes.sizeof(SearchStats) == 24 and ctypes.sizeof(SelfplayCounters) == 40
 
 class SgdNet(ctypes.Structure):  # gz_sgd_net
@@ -236,6 +246,10 @@ SIGNATURES = {
     "gz_puct_cap_full": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_double, _P, _P]),
     "gz_puct_cap_full_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, ctypes.c_double]),
     "gz_puct_forced_prune_host": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, _I32, _P, _P, _P, _P]),
+    "gz_puct_gumbel_bytes": (ctypes.c_size_t, [_I32, _I32, _I32]),
+    "gz_puct_gumbel_sequence_host": (ctypes.c_int, [_I32, _I32, _P]),
+    "gz_puct_gumbel_root_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, _P, _I32, ctypes.c_double, _P]),
+    "gz_puct_gumbel_policy_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "gz_puct_root_noise_host": (ctypes.c_int, [ctypes.c_uint64, _I64, _I32, _P, ctypes.c_double, _P]),
     "gz_knowledge_scores": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
     "gz_dataset_build": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),

@@ -398,7 +398,7 @@ def plan_search(states, game_ids, params, pparams, gn_weights, want_trees=False,
 # ---------------------------------------------------------------- PUCT search
 def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision="f16x3", dirichlet_alpha=None,
                 noise_eps=0.25, leaves_per_round=1, fast_simulations=None, full_prob=0.25, leaf_symmetry=False,
-                forced_playouts=None):
+                forced_playouts=None, gumbel_considered=None, c_visit=50.0, c_scale=0.5, gumbel_scale=1.0):
     """gz_puct_params; precision ("fp32" / "f16x3" / "f16") is the forward gz_puct_search runs.
     dirichlet_alpha: Dirichlet noise at the search root, prior' = (1 - noise_eps) prior +
     noise_eps Dir(dirichlet_alpha) over the empty cells, once per root (include/gzero.h);
@@ -418,7 +418,20 @@ def puct_params(num_simulations=200, c_puct=1.6, temp_plies=0, seed=0, precision
     forced_playouts k: forced playouts at full-budget roots and pruning of the visit rows
     that leave the search (a gz_puct_forced_params with GZ_PUCT_FORCED_PLAYOUTS set;
     include/gzero.h), k finite and in [0, 16] (KataGo: 2; 0 forces and prunes nothing).
-    None (the default): the flag is clear.  Not with leaves_per_round > 1."""
+    None (the default): the flag is clear.  Not with leaves_per_round > 1.
+    gumbel_considered m: the Gumbel root with sequential halving (a gz_puct_gumbel_params with
+    GZ_PUCT_GUMBEL set; include/gzero.h): m in [1, 32] root moves sampled without replacement,
+    the budget spent by halving, the move and the policy target from logits + sigma(q) with
+    sigma(q) = (c_visit + max visits) c_scale q (q in [-1, 1]: c_scale 0.5 is the paper's 1.0),
+    gumbel_scale 0 for the deterministic variant.  None (the default): the flag is clear and
+    c_visit, c_scale, gumbel_scale are not read.  Only with leaf_symmetry among the options."""
+    if gumbel_considered is not None:
+        if dirichlet_alpha is not None or int(leaves_per_round) != 1 or fast_simulations is not None \
+                or forced_playouts is not None:
+            raise ValueError("gumbel_considered is not supported with dirichlet_alpha, leaves_per_round > 1, "
+                             "fast_simulations or forced_playouts")
+        return _with_gumbel(puct_params(num_simulations, c_puct, temp_plies, seed, precision,
+                                        leaf_symmetry=leaf_symmetry), gumbel_considered, c_visit, c_scale, gumbel_scale)
     if forced_playouts is not None:
         return _with_forced(puct_params(num_simulations, c_puct, temp_plies, seed, precision, dirichlet_alpha,
                                         noise_eps, leaves_per_round, fast_simulations, full_prob, leaf_symmetry),
@@ -484,6 +497,69 @@ def _with_forced(params, forced_playouts):
                                  prob, k)
 
 
+def _with_gumbel(params, gumbel_considered, c_visit=50.0, c_scale=0.5, gumbel_scale=1.0):
+    """The gz_puct_gumbel_params of plain params (leaf_symmetry allowed); the inner fields
+    of the other options are zero and not read."""
+    m, cv, cs, gsc = int(gumbel_considered), float(c_visit), float(c_scale), float(gumbel_scale)
+    if params.flags & ~_lib.GZ_PUCT_LEAF_SYM:
+        raise ValueError("gumbel_considered is not supported with dirichlet_alpha, leaves_per_round > 1, "
+                         "fast_simulations or forced_playouts")
+    if not 1 <= m <= _lib.GZ_PUCT_GUMBEL_MAX_CONSIDERED:
+        raise ValueError(f"gumbel_considered must be in [1, {_lib.GZ_PUCT_GUMBEL_MAX_CONSIDERED}], "
+                         f"not {gumbel_considered!r}")
+    if not 0.0 <= cv <= 1e4:  # (a NaN fails both)
+        raise ValueError(f"c_visit must be in [0, 1e4], not {c_visit!r}")
+    if not 0.0 <= cs <= 1e3:
+        raise ValueError(f"c_scale must be in [0, 1e3], not {c_scale!r}")
+    if not 0.0 <= gsc <= 8.0:
+        raise ValueError(f"gumbel_scale must be in [0, 8], not {gumbel_scale!r}")
+    return _lib.PuctGumbelParams(params.num_simulations, params.temp_plies, params.c_puct, params.seed,
+                                 params.precision, params.flags | _lib.GZ_PUCT_GUMBEL, 0.0, 0.0, 1, 0, 0, 0, 0.0, 0.0,
+                                 m, 0, cv, cs, gsc)
+
+
+def puct_gumbel_sequence_host(m, num_simulations):
+    """seq(m, S) int16 [S] of gz_puct_gumbel_sequence_host (no GPU): the visit count the
+    considered child selected at each simulation has."""
+    lib = _lib.load()
+    out = np.zeros(max(1, int(num_simulations)), np.int16)
+    _lib.check(lib.gz_puct_gumbel_sequence_host(int(m), int(num_simulations), out.ctypes.data),
+               "gz_puct_gumbel_sequence_host")
+    return out
+
+
+def puct_gumbel_root_host(seed, game_id, ply, prior, empty, max_considered, gumbel_scale=1.0):
+    """gs float64 [225] of gz_puct_gumbel_root_host (no GPU): g + logit at the considered
+    cells, -inf elsewhere; prior float64 [225], empty = 225 truth values."""
+    lib = _lib.load()
+    pr = np.ascontiguousarray(prior, np.float64)
+    e = np.ascontiguousarray(np.asarray(empty).astype(bool), np.uint8)
+    if pr.shape != (225,) or e.shape != (225,):
+        raise ValueError("prior and empty must have 225 entries")
+    out = np.zeros(225, np.float64)
+    _lib.check(lib.gz_puct_gumbel_root_host(int(seed) & ((1 << 64) - 1), int(game_id), int(ply), pr.ctypes.data,
+                                            e.ctypes.data, int(max_considered), float(gumbel_scale), out.ctypes.data),
+               "gz_puct_gumbel_root_host")
+    return out
+
+
+def puct_gumbel_policy_host(prior, W, visits, v0, c_visit=50.0, c_scale=0.5):
+    """(pi float64 [225], row int32 [225]) of gz_puct_gumbel_policy_host (no GPU): prior and
+    W float64 [225] (prior 0.0 at stones), visits int32 [225] with 0 where the root has no
+    child, v0 the root's value."""
+    lib = _lib.load()
+    pr = np.ascontiguousarray(prior, np.float64)
+    w = np.ascontiguousarray(W, np.float64)
+    v = np.ascontiguousarray(visits, np.int32)
+    if pr.shape != (225,) or w.shape != (225,) or v.shape != (225,):
+        raise ValueError("prior, W and visits must have 225 entries")
+    pi, row = np.zeros(225, np.float64), np.zeros(225, np.int32)
+    _lib.check(lib.gz_puct_gumbel_policy_host(pr.ctypes.data, w.ctypes.data, v.ctypes.data, float(v0), float(c_visit),
+                                              float(c_scale), pi.ctypes.data, row.ctypes.data),
+               "gz_puct_gumbel_policy_host")
+    return pi, row
+
+
 def forced_prune_host(c_puct, forced_k, root_visits, prior, W, visits):
     """The pruned visit row int32 [225] of gz_puct_forced_prune_host (no GPU): prior and W
     float64 [225], visits int32 [225] with 0 where the root has no child."""
@@ -534,6 +610,8 @@ def with_leaves(params, leaves_per_round):
         raise ValueError("leaves_per_round > 1 is not supported with fast_simulations (the playout cap)")
     if params.flags & _lib.GZ_PUCT_FORCED_PLAYOUTS:
         raise ValueError("leaves_per_round > 1 is not supported with forced_playouts")
+    if params.flags & _lib.GZ_PUCT_GUMBEL:
+        raise ValueError("leaves_per_round > 1 is not supported with gumbel_considered")
     noise = params.flags & _lib.GZ_PUCT_ROOT_NOISE
     sym = params.flags & _lib.GZ_PUCT_LEAF_SYM
     flags = noise | sym | (_lib.GZ_PUCT_LEAF_BATCH if K > 1 else 0)
@@ -549,7 +627,18 @@ def _puct_workspace_bytes(lib, n, params):
     S = max(0, min(params.num_simulations, _lib.GZ_MAX_SIMULATIONS))
     K = puct_leaves(params)
     size = lib.gz_puct_batch_workspace_bytes(n, S, K) if K else lib.gz_puct_workspace_bytes(n, S)
-    return size + puct_sym_bytes(lib, n * max(1, K), params)
+    return puct_extra_bytes(lib, size, n * max(1, K), n, params)
+
+
+def puct_extra_bytes(lib, size, rows, n, params):
+    """The workspace of `size` flag-clear bytes with what the params' options put behind it:
+    gz_puct_sym_bytes(rows) with GZ_PUCT_LEAF_SYM, then, rounded up to 256,
+    gz_puct_gumbel_bytes(n, S, max_considered) with GZ_PUCT_GUMBEL."""
+    size += puct_sym_bytes(lib, rows, params)
+    if params.flags & _lib.GZ_PUCT_GUMBEL:
+        S = max(1, min(params.num_simulations, _lib.GZ_MAX_SIMULATIONS))
+        size = ((size + 255) & ~255) + lib.gz_puct_gumbel_bytes(int(n), S, int(params.max_considered))
+    return size
 
 
 def puct_sym_bytes(lib, rows, params):
@@ -655,6 +744,11 @@ class PuctStepper:
     With forced playouts (puct_params(forced_playouts=k)) nothing changes for the caller:
     ``select()`` forces at full-budget roots, ``finish()`` returns the pruned visit rows and
     picks the moves from the raw counts, ``trees()`` shows the raw counts.
+
+    With the Gumbel root (puct_params(gumbel_considered=m)) the calls are the same: ``backup()``
+    of the roots prepares the considered moves, ``select()`` follows the halving schedule at the
+    root, ``finish()`` returns the improved-policy rows (scaled to 32767) and the moves;
+    ``reroot()`` is an error.
 
     With leaves_per_round K > 1 (here or in params) every buffer has n K rows, game g at
     rows g K .. g K + K - 1, and a search is no fixed number of rounds: after the root's

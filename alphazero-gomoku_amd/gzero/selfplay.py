@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .boards import RECORD_DTYPE, STATE_DTYPE, words_to_cells
-from .device import (GNWeights, PVWeights, ptr, puct_leaves, puct_params, puct_sym_bytes, require_gpu, search_params,
+from .device import (GNWeights, PVWeights, ptr, puct_extra_bytes, puct_leaves, puct_params, require_gpu, search_params,
                      stream)
 
 COUNTER_DTYPE = np.dtype([("records", "<i4"), ("leaves", "<i4"), ("records_dropped", "<i4"),
@@ -31,7 +31,7 @@ class SelfPlayEngine:
                  pv_mode="full", game_id_end=None, search="reference", temp_plies=12, tree_reuse=False,
                  rounds_per_step=None, dirichlet_alpha=None, noise_eps=0.25, leaves_per_round=1,
                  compact_slots=False, fast_simulations=None, full_prob=0.25, leaf_symmetry=False,
-                 forced_playouts=None):
+                 forced_playouts=None, gumbel_considered=None, c_visit=50.0, c_scale=0.5, gumbel_scale=1.0):
         """search: "reference" (default) = the reference's search, in which the network's
         outputs are computed and never read; "puct" = the network-guided search
         (gz_selfplay_puct_run): the priors steer selection, the value head replaces the
@@ -81,6 +81,15 @@ class SelfPlayEngine:
         played comes from the raw counts; rows no longer sum to num_simulations.  Lock-step
         and tree_reuse alike; fast plies of a playout cap neither force nor prune; the
         burn-in of :meth:`advance` does not force.  Not with leaves_per_round > 1.
+        gumbel_considered m (search="puct" only; default None = the flag clear): the Gumbel root
+        with sequential halving (GZ_PUCT_GUMBEL, include/gzero.h; Danihelka et al. 2022), the
+        search for budgets of 16..32 simulations: m root moves sampled without replacement, the
+        budget halved among them, the move from g + logit + sigma(q) and, as the policy target,
+        the improved policy softmax(logit + sigma(completed q)) as a row scaled to 32767 in
+        place of the visit counts (c_visit, c_scale, gumbel_scale: puct_params).  temp_plies is
+        not read and no main-stream draw is made.  Lock-step only (tree_reuse raises), with
+        leaf_symmetry and compact_slots; not with dirichlet_alpha, leaves_per_round > 1,
+        fast_simulations or forced_playouts; the burn-in of :meth:`advance` is plain PUCT.
         game_id_end: a slot whose next game id would be >= game_id_end goes idle
         instead of restarting (gz_selfplay_set_game_end; default: continuous refill);
         :meth:`compact` then moves the active slots to the front so that only those run.
@@ -124,6 +133,11 @@ class SelfPlayEngine:
                 raise ValueError("forced_playouts needs search='puct'")
             if self.leaves_per_round > 1:
                 raise ValueError("forced_playouts is not supported with leaves_per_round > 1")
+        if gumbel_considered is not None:
+            if search != "puct":
+                raise ValueError("gumbel_considered needs search='puct'")
+            if self.tree_reuse:
+                raise ValueError("gumbel_considered is not supported with tree_reuse")
         if search == "puct":
             if pv_weights is None:
                 raise ValueError("search='puct' needs pv_weights (the network guides the search)")
@@ -176,12 +190,14 @@ class SelfPlayEngine:
         if search == "puct":
             self.puct = puct_params(S, c_puct, temp_plies, seed, self.pv_weights.precision, dirichlet_alpha,
                                     noise_eps, self.leaves_per_round, fast_simulations, full_prob,
-                                    self.leaf_symmetry, forced_playouts)
+                                    self.leaf_symmetry, forced_playouts, gumbel_considered, c_visit, c_scale,
+                                    gumbel_scale)
             K = puct_leaves(self.puct)
             nbytes = self.lib.gz_selfplay_puct_batch_workspace_bytes(self.n_slots, S, K) if K else \
                 self.lib.gz_selfplay_puct_workspace_bytes(self.n_slots, S)
-            # (the transform of every round row, behind the flag-clear workspace)
-            nbytes += puct_sym_bytes(self.lib, self.n_slots * max(1, K), self.puct)
+            # (the transform of every round row and the Gumbel root's region, behind the flag-clear
+            # workspace)
+            nbytes = puct_extra_bytes(self.lib, nbytes, self.n_slots * max(1, K), self.n_slots, self.puct)
             self.d_puct_ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
             # uint16 [record_cap][225] visit rows, aligned with d_records (int16 storage: torch
             # has no uint16 arithmetic; a count is at most GZ_MAX_SIMULATIONS)
@@ -333,7 +349,7 @@ class SelfPlayEngine:
             # cleared; leaf_symmetry has no struct of its own and stays: the burn-in is a search too)
             p = _lib.PuctParams.from_buffer_copy(self.puct)
             p.flags &= ~(_lib.GZ_PUCT_ROOT_NOISE | _lib.GZ_PUCT_LEAF_BATCH | _lib.GZ_PUCT_PLAYOUT_CAP |
-                         _lib.GZ_PUCT_FORCED_PLAYOUTS)
+                         _lib.GZ_PUCT_FORCED_PLAYOUTS | _lib.GZ_PUCT_GUMBEL)
             p.num_simulations = min(8, p.num_simulations)
             for _ in range(int(n_plies) if self.n_active > 0 else 0):
                 self.d_counters.zero_()

@@ -251,7 +251,9 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          plies_per_step: int = 4, tree_reuse: bool = False, dirichlet_alpha: Optional[float] = None,
                          noise_eps: float = 0.25, leaves_per_round: int = 1, compact: bool = True,
                          pv_weights=None, fast_simulations: Optional[int] = None, full_prob: float = 0.25,
-                         leaf_symmetry: bool = False, forced_playouts: Optional[float] = None):
+                         leaf_symmetry: bool = False, forced_playouts: Optional[float] = None,
+                         gumbel_considered: Optional[int] = None, c_visit: float = 50.0, c_scale: float = 0.5,
+                         gumbel_scale: float = 1.0):
     """training.run_iteration's self-play with search="puct" (one rank): game ids
     [game_id_base, game_id_base + n_games) on a PUCT engine, their records and root
     visit rows collected on the device.  Every step's finished games are filtered to
@@ -285,6 +287,9 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
     forced_playouts k: forced playouts at full-budget roots, and visit rows pruned of the
     playouts a move did not earn (SelfPlayEngine(forced_playouts=k); KataGo uses 2): the rows
     returned are the pruned ones and sum to at most num_simulations.  None (default): off.
+    gumbel_considered m: the Gumbel root with sequential halving
+    (SelfPlayEngine(gumbel_considered=m), lock-step only): the rows returned are the improved
+    policy of every ply scaled to 32767, not visit counts.  None (default): off.
     Returns (device uint8 records [n, 80], device int16 visit rows [n, 225], n, stats)."""
     from gzero.selfplay import SelfPlayEngine
     _check_search("puct", model, 0)
@@ -298,7 +303,8 @@ def selfplay_puct_device(n_games: int, num_simulations: int = 200, difficulty: s
                          dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps, leaves_per_round=leaves_per_round,
                          game_id_end=game_id_base + n_games if compact else None, compact_slots=bool(compact),
                          fast_simulations=fast_simulations, full_prob=full_prob, leaf_symmetry=leaf_symmetry,
-                         forced_playouts=forced_playouts)
+                         forced_playouts=forced_playouts, gumbel_considered=gumbel_considered, c_visit=c_visit,
+                         c_scale=c_scale, gumbel_scale=gumbel_scale)
     lo, hi = int(game_id_base), int(game_id_base) + int(n_games)
     cap = n_games * _MAX_GAME_RECORDS
     # row `cap` takes the rows of games outside [lo, hi)
@@ -649,7 +655,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                   noise_eps: float = 0.25, leaves_per_round: int = 1,
                   selfplay_precision: Optional[str] = None, fast_simulations: Optional[int] = None,
                   full_prob: float = 0.25, leaf_symmetry: bool = False,
-                  forced_playouts: Optional[float] = None) -> dict:
+                  forced_playouts: Optional[float] = None, gumbel_considered: Optional[int] = None,
+                  c_visit: float = 50.0, c_scale: float = 0.5, gumbel_scale: float = 1.0) -> dict:
     """One iteration of training.main on the device (training.py:399-480):
     self-play of ``games_per_iteration`` games per rank (ids sharded by rank,
     records all-gathered so every rank holds the same replay), the dataset with
@@ -680,7 +687,11 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
     full-budget roots and the dataset is built from the pruned visit rows
     (selfplay_puct_device); gz_dataset_pi normalises every row by its own sum, so the rows
     train as they are.  With ``dirichlet_alpha`` the noise then explores without being
-    imitated."""
+    imitated.
+    ``gumbel_considered`` m (search="puct", lock-step): self-play searches with the Gumbel root
+    and sequential halving, the search for ``num_simulations`` of 16..32, and the dataset is
+    built from its improved-policy rows (selfplay_puct_device), which go through
+    DeviceDataset(records, visits=...) as visit rows do: a row is divided by its own sum."""
     from gzero import dist as gdist
     from gzero.train import DeviceDataset
     from gzero.weights import PRECISIONS
@@ -701,6 +712,8 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
         raise ValueError("leaf_symmetry needs search='puct'")
     if forced_playouts is not None and search != "puct":
         raise ValueError("forced_playouts needs search='puct'")
+    if gumbel_considered is not None and search != "puct":
+        raise ValueError("gumbel_considered needs search='puct'")
     if selfplay_precision is not None:
         if search != "puct":
             raise ValueError("selfplay_precision needs search='puct'")
@@ -718,7 +731,9 @@ def run_iteration(model, trainer, it: int, games_per_iteration: int = 10, num_si
                                                    leaves_per_round=leaves_per_round,
                                                    pv_weights=model.device_weights(selfplay_precision),
                                                    fast_simulations=fast_simulations, full_prob=full_prob,
-                                                   leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts)
+                                                   leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts,
+                                                   gumbel_considered=gumbel_considered, c_visit=c_visit,
+                                                   c_scale=c_scale, gumbel_scale=gumbel_scale)
     else:
         # every rank's records reach every rank step by step (RecordExchange), sorted by
         # game id at the end: the same replay on every rank, in the reference's game order
@@ -805,7 +820,9 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
          temp_plies: int = 8, dirichlet_alpha: Optional[float] = None, noise_eps: float = 0.25,
          leaves_per_round: int = 1, selfplay_precision: Optional[str] = None, arena_search: str = "reference",
          tree_reuse: bool = False, fast_simulations: Optional[int] = None, full_prob: float = 0.25,
-         leaf_symmetry: bool = False, forced_playouts: Optional[float] = None):
+         leaf_symmetry: bool = False, forced_playouts: Optional[float] = None,
+         gumbel_considered: Optional[int] = None, c_visit: float = 50.0, c_scale: float = 0.5,
+         gumbel_scale: float = 1.0):
     """training.main (training.py:361-537) on the MI355X engine: same loop, the
     same hyper-parameters (Adam 8e-4 / wd 1e-5, StepLR(2, 0.85), clip 0.8,
     batch 128, 2 epochs, 35 % augmentation, 90/10 split, patience 3, 6 arena
@@ -823,6 +840,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
     board symmetry (run_iteration, evaluate_model(puct={"leaf_symmetry": True})).
     ``forced_playouts=k``: forced playouts and pruned policy targets in self-play
     (run_iteration); the arena does not force.
+    ``gumbel_considered=m``: self-play with the Gumbel root and sequential halving
+    (run_iteration; lock-step, not with ``tree_reuse``); the arena stays PUCT.
     ``arena_search="puct"``: rank 0's per-iteration arena is a device-side match of the
     network-guided search between the model and the best snapshot
     (evaluate_model(search="puct"), colours alternating), so the win rate printed depends
@@ -840,6 +859,8 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
         raise ValueError("leaf_symmetry needs search='puct'")
     if forced_playouts is not None and search != "puct":
         raise ValueError("forced_playouts needs search='puct'")
+    if gumbel_considered is not None and (search != "puct" or tree_reuse):
+        raise ValueError("gumbel_considered needs search='puct' and no tree_reuse")
     if arena_search not in ("reference", "puct"):
         raise ValueError(f"arena_search must be 'reference' or 'puct', not {arena_search!r}")
     rank, ws = gdist.init_from_env()
@@ -861,7 +882,9 @@ def main(iterations: int = 6, games_per_iteration: int = 10, seed: Optional[int]
                             temp_plies=temp_plies, dirichlet_alpha=dirichlet_alpha, noise_eps=noise_eps,
                             leaves_per_round=leaves_per_round, selfplay_precision=selfplay_precision,
                             tree_reuse=tree_reuse, fast_simulations=fast_simulations, full_prob=full_prob,
-                            leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts)
+                            leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts,
+                            gumbel_considered=gumbel_considered, c_visit=c_visit, c_scale=c_scale,
+                            gumbel_scale=gumbel_scale)
         if res.get("skipped"):
             if rank == 0:
                 print("自我对弈样本过少，跳过本轮训练。")

@@ -382,7 +382,7 @@ typedef struct gz_puct_params {
     uint64_t seed;           /* RNG streams (gzero/rng.py) */
     int32_t precision;       /* GZ_PV_FP32 / GZ_PV_F16X3 / GZ_PV_F16: the forward of every search and self-play entry */
     int32_t flags;           /* 0 or GZ_PUCT_ROOT_NOISE | GZ_PUCT_LEAF_BATCH | GZ_PUCT_PLAYOUT_CAP | GZ_PUCT_LEAF_SYM |
-                                GZ_PUCT_FORCED_PLAYOUTS */
+                                GZ_PUCT_FORCED_PLAYOUTS | GZ_PUCT_GUMBEL */
 } gz_puct_params;
 /* Dirichlet noise at the search root (opt-in; AlphaZero's exploration in self-play).
  * With GZ_PUCT_ROOT_NOISE in flags the p given to gz_puct_begin, gz_puct_search,
@@ -546,6 +546,79 @@ typedef struct gz_puct_forced_params {
  * at c (W[c] and prior[c] are then not read), root_visits = N >= 1, out != visits. */
 int gz_puct_forced_prune_host(double c_puct, double forced_k, int32_t root_visits, const double prior[225],
                               const double W[225], const int32_t visits[225], int32_t out[225]);
+/* The Gumbel root with sequential halving (opt-in; "Policy improvement by planning with
+ * Gumbel", Danihelka et al., ICLR 2022): a search of S = 16..32 simulations that still
+ * improves the policy.  With GZ_PUCT_GUMBEL in flags p points at a gz_puct_gumbel_params (its
+ * inner fields are not read: the flag combines with GZ_PUCT_LEAF_SYM only); without it
+ * nothing past the bytes read before is read and every entry point computes what it did.
+ * Everything is fp64 in exactly the order written (csrc/gz_gumbel.h; tests/puct_gumbel_ref.py
+ * restates it), with gz_log / gz_exp of csrc/gz_dirichlet.h.  q lives in [-1, 1], so
+ * c_scale = 0.5 is the paper's 1.0 on values in [0, 1]; there is no min-max rescaling.
+ * Root preparation, once per root, when node 0's evaluation is stored (the backup step).
+ * E = the root's empty cells; a cell of E is ok when DBL_MIN <= prior[0][c] <= DBL_MAX; with
+ * no ok cell every cell of E is ok with logit 0.0, else logit(c) = gz_log(prior[0][c]).
+ *   u = unit_open(draw(stream_key(seed, game, ply, 0x47554D42), c));  e = -gz_log(u);
+ *   if (!(e >= DBL_MIN)) e = 0x1p-53;   g(c) = gumbel_scale * (-gz_log(e));
+ *   base(c) = g(c) + logit(c);   m = min(max_considered, ok cells)
+ *   considered: m times the first maximum of base over the ok cells not yet taken;
+ *   gs[c] = base(c) at the considered cells, -infinity elsewhere.
+ * Schedule, seq(m, S), in integers (gz_puct_gumbel_sequence_host):
+ *   m <= 1: 0, 1, .., S-1;  else L = ceil(log2 m), visits = [0]*m, k = m, and while fewer
+ *   than S entries: x = max(1, S / (L k)); x times: append visits[:k], visits[i] += 1 for
+ *   i < k; then k = max(2, k / 2).  The first S entries.
+ * Root selection at simulation t = visits[0] - 1: want = seq(m, S)[t]; among the considered
+ * cells whose child has want visits (no child: 0), with maxN the largest root-child count,
+ *   score(c) = want == 0 ? gs[c] : gs[c] + ((c_visit + (double)maxN) * c_scale) * (W[child] / (double)N)
+ * the first maximum (there always is a candidate; without one nothing descends).  Below the
+ * root the descent, the backup, the terminal rules and the budget are the search's own: a
+ * search is still S+1 rounds.
+ * The move: among the considered cells with the most visits the first maximum of
+ * gs[c] + sigma(q(c)), sigma(q) = ((c_visit + maxN) * c_scale) * q.  temp_plies is not read
+ * and main_draws is 0: the Gumbel draw already samples.  gumbel_scale = 0 is deterministic.
+ * The policy target, the row that leaves the search (gz_puct_finish's d_visits, so the row of
+ * a lock-step self-play ply): over the visited children N(c), q(c) = W / N, sumN = sum N,
+ * P and A the running sums in ascending cell order of prior[c] and prior[c] * q(c),
+ *   v0 = (double)value[0];  v_mix = (sumN > 0 && P > 0) ? (v0 + sumN * (A / P)) / (1.0 + sumN) : v0
+ *   x(c) = logit(c) + sigma(visited ? q(c) : v_mix) over all ok cells;  mx = max x
+ *   e(c) = gz_exp(x(c) - mx);  Z = the running sum in ascending cell order;  pi(c) = e(c) / Z
+ *   row[c] = (int32)(pi(c) * 32767.0 + 0.5), 0 at every other cell.
+ * 32767 survives the uint16 rows and the int16 views of them; gz_dataset_pi divides a row by
+ * its own sum, so the scale cancels; the largest entry is at least 146, so no row is empty.
+ * Unchanged: d_root_q, the exported tree (raw visits, the root's stored row), a board that is
+ * over (move -1, the zero row).
+ * Workspace: the caller allocates the flag-clear size (plus gz_puct_sym_bytes(rows) with
+ * GZ_PUCT_LEAF_SYM) rounded up to 256, plus gz_puct_gumbel_bytes(n, S, max_considered): gs
+ * f64 [n][225], then the tables seq(m', S), m' = 1..max_considered, int16, which gz_puct_begin
+ * writes.  With the flag clear nothing past the flag-clear size is touched.
+ * Honoured by gz_puct_begin / select / backup / finish (begin notes the search with the
+ * workspace), gz_puct_search and gz_selfplay_puct_run(_active); with every precision.
+ * GZ_ERR_ARG before any launch: max_considered outside [1, 32]; c_visit not finite or outside
+ * [0, 1e4], c_scale outside [0, 1e3], gumbel_scale outside [0, 8]; the flag together with
+ * GZ_PUCT_ROOT_NOISE, GZ_PUCT_LEAF_BATCH, GZ_PUCT_PLAYOUT_CAP or GZ_PUCT_FORCED_PLAYOUTS; the
+ * flag in gz_selfplay_puct_rounds(_active) and gz_puct_match_run; gz_puct_reroot on a
+ * workspace begun with the flag (an inherited root has no schedule). */
+#define GZ_PUCT_GUMBEL 32
+#define GZ_PUCT_GUMBEL_MAX_CONSIDERED 32
+#define GZ_PUCT_GUMBEL_ROW_SCALE 32767
+typedef struct gz_puct_gumbel_params {
+    gz_puct_forced_params forced; /* base; none of its inner fields is read */
+    int32_t max_considered;       /* 1..32 (16) */
+    int32_t pad;
+    double c_visit;               /* 50 */
+    double c_scale;               /* 0.5 on q in [-1, 1] */
+    double gumbel_scale;          /* 1; 0: no noise */
+} gz_puct_gumbel_params;          /* 112 bytes */
+size_t gz_puct_gumbel_bytes(int32_t n, int32_t num_simulations, int32_t max_considered);
+/* The same code on the host, no GPU.  sequence: out[S].  root: empty225[c] != 0 = an empty
+ * cell; gs_out[225]; returns GZ_OK.  policy: visits[c] == 0 means no child at c (W[c] is then
+ * not read); every cell counts as empty, so a stone carries a prior that is not ok (0.0); pi_out
+ * and row_out [225], either may be NULL. */
+int gz_puct_gumbel_sequence_host(int32_t m, int32_t num_simulations, int16_t* out);
+int gz_puct_gumbel_root_host(uint64_t seed, int64_t game_id, int32_t ply, const double prior[225],
+                             const uint8_t* empty225, int32_t max_considered, double gumbel_scale,
+                             double gs_out[225]);
+int gz_puct_gumbel_policy_host(const double prior[225], const double W[225], const int32_t visits[225], double v0,
+                               double c_visit, double c_scale, double pi_out[225], int32_t row_out[225]);
 /* Leaf symmetry (opt-in; AlphaGo Zero's random board symmetry per leaf evaluation): with
  * GZ_PUCT_LEAF_SYM in flags every leaf x is evaluated as
  *   t = gz_pv_sym(seed, x);  (prior_y, value) = gz_pv_forward(T_t(x));  prior[c] mapped back
@@ -677,8 +750,10 @@ int gz_selfplay_puct_layout(int32_t n_slots, int32_t num_simulations, int32_t le
  *                     the old one).  Lock-step and batched searches rebuild every tree
  *                     each ply and pass move_trees = 0.
  * What the hole held (its old tree and rows) is dead and stays as it is, as does the
- * filler's old place.  d_order [n_active]: the new index of each old slot (the identity
- * except at the pairs); *d_n_active = a; the caller then runs the first a slots
+ * filler's old place.  The gs rows of a GZ_PUCT_GUMBEL engine (lock-step only) are not
+ * moved: they are dead between plies, every ply's root preparation writes its own.
+ * d_order [n_active]: the new index of each old slot (the identity except at the pairs);
+ * *d_n_active = a; the caller then runs the first a slots
  * (gz_selfplay_puct_run_active / _rounds_active).  No active slot below a, or no idle
  * one: only d_order and d_n_active are written.  d_puct_workspace: the self-play
  * workspace of n_slots slots; d_workspace: gz_selfplay_puct_compact_workspace_bytes(n_slots).

@@ -41,6 +41,19 @@ noise on and off.
     python tools/puct_bench.py --noise 0.3,0.25 --reuse --precisions f16x3 --steps 5 \\
         --lockstep-library parent/libgzero.so --out profiles/puct/noise_bench.json
 
+--gumbel M measures the Gumbel root with sequential halving
+(SelfPlayEngine(gumbel_considered=M), lock-step): a round of the parent build
+(--lockstep-library), of this build with the flag clear and with it set, child processes
+taking turns; the select / forward / backup / finish launches of a step-API search with and
+without the flag (device events); moves/s at the budgets of --gumbel-sims, measured on a
+lock-step engine and as the arithmetic slots / ((S + 1) x round); and the mean
+KL(pi' || prior) of the rows recorded by --gumbel-kl-slots games at --gumbel-kl-sims
+simulations, at the init weights and with the policy FC scaled (--policy-scale).  No claim
+about playing strength.
+
+    python tools/puct_bench.py --gumbel 16 --precisions f16x3 --steps 7 \\
+        --lockstep-library parent/libgzero.so --out profiles/puct/gumbel_bench.json
+
 --forced K measures forced playouts and policy-target pruning
 (SelfPlayEngine(forced_playouts=K)) the way --noise measures the noise, with the root noise
 of --forced-noise on in all three engines: the parent build (--lockstep-library), this build
@@ -155,6 +168,12 @@ ap.add_argument("--forced-noise", default="0.3,0.25", metavar="ALPHA,EPS", help=
 ap.add_argument("--forced-positions", type=int, default=512, help="--forced: positions of the share measurement")
 ap.add_argument("--forced-child", default=None, metavar="MODE:off|K",
                 help="(child) one engine of --forced: lockstep or reuse, the flag clear or forced_playouts=K")
+ap.add_argument("--gumbel", type=int, default=None, metavar="M", help="measure the Gumbel root with sequential halving (see above)")
+ap.add_argument("--gumbel-sims", default="16,32,200", help="--gumbel: the budgets of the moves/s table (comma-separated)")
+ap.add_argument("--gumbel-kl-slots", type=int, default=256, help="--gumbel: games of the KL(pi' || prior) measurement (0: skip)")
+ap.add_argument("--gumbel-kl-sims", type=int, default=32, help="--gumbel: simulations of the KL measurement")
+ap.add_argument("--gumbel-child", default=None, metavar="MODE:off|M",
+                help="(child) one engine of --gumbel: lockstep, the flag clear or gumbel_considered=M")
 ap.add_argument("--leaves", default=None, metavar="K,K,...",
                 help="measure leaf batching (SelfPlayEngine(leaves_per_round=K)) over --sweep-slots (see above)")
 ap.add_argument("--sweep-slots", default="1,8,64,256", help="--leaves: the slot counts (comma-separated)")
@@ -460,6 +479,132 @@ def forced_child():
     if spec != "off":
         kw["forced_playouts"] = float(spec)
     step_child(mode, kw)
+
+
+def gumbel_child():
+    mode, spec = a.gumbel_child.split(":")
+    step_child(mode, {} if spec == "off" else {"gumbel_considered": int(spec)})
+
+
+def spread(xs):
+    return {"median": median(xs), "min": min(xs), "max": max(xs), "n": len(xs)}
+
+
+def gumbel_mode_run(prec):
+    kinds = [("parent", "off", a.lockstep_library), ("gumbel_off", "off", None), ("gumbel_on", str(a.gumbel), None)]
+    out = three_way_run(prec, "lockstep", "--gumbel-child", kinds, "Gumbel root")
+    for r in out.values():
+        r["round_ms"] = spread([x / r["rounds_per_step"] for x in r["step_ms"]])
+    return out
+
+
+def gumbel_kernels(prec):
+    """The launches of a step-API search of --slots mid-game positions, device events around
+    each: per round select, the forward (PuctStepper.evaluate), backup; finish once."""
+    import torch
+    from gzero import device
+    from gzero.selfplay import SelfPlayEngine
+    n, S = a.slots, a.sims
+    w = bench_weights(prec, 1.0)
+    eng = SelfPlayEngine(n_slots=n, num_simulations=S, seed=1, pv_weights=w, search="puct", temp_plies=a.temp_plies)
+    eng.advance(a.burn)
+    st, _ = eng.boards()
+    del eng
+    torch.cuda.empty_cache()
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = f()
+        e1.record()
+        return r, (e0, e1)
+
+    out = {}
+    for name, m in (("flag_clear", None), ("gumbel", a.gumbel)):
+        sp = device.PuctStepper(st, list(range(n)), device.puct_params(S, 1.6, a.temp_plies, 1, prec, gumbel_considered=m))
+        ev = {"select": [], "forward": [], "backup": [], "finish": []}
+        for rnd in range(S + 1):
+            if rnd:
+                ev["select"].append(timed(sp.select)[1])
+            (prior, value), e = timed(lambda: sp.evaluate(w))
+            ev["forward"].append(e)
+            ev["backup"].append(timed(lambda: sp.backup(prior, value))[1])
+        ev["finish"].append(timed(sp.finish)[1])
+        torch.cuda.synchronize()
+        # (round 0's backup is the root's: with the flag it holds the root preparation)
+        ms = {k: [e0.elapsed_time(e1) for e0, e1 in v] for k, v in ev.items()}
+        out[name] = {k: spread(v) for k, v in ms.items()}
+        out[name]["root_backup_ms"] = ms["backup"][0]
+        out[name]["search_ms_sum"] = sum(sum(v) for v in ms.values())
+        del sp
+        torch.cuda.empty_cache()
+        print(f"{prec} {name}: select {out[name]['select']['median']:.4f} ms, forward {out[name]['forward']['median']:.4f}, "
+              f"backup {out[name]['backup']['median']:.4f} (root's {out[name]['root_backup_ms']:.4f}), "
+              f"finish {out[name]['finish']['median']:.4f}")
+    return out
+
+
+def gumbel_moves(prec, S, round_ms_flagged):
+    """Moves/s of a lock-step Gumbel engine at S simulations, measured, and the arithmetic
+    slots / ((S + 1) x the flagged round at --sims)."""
+    import torch
+    from gzero.selfplay import SelfPlayEngine
+    eng = SelfPlayEngine(n_slots=a.slots, num_simulations=S, seed=1, pv_weights=bench_weights(prec, 1.0), search="puct",
+                         temp_plies=a.temp_plies, gumbel_considered=a.gumbel, plies_per_step=1)
+    eng.advance(a.burn)
+    eng.step()
+    ms = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.step()
+        e1.record()
+        torch.cuda.synchronize()
+        assert eng.counters()["moves"] == a.slots
+        ms.append(e0.elapsed_time(e1))
+    del eng
+    torch.cuda.empty_cache()
+    out = {"simulations": S, "considered": a.gumbel, "ply_ms": spread(ms), "round_ms_median": median(ms) / (S + 1),
+           "moves_per_s_measured": a.slots / (median(ms) / 1e3),
+           "moves_per_s_arithmetic": a.slots / ((S + 1) * round_ms_flagged / 1e3)}
+    print(f"{prec} S={S} m={a.gumbel}: {out['moves_per_s_measured']:.0f} moves/s measured, "
+          f"{out['moves_per_s_arithmetic']:.0f} by (S+1) x the flagged round at S={a.sims}")
+    return out
+
+
+def gumbel_kl(prec, scale):
+    """Mean KL(pi' || prior) over the rows a lock-step Gumbel engine records: --gumbel-kl-slots
+    games from the empty board played to the end, pi' = row / sum, prior = the forward's
+    masked row of the record's position.  Descriptive."""
+    import numpy as np
+    from gzero import boards, device
+    from gzero.selfplay import SelfPlayEngine
+    n, S = a.gumbel_kl_slots, a.gumbel_kl_sims
+    w = bench_weights(prec, scale)
+    eng = SelfPlayEngine(n_slots=n, num_simulations=S, seed=1, pv_weights=w, search="puct", temp_plies=a.temp_plies,
+                         gumbel_considered=a.gumbel, game_id_end=n, plies_per_step=10)
+    recs, rows = [], []
+    for _ in range(21):
+        eng.step()
+        if eng.counters()["records"]:
+            recs.append(eng.records().copy())
+            rows.append(eng.visits().copy())
+        if sum(len(r) for r in recs) and len(set(np.concatenate(recs)["game_id"].tolist())) == n:
+            break
+    recs, rows = np.concatenate(recs), np.concatenate(rows).astype(np.float64)
+    kl = []
+    for lo in range(0, len(recs), 4096):
+        r = recs[lo:lo + 4096]
+        _, _, _, prior = device.pv_forward(w, boards.leaf_words(r["black"], r["white"]), want_prior=True)
+        pi = rows[lo:lo + 4096] / rows[lo:lo + 4096].sum(axis=1, keepdims=True)
+        on = pi > 0
+        kl.append(np.where(on, pi * (np.log(np.where(on, pi, 1.0)) - np.log(np.where(on, prior, 1.0))), 0.0).sum(axis=1))
+    kl = np.concatenate(kl)
+    out = {"games": int(len(set(recs["game_id"].tolist()))), "rows": int(len(recs)), "simulations": S,
+           "considered": a.gumbel, "kl_mean": float(kl.mean()), "kl_median": float(np.median(kl)),
+           "kl_max": float(kl.max())}
+    print(f"{prec} policy x{scale:g}: mean KL(pi' || prior) {out['kl_mean']:.5f} over {out['rows']} rows of {out['games']} games")
+    return out
 
 
 def step_child(mode, engine_kw):
@@ -977,6 +1122,44 @@ if a.sym_child is not None:
     sys.exit(0)
 if a.forced_child is not None:
     forced_child()
+    sys.exit(0)
+if a.gumbel_child is not None:
+    gumbel_child()
+    sys.exit(0)
+if a.gumbel is not None:
+    prec = precisions[0]
+    res = {"config": {"slots": a.slots, "simulations": a.sims, "burn_in_plies": a.burn, "temp_plies": a.temp_plies,
+                      "precision": prec, "considered": a.gumbel, "c_visit": 50.0, "c_scale": 0.5, "gumbel_scale": 1.0,
+                      "steps": a.steps,
+                      "timing": "device events around one lock-step step (S+1 rounds); three child processes (parent "
+                                "build, this build with the flag clear and with gumbel_considered) take turns",
+                      "parent_library": "another build (--lockstep-library)" if a.lockstep_library else "this build",
+                      "claims": "cost per round, moves/s as (S+1) rounds per move, and a descriptive KL; nothing "
+                                "about playing strength or learning"},
+           "results": {}}
+    if a.note:
+        res["config"]["note"] = a.note
+    res["results"]["lockstep"] = gumbel_mode_run(prec)
+    flagged = res["results"]["lockstep"]["gumbel_on"]["round_ms_median"]
+    parent = res["results"]["lockstep"]["parent"]["round_ms_median"]
+    res["results"]["kernels"] = gumbel_kernels(prec)
+    res["results"]["moves_per_s"] = {"parent_puct": {"simulations": a.sims,
+                                                     "moves_per_s": a.slots / ((a.sims + 1) * parent / 1e3)}}
+    for S in (int(x) for x in a.gumbel_sims.split(",") if x):
+        res["results"]["moves_per_s"][f"S{S}_m{a.gumbel}"] = gumbel_moves(prec, S, flagged)
+    res["results"]["kl"] = None
+    if a.gumbel_kl_slots > 0:
+        res["results"]["kl"] = {"init_weights": gumbel_kl(prec, 1.0)}
+        for scale in (float(x) for x in a.policy_scale.split(",") if x):
+            res["results"]["kl"][f"policy_fc_x{scale:g}_synthetic"] = gumbel_kl(prec, scale)
+    import torch
+    res["device"] = torch.cuda.get_device_name(0)
+    print("PUCT_GUMBEL_JSON " + json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     sys.exit(0)
 if a.forced is not None:
     prec = precisions[0]
